@@ -13,7 +13,9 @@ The stopping tests are evaluated every step but not taken (CUDAMAT_FLAG_NO_EXIT)
 solve restarts from x0 = 1 every 50 steps so the residual stays far from underflow; each
 restart's extra SpMV is inside the timed region and not counted as a step.
 
-Output: ONE JSON line on rank 0 (see DESIGN.md "Measurement").
+Output: ONE JSON line on rank 0 (see DESIGN.md "Measurement").  A plain run sets up, warms up, times the steps and
+prints the line; `--full` adds the side measurements (CPU baseline, value dictionary, drop-in calls, stream ceilings,
+the other configurations).  `--dump-outputs DIR` writes what the last timed step computed as .npy files.
 """
 import argparse
 import json
@@ -180,9 +182,17 @@ def parse():
     ap.add_argument("--loop", default="pbicgstab", choices=["pbicgstab", "pipelined"],
                     help="pbicgstab: the reference's loop (pbicgstab.cu:45-154), the headline; pipelined: the same "
                          "recurrences re-arranged so that the reductions run beside the SpMVs (SURVEY 8 f4; with --precond: its preconditioned form)")
-    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline, the value-dictionary "
+                         "side figure, the drop-in calls, the measured stream ceilings and the other configurations "
+                         "(each can still be switched off below); without it a run sets up, warms up, times --steps and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64): the iterate x "
+                         "(all rows up to 2^20, else a fixed seeded sample of 2^20 rows, DIR/x_rows.npy) and the solver's "
+                         "stats (DIR/stats.npy: iters, converged, breakdown, half_exit, nrm0, nrm)")
+    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"], help="auto: with --full")
     ap.add_argument("--drop-in", default="auto", choices=["auto", "off"],
-                    help="auto: also time the host-pointer entry point (cudamat_solve = bicgstab(), pbicgstab.h:113) end to end, "
+                    help="auto (with --full): also time the host-pointer entry point (cudamat_solve = bicgstab(), pbicgstab.h:113) end to end, "
                          "twice (one GPU only; the second call reuses the first one's plan)")
     ap.add_argument("--cpu-iters-full", type=int, default=2, help="iterations of the CPU baseline on the full matrix, per OpenMP team size")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED)
@@ -191,7 +201,7 @@ def parse():
                          "box finds the GPU in its low-power state and its first seconds of work run 6-8 %% slower (round 5: "
                          "the first bench.py on a fresh box 175-176 it/s, every later one 181-190); 0 = none")
     ap.add_argument("--other-configs", default="auto", choices=["auto", "off"],
-                    help="auto: after the judged region of the default (headline) invocation on one GPU, also run BASELINE.json's "
+                    help="auto (with --full): after the judged region of the default (headline) invocation on one GPU, also run BASELINE.json's "
                          "other single-GPU configurations -- C3 poisson5, C5 rand50 + ILU(0), C2 mat10000 -- as side sections "
                          "of the same JSON line (`other_configs`)")
     return ap.parse_args()
@@ -522,7 +532,7 @@ def main():
             args.other_configs = "off"
         headline = (args.workload == "rand50" and args.rows == 10_000_000 and args.per_row == 50 and args.precond == "none"
                     and args.loop == "pbicgstab")
-        if out is not None and out.get("n_gpus") == 1 and headline and args.other_configs != "off":
+        if out is not None and out.get("n_gpus") == 1 and headline and args.full and args.other_configs != "off":
             out["other_configs"] = other_configs(args)
     finally:
         sys.stdout.flush()
@@ -553,7 +563,7 @@ def other_configs(args):
         a = copy.copy(args)
         for k, v in over.items():
             setattr(a, k, v)
-        a.cpu_baseline, a.other_configs, a.loop = "off", "off", "pbicgstab"
+        a.cpu_baseline, a.other_configs, a.loop, a.dump_outputs = "off", "off", "pbicgstab", None
         t0 = time.perf_counter()
         try:
             full = run_bench(a)
@@ -563,6 +573,36 @@ def other_configs(args):
         sec["section_seconds"] = time.perf_counter() - t0
         sections[name] = sec
     return sections
+
+
+DUMP_ROWS = 1 << 20     # rows of x that --dump-outputs writes (8 MB): all of them up to this size, else a fixed sample
+DUMP_SEED = 0x5A11
+
+
+def dump_outputs(out_dir, x, st, n, row0, row1, rank, shards, dist):
+    """--dump-outputs: what the last timed step handed its caller -- the iterate x (this rank's rows row0..row1 of n; `shards`
+    ranks hold contiguous slices of it, collected on rank 0) and the solver's stats -- as float64 .npy files on rank 0.
+    The sampled rows depend on n alone, so two runs with the same arguments write the same rows."""
+    import numpy as np
+    if n <= DUMP_ROWS:
+        rows = np.arange(n, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+    xh = x.cpu().numpy()
+    if shards > 1:
+        vals = xh[rows[(rows >= row0) & (rows < row1)] - row0]
+        parts = [None] * shards
+        dist.all_gather_object(parts, vals)
+        vals = np.concatenate(parts)
+    else:
+        vals = xh[rows]
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "x.npy"), vals.astype(np.float64))
+    np.save(os.path.join(out_dir, "x_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "stats.npy"), np.array([st.iters, st.converged, st.breakdown, st.half_exit, st.nrm0, st.nrm],
+                                                         dtype=np.float64))
 
 
 def run_bench(args):
@@ -806,6 +846,9 @@ def run_bench(args):
         dt = time.perf_counter() - t0
         gpu_state = sampler.stop()
         dt = host_allreduce(dt, "max")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, x, st, n, row0, row1, rank, world if (use_dist and not replicas) else 1,
+                         dist if use_dist else None)
 
         # what the output needs to know about the resident solver; it is closed before the drop-in calls below, so that those
         # run like a host program's would -- not beside a second ~50 GB solver of the same matrix -- and draw on the blocks it
@@ -817,7 +860,7 @@ def run_bench(args):
         # The value dictionary as a side figure: the same workload timed -- outside the judged region, one GPU only -- with
         # the 8-bit value indices the library would pick by itself for this matrix (<= 256 distinct values)
         side = None
-        if (world == 1 and not latency_bound and precond == cm.PRECOND_NONE and forced_fp64
+        if (args.full and world == 1 and not latency_bound and precond == cm.PRECOND_NONE and forced_fp64
                 and os.environ.get("CUDAMAT_BENCH_COMPARE", "1") != "0"):
             ctx.set_option("VALUE_DICT", "1")         # (a context reads the environment once; later changes go through set_option)
             s2 = None
@@ -844,8 +887,9 @@ def run_bench(args):
         # example.cpp:364-365): ONE call of cudamat_solve() on HOST arrays -- upload over PCIe, analysis, loop, download --
         # and a second call with the same matrix, which reuses the first one's plan.  Outside the judged region.
         drop_in = None
-        ceil = hbm_ceiling(ctx) if (world == 1 and not latency_bound) else None
-        if world == 1 and args.drop_in != "off" and precond in (cm.PRECOND_NONE, cm.PRECOND_ILU0) and not latency_bound:
+        ceil = hbm_ceiling(ctx) if (args.full and world == 1 and not latency_bound) else None
+        if (args.full and world == 1 and args.drop_in != "off" and precond in (cm.PRECOND_NONE, cm.PRECOND_ILU0)
+                and not latency_bound):
             solver.set_comm(None) if comm is not None else None
             solver.close()
             solver = None
@@ -1078,7 +1122,7 @@ def run_bench(args):
             # what the fabric really carried per launch (PMC), as a rate: the figure to hold against a stream ceiling
             out["roofline"]["moved_gbs"] = traffic / (spmv_ms * 1e-3) / 1e9
             out["roofline"]["moved_over_algorithmic"] = traffic / b_spmv
-        if world == 1 and not latency_bound:
+        if ceil is not None:
             out["roofline"]["measured_stream_ceiling"] = ceil
             out["roofline"]["frac_of_measured_ceiling"] = achieved / ceil["gbs"]
             if sv_mode == 3:
@@ -1097,7 +1141,7 @@ def run_bench(args):
                 out["roofline"]["ms_at_measured_ceilings"] = t_floor
                 out["roofline"]["note_ceilings"] = ("counter bytes of phase 1 / triad ceiling + counter bytes of phase 2 / read ceiling: "
                                                     "the launch pair runs at %.2f of that" % (t_floor / spmv_ms if spmv_ms > 0 else 0.0))
-        if world == 1 and args.cpu_baseline != "off":
+        if args.full and world == 1 and args.cpu_baseline != "off":
             out["cpu_baseline"] = cpu_baseline(args)
     if solver is not None:
         solver.close()

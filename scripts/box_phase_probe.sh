@@ -3,15 +3,16 @@
 # vector kernels, and the device's state -- to tell WHICH launch differs between a 175 it/s box and a 190 it/s box.
 #   gpurun -- bash scripts/box_phase_probe.sh
 R=$(pwd)
-bash scripts/headline_state.sh 1 || exit 1
+HS=$R/bench_runs      # where headline_state.sh writes its line
+bash scripts/headline_state.sh 1 "$HS" || exit 1
 python - <<'PY'
 import torch
 p = torch.cuda.get_device_properties(0)
 print("device: %s  CUs %d  clock %s  L2 %s  mem %d GB" % (p.name, p.multi_processor_count, getattr(p, "clock_rate", None), getattr(p, "L2_cache_size", None), p.total_memory >> 30))
 PY
-python - <<'PY'
-import glob, json
-d = json.loads(open("gpurun_out/headline_state_1.json").read().strip().splitlines()[-1])
+python - "$HS/headline_state_1.json" <<'PY'
+import glob, json, sys
+d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 bdf = (d.get("host_placement") or {}).get("gpu_pci")
 for f in ("pp_dpm_sclk", "pp_dpm_mclk", "pp_dpm_fclk", "pp_dpm_socclk", "current_compute_partition", "current_memory_partition", "vbios_version", "mem_info_vram_total"):
     try:
@@ -19,9 +20,9 @@ for f in ("pp_dpm_sclk", "pp_dpm_mclk", "pp_dpm_fclk", "pp_dpm_socclk", "current
     except OSError as e:
         print(f, "->", type(e).__name__)
 PY
-python - <<'PY'
-import glob, json, os
-d = json.loads(open("gpurun_out/headline_state_1.json").read().strip().splitlines()[-1])
+python - "$HS/headline_state_1.json" <<'PY'
+import glob, json, os, sys
+d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 bdf = (d.get("host_placement") or {}).get("gpu_pci")
 fw = []
 for f in sorted(glob.glob("/sys/bus/pci/devices/%s/fw_version/*" % bdf)):
@@ -48,7 +49,7 @@ export CUDAMAT_BENCH_OTHER_CONFIGS=off
 cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out
 rm -rf $O/trace_boxphase
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_boxphase -- python3 $R/bench.py --steps 100 --warmup 5 --cpu-baseline off --drop-in off --other-configs off > $O/trace_boxphase.json 2> $O/trace_boxphase.err || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_boxphase -- python3 $R/bench.py --full --steps 100 --warmup 5 --cpu-baseline off --drop-in off --other-configs off > $O/trace_boxphase.json 2> $O/trace_boxphase.err || exit 1
 python3 - "$O/trace_boxphase" <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + "/*/*kernel_trace.csv")

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 R=/root/repo; O=$R/gpurun_out
 for r in $(seq ${1:-2}); do for perm in 1 0; do
   rm -rf $O/permab_$perm
-  CUDAMAT_TRSV_PERM=$perm timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/permab_$perm -- python3 $R/bench.py --precond ilu0 --steps 6 --warmup 2 --cpu-baseline off --drop-in off --other-configs off > /dev/null 2>&1
+  CUDAMAT_TRSV_PERM=$perm timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/permab_$perm -- python3 $R/bench.py --full --precond ilu0 --steps 6 --warmup 2 --cpu-baseline off --drop-in off --other-configs off > /dev/null 2>&1
   python3 - $O/permab_$perm $perm $r <<'PY'
 import csv, glob, sys, collections
 d, perm, r = sys.argv[1:4]

@@ -1,12 +1,13 @@
 #!/bin/bash
 # GPU box: counters of the C3 (Poisson 4000 x 2500) SpMV kernel, one rocprofv3 --pmc pass per group
+ROOT=$(cd "$(dirname "$0")/.." && pwd)      # the repository, found before the cd below
 cd /tmp && export TMPDIR=/tmp
 O=/root/repo/gpurun_out
 for kv in "$@"; do export "$kv"; done
 for c in FETCH_SIZE "TCC_HIT_sum TCC_MISS_sum" "SQ_WAVE_CYCLES SQ_WAIT_ANY" "SQ_BUSY_CYCLES SQ_WAVES" "SQ_INSTS_VMEM_RD SQ_INSTS_LDS" "TCC_EA0_RDREQ_sum TCC_REQ_sum" "TCP_TCC_READ_REQ_sum" "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "TA_BUSY_avr TA_TA_BUSY_sum" "TCP_PENDING_STALL_CYCLES_sum" "SQ_INST_LEVEL_VMEM" "SQ_LEVEL_WAVES"; do
   tag=$(echo $c | tr ' ' '_')
   rm -rf $O/pmc3_$tag
-  timeout -k 10 200 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc3_$tag -- python3 /root/repo/bench.py --workload poisson5 --steps 10 --warmup 2 --cpu-baseline off --drop-in off --other-configs off > /dev/null 2>&1 || echo "pass $c failed"
+  timeout -k 10 200 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc3_$tag -- python3 $ROOT/bench.py --full --workload poisson5 --steps 10 --warmup 2 --cpu-baseline off --drop-in off --other-configs off > /dev/null 2>&1 || echo "pass $c failed"
 done
 python3 - <<'PY'
 import csv,glob,collections

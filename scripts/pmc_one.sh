@@ -1,12 +1,13 @@
 #!/bin/bash
 export CUDAMAT_BENCH_OTHER_CONFIGS=off   # the headline alone: no side sections (bench.py other_configs) under a profiler / in an A/B
 # usage: scripts/pmc_one.sh <name> <kernel substring> <bench args...>   (GPU box) -- FETCH_SIZE / WRITE_SIZE of one kernel
+ROOT=$(cd "$(dirname "$0")/.." && pwd)      # the repository, found before the cd below
 cd /tmp && export TMPDIR=/tmp
 name=$1; kern=$2; shift 2
 O=/root/repo/gpurun_out
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf $O/pmc1_${name}_$c
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc1_${name}_$c -- python3 /root/repo/bench.py "$@" --steps 2 --warmup 1 --cpu-baseline off > /dev/null 2>&1 || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc1_${name}_$c -- python3 $ROOT/bench.py --full "$@" --steps 2 --warmup 1 --cpu-baseline off > /dev/null 2>&1 || exit 1
 done
 python3 - "$O" "$name" "$kern" <<'PY'
 import csv,glob,sys

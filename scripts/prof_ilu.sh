@@ -1,13 +1,14 @@
 #!/bin/bash
 export CUDAMAT_BENCH_OTHER_CONFIGS=off   # the headline alone: no side sections (bench.py other_configs) under a profiler / in an A/B
 # kernel-trace of the C5 bench (run on the GPU box); prints the top kernels
+ROOT=$(cd "$(dirname "$0")/.." && pwd)      # the repository, found before the cd below
 cd /tmp && export TMPDIR=/tmp
 O=/root/repo/gpurun_out/prof_ilu_$1
 shift
 rm -rf $O
 env "$@" true
 for kv in "$@"; do export "$kv"; done
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 /root/repo/bench.py --precond ilu0 --steps 4 --warmup 1 --cpu-baseline off > $O.json 2> $O.err || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 $ROOT/bench.py --full --precond ilu0 --steps 4 --warmup 1 --cpu-baseline off > $O.json 2> $O.err || exit 1
 f=$(find $O -name "*kernel_stats.csv" | head -1)
 python3 - "$f" <<'PY'
 import csv,sys

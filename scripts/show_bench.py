@@ -1,4 +1,4 @@
-"""One bench line (a JSON file as bench.py prints it) in four lines: headline, memory placement, device state, side sections."""
+"""One bench line (a JSON file as `bench.py --full` prints it; a plain line has no side sections) in four lines: headline, memory placement, device state, side sections."""
 import json
 import sys
 

@@ -7,7 +7,7 @@ R=/root/repo
 O=$R/gpurun_out
 name=$1; shift
 rm -rf $O/trace_$name
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$name -- python3 $R/bench.py "$@" --cpu-baseline off --drop-in off --other-configs off > $O/trace_$name.json 2> $O/trace_$name.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$name -- python3 $R/bench.py --full "$@" --cpu-baseline off --drop-in off --other-configs off > $O/trace_$name.json 2> $O/trace_$name.err
 python3 - "$O/trace_$name" <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + "/*/*kernel_trace.csv")

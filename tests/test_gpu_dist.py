@@ -427,7 +427,7 @@ def test_bench_line_contract_on_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "CUDAMAT_BENCH_FORMS", "CUDAMAT_VALUE_DICT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rows", "3000000", "--steps", "10", "--warmup", "2",
-                        "--cpu-baseline", "off"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--full", "--cpu-baseline", "off"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -445,6 +445,54 @@ def test_bench_line_contract_on_one_gpu():
     assert d["first_call"]["plan_reused"] == 0 and d["second_call_same_matrix"]["plan_reused"] == 1
     assert d["first_call"]["converged"] and d["first_call"]["max_abs_err"] < 2e-5 and d["first_call"]["tune_s"] >= 0
     assert d["second_call_same_matrix"]["setup_s"] == 0
+
+
+def test_bench_plain_line_and_dumped_outputs(oracle, tmp_path):
+    """a plain one-GPU run (no --full) prints the headline alone -- no side figures, no CPU baseline -- and --dump-outputs
+    writes what the last timed step computed: x on a fixed sample of 2^20 rows (n > 2^20) and the loop's stats.  Two runs
+    with the same arguments write the same arrays, and they are the iterate of the timed loop: the oracle's restatement of
+    pbicgstab.cu:45-154 from x0 = 1 on the same system after the same number of steps (and clearly not after one more or
+    one fewer: this system gains ~1.6 digits per step)."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "CUDAMAT_BENCH_FORMS", "CUDAMAT_VALUE_DICT"):
+        env.pop(k, None)
+    n, steps, seed, outs = 1_500_000, 3, 0x5EED, []
+    for i in range(2):
+        d = str(tmp_path / ("run%d" % i))
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rows", str(n), "--steps", str(steps), "--warmup", "2",
+                            "--dump-outputs", d], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == steps and abs(out["value"] - 1e3 / out["ms_per_step"]) <= 1e-6 * out["value"]
+        for k in ("cpu_baseline", "drop_in", "with_value_dictionary", "other_configs"):
+            assert k not in out, k
+        assert "measured_stream_ceiling" not in out["roofline"]
+        got = {name: np.load(os.path.join(d, name + ".npy")) for name in ("x", "x_rows", "stats")}
+        assert all(a.dtype == np.float64 for a in got.values())
+        rows = got["x_rows"].astype(np.int64)
+        assert got["x"].shape == rows.shape == (1 << 20,) and np.all(np.diff(rows) > 0) and 0 <= rows[0] and rows[-1] < n
+        assert got["stats"][0] == steps                   # one chunk from x0 = 1
+        outs.append(got)
+    for name in ("x", "x_rows", "stats"):
+        np.testing.assert_allclose(outs[1][name], outs[0][name], rtol=1e-12, atol=0)
+    A = oracle.rand_rows(n, 50, seed)
+    b = oracle.spmv(A, oracle.xstar(n, seed + 1))
+    rows = outs[0]["x_rows"].astype(np.int64)
+    ref = {k: oracle.pbicgstab(A, b, maxit=k, tol=0.0) for k in (steps - 1, steps, steps + 1)}
+    assert ref[steps][1].iters == steps
+
+    def dist(k):
+        xo = ref[k][0][rows]
+        return np.abs(outs[0]["x"] - xo).max() / np.abs(xo).max()
+    assert dist(steps) <= 1e-10, dist(steps)
+    assert dist(steps - 1) > 1e-7 and dist(steps + 1) > 1e-7, (dist(steps - 1), dist(steps + 1))
+    np.testing.assert_allclose(outs[0]["stats"][4], ref[steps][1].nrm0, rtol=1e-10)     # ||b - A x0||
+    np.testing.assert_allclose(outs[0]["stats"][5], ref[steps][1].nrm, rtol=1e-3)       # recursive residual after the steps
 
 
 def test_bench_plain_command_launches_its_ranks_and_survives_a_hanging_form():
