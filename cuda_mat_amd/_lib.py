@@ -126,6 +126,12 @@ _SIGS = {
     "cudamat_solver_solve": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                        C.POINTER(Stats)]),
     "cudamat_solver_history": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
+    "cudamat_solver_spmm": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int]),
+    "cudamat_solver_solve_many": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                            C.c_int, _P, C.POINTER(C.c_int)]),
+    "cudamat_solver_history_col": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
+    "cudamat_solve_many": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int,
+                                     C.c_int, C.c_int, C.c_double, _P, C.POINTER(C.c_int)]),
     "cudamat_solve": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int,
                                 C.c_double, C.c_int, _P, C.POINTER(Stats)]),
     "cudamat_plan_cache_clear": (C.c_int, []),

@@ -4,6 +4,7 @@ Names and argument meaning follow pbicgstab.h / mmio_wrapper.h of the reference:
   bicgstab(n, nnz, A, iA, jA, b, maxit, tol, debug)                  pbicgstab.h:113
   bicgstab_d(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug)      pbicgstab.h:116 (overload)
   bicgstab_lu_precond(n, nnz, A, iA, jA, b, maxit, tol, debug)       pbicgstab.h:119
+  bicgstab_many(n, nnz, A, iA, jA, B, maxit, tol, d, x0)             bicgstab / bicgstab_d for the columns of B (new)
   loadMMSparseMatrix(filename, elem_type, csrFormat)                 mmio_wrapper.h:133
   toDenseVector(n, nnz, A, IA)                                       pbicgstab.cu:1101
 Each solver returns (ok, x, dtAlg, stats): `ok` is the reference's bool, x the
@@ -80,6 +81,32 @@ def bicgstab_lu_precond(n, nnz, A, iA, jA, b, maxit, tol, debug=False):
     in stats.converged."""
     x, st = _solve(n, nnz, A, iA, jA, None, None, b, PRECOND_ILU0, LOOP_PBICGSTAB, maxit, tol, debug)
     return True, x, st.t_solve, st
+
+
+def bicgstab_many(n, nnz, A, iA, jA, B, maxit, tol, d=None, x0=None):
+    """bicgstab (d None) / bicgstab_d for every column of B, shape (n, k), in one call (cudamat_solve_many): the same loop
+    (LOOP_PBICGSTAB2, x0 = ones unless given, shape (n, k)), the same plan cache.  Returns (ok, X, dtAlg, stats, form):
+    ok a list of k bools, X of shape (n, k), dtAlg the whole call's loop seconds, stats a list of k Stats, form 1 when the
+    columns ran batched (several per launch) and 0 when column by column."""
+    A, iA, jA = _np(A, np.float64), _np(iA, np.int32), _np(jA, np.int32)
+    B = np.asarray(B, dtype=np.float64)
+    if B.ndim == 1:
+        B = B[:, None]
+    if len(iA) != n + 1 or len(A) < nnz or len(jA) < nnz or B.shape[0] != n:
+        raise ValueError("array sizes do not match n / nnz")
+    k = B.shape[1]
+    Bf = np.asfortranarray(B)
+    d = None if d is None else _np(d, np.float64)
+    x0f = None
+    if x0 is not None:
+        x0f = np.asfortranarray(np.asarray(x0, dtype=np.float64).reshape(n, k))
+    X = np.zeros((n, k), order="F")
+    st = (Stats * max(k, 1))()
+    form = C.c_int(0)
+    check(_lib.lib().cudamat_solve_many(n, nnz, _vp(A), _vp(iA), _vp(jA), _vp(d), k, _vp(Bf), n, _vp(x0f), _vp(X), n,
+                                        PRECOND_NONE, LOOP_PBICGSTAB2, maxit, tol, st, C.byref(form)))
+    stats = [st[j] for j in range(k)]
+    return [bool(s.converged) for s in stats], np.ascontiguousarray(X), (stats[0].t_solve if k else 0.0), stats, form.value
 
 
 def loadMMSparseMatrix(filename, elem_type="d", csrFormat=True):
@@ -365,8 +392,30 @@ class Solver:
                                               C.byref(st)))
         return st
 
-    def history(self, cap=1 << 16):
+    def history(self, cap=1 << 16, col=None):
+        """residual history of the last solve; col=j: of column j of the last solve_many"""
+        if col is not None:
+            return self.history_col(col, cap)
         buf = np.empty(cap)
         cnt = C.c_int()
         check(_lib.lib().cudamat_solver_history(self.h, _vp(buf), cap, C.byref(cnt)))
         return buf[:cnt.value].copy()
+
+    def history_col(self, col, cap=1 << 16):
+        buf = np.empty(cap)
+        cnt = C.c_int()
+        check(_lib.lib().cudamat_solver_history_col(self.h, int(col), _vp(buf), cap, C.byref(cnt)))
+        return buf[:cnt.value].copy()
+
+    def spmm(self, nrhs, X, ldx, Y, ldy):
+        """Y = (A + diag d) X for nrhs column-major device blocks (leading dimensions ldx, ldy)"""
+        check(_lib.lib().cudamat_solver_spmm(self.h, int(nrhs), _ptr(X), int(ldx), _ptr(Y), int(ldy)))
+
+    def solve_many(self, nrhs, B, ldb, X, ldx, precond=PRECOND_NONE, loop=LOOP_PBICGSTAB, maxit=2000, tol=1e-8, flags=0):
+        """nrhs right-hand sides (column-major device blocks): returns (list of Stats, form) -- form 1 batched, 0 column by
+        column"""
+        st = (Stats * max(int(nrhs), 1))()
+        form = C.c_int(0)
+        check(_lib.lib().cudamat_solver_solve_many(self.h, int(nrhs), _ptr(B), int(ldb), _ptr(X), int(ldx), precond, loop,
+                                                   maxit, tol, flags, st, C.byref(form)))
+        return [st[j] for j in range(int(nrhs))], form.value

@@ -78,6 +78,8 @@ const Option kOptions[] = {
     OPT_FLAG("SHARDED_ONE_DEVICE", sharded_one_device,
              "1: cudamat_solve_sharded with every rank on device 0 and host-synchronised copies in place of RCCL (debugging aid)"),
     OPT_FLAG("PLAN_CACHE", plan_cache, "0: cudamat_solve does not keep the solver of its last call"),
+    OPT_ENUM("MANY_FORM", many_form, "auto=0,batched=1,columns=2",
+             "several right-hand sides: batched (one SpMM per step for up to 8 columns) / columns (one solve per column); auto: the faster as timed at the first solve"),
     {"TEST_COMM_FAIL", K_FAIL, nullptr, nullptr, 0, 0, nullptr, "rank:k -- fault injection: that rank's k-th all-reduce reports an error (tests)"},
 };
 

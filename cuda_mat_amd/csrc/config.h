@@ -60,6 +60,8 @@ struct Config {
     int sharded_one_device = 0;   // SHARDED_ONE_DEVICE 1: cudamat_solve_sharded with every rank on device 0, host-synchronised copies for RCCL
     // ---- drop-in entry point
     int plan_cache = 1;           // PLAN_CACHE         0: cudamat_solve does not keep the solver of its last call
+    // ---- several right-hand sides
+    int many_form = 0;            // MANY_FORM          auto | batched | columns: how cudamat_solver_solve_many runs its columns (0: by timing)
     // ---- fault injection (tests)
     int fail_rank = -1, fail_call = -1;   // TEST_COMM_FAIL = rank:k   that rank's k-th all-reduce reports an error
 

@@ -258,6 +258,7 @@ struct HostSystem {
     const double *A;
     const int *iA, *jA;
     const double *d, *x0, *b;
+    int nrhs = 1;         // columns of b and x0 (n each, contiguous): cudamat_solve_many
 };
 
 // ---- a call whose shape matches the cached solver's: upload into scratch arrays, compare on the device, reuse or rebuild
@@ -281,8 +282,8 @@ int build_or_reuse_candidate(cudamat_ctx *ctx, const Config &cfg, const HostSyst
             up.add(d_rp, h.iA, sizeof(int) * ((size_t)n + 1));            // pbicgstab.cu:313-315
             up.add(d_ci, h.jA, sizeof(int) * (size_t)nnz);
             up.add(d_val, h.A, sizeof(double) * (size_t)nnz);
-            up.add(d_b, h.b, sizeof(double) * (size_t)n);
-            if (h.x0) up.add(d_x, h.x0, sizeof(double) * (size_t)n);
+            up.add(d_b, h.b, sizeof(double) * (size_t)n * (size_t)h.nrhs);
+            if (h.x0) up.add(d_x, h.x0, sizeof(double) * (size_t)n * (size_t)h.nrhs);
             if (h.d) up.add(d_d, h.d, sizeof(double) * (size_t)n);
             if ((rc = up.start(ctx->device))) break;
             if ((rc = up.finish())) break;
@@ -399,8 +400,8 @@ int build_beside_upload(cudamat_ctx *ctx, const Config &cfg, const HostSystem &h
                 e0 = (size_t)cut;
             }
         }
-        if (h.b) up.add(d_b, h.b, sizeof(double) * (size_t)n);
-        if (h.x0) up.add(d_x, h.x0, sizeof(double) * (size_t)n);
+        if (h.b) up.add(d_b, h.b, sizeof(double) * (size_t)n * (size_t)h.nrhs);
+        if (h.x0) up.add(d_x, h.x0, sizeof(double) * (size_t)n * (size_t)h.nrhs);
         if (h.d) up.add(d_d, h.d, sizeof(double) * (size_t)n);
         const int m_all = up.mark();
         do {
@@ -502,9 +503,10 @@ int build_beside_upload(cudamat_ctx *ctx, const Config &cfg, const HostSystem &h
     return CUDAMAT_OK;
 }
 
-// one attempt (the caller holds g_cache.mu)
+// one attempt (the caller holds g_cache.mu).  many: cudamat_solve_many -- h.nrhs columns solved by cudamat_solver_solve_many,
+// `out` then has h.nrhs entries
 int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, int precond, int loop, int maxit, double tol, int debug,
-                      double *x, cudamat_stats *out)
+                      double *x, cudamat_stats *out, bool many = false, int *form = nullptr)
 {
     const int n = h.n, nnz = h.nnz, base = h.base;
     const double t0 = now_s();
@@ -527,8 +529,8 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
     memset(&st, 0, sizeof(st));
     double t_up = 0.0;
     do {
-        if ((rc = cudamat_malloc(ctx, sizeof(double) * (size_t)n, (void **)&d_b))) break;
-        if ((rc = cudamat_malloc(ctx, sizeof(double) * (size_t)n, (void **)&d_x))) break;
+        if ((rc = cudamat_malloc(ctx, sizeof(double) * (size_t)n * (size_t)h.nrhs, (void **)&d_b))) break;
+        if ((rc = cudamat_malloc(ctx, sizeof(double) * (size_t)n * (size_t)h.nrhs, (void **)&d_x))) break;
         if (h.d && (rc = cudamat_malloc(ctx, sizeof(double) * (size_t)n, (void **)&d_d))) break;
         if (candidate) {
             if ((rc = build_or_reuse_candidate(ctx, cfg, h, d_b, d_x, d_d, &s, &reused, &t_up))) break;
@@ -546,8 +548,13 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
             printf("csrilu0 (HIP, level-scheduled) time(s) = %10.8f \n", s->t_factor);            // :355,363
         }
         int flags = (debug ? CUDAMAT_FLAG_DEBUG : 0) | (h.x0 ? 0 : CUDAMAT_FLAG_X0_ONES);
-        if ((rc = cudamat_solver_solve(s, d_b, d_x, precond, loop, maxit, tol, flags, &st))) break;
-        if ((rc = cudamat_d2h(ctx, x, d_x, sizeof(double) * (size_t)n))) break;            // :381
+        if (many) {
+            if ((rc = cudamat_solver_solve_many(s, h.nrhs, d_b, n, d_x, n, precond, loop, maxit, tol, flags, out, form))) break;
+            st = out[0];
+        } else if ((rc = cudamat_solver_solve(s, d_b, d_x, precond, loop, maxit, tol, flags, &st))) {
+            break;
+        }
+        if ((rc = cudamat_d2h(ctx, x, d_x, sizeof(double) * (size_t)n * (size_t)h.nrhs))) break;            // :381
     } while (0);
     char saved[512];
     strncpy(saved, cudamat_last_error(), sizeof(saved) - 1);
@@ -581,7 +588,16 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
     }
     if (rc) set_error("%s", saved);
     st.t_total = now_s() - t0;
-    if (out) *out = st;
+    if (many) {
+        for (int j = 0; j < h.nrhs && rc == CUDAMAT_OK; j++) {
+            out[j].t_upload = st.t_upload;
+            out[j].plan_reused = st.plan_reused;
+            if (reused) { out[j].t_setup = 0.0; out[j].t_tune = 0.0; }
+            out[j].t_total = st.t_total;
+        }
+    } else if (out) {
+        *out = st;
+    }
     return rc;
 }
 
@@ -612,6 +628,58 @@ extern "C" int cudamat_solve(int n, int nnz, const double *A, const int *iA, con
         rc = solve_host_locked(cfg, h, false, precond, loop, maxit, tol, debug, x, out);
     }
     return rc;
+}
+
+extern "C" int cudamat_solve_many(int n, int nnz, const double *A, const int *iA, const int *jA, const double *d, int nrhs,
+                                  const double *B, int ldb, const double *x0, double *X, int ldx, int precond, int loop, int maxit,
+                                  double tol, cudamat_stats *out, int *form)
+{
+    // every argument is checked before a device is touched
+    if (form) *form = 0;
+    CM_ARG(nrhs >= 0, "nrhs < 0");
+    CM_ARG(ldb >= n && ldx >= n, "leading dimension below n");
+    if (nrhs == 0) return CUDAMAT_OK;
+    CM_ARG(B && X, "null pointer");
+    CM_ARG(n > 0 && nnz >= 0 && A && iA && jA, "null pointer or empty system");
+    CM_ARG(maxit >= 0, "maxit");
+    const int base = iA[0];
+    CM_ARG(base == 0 || base == 1, "iA[0] must be 0 or 1");
+    CM_ARG(iA[n] - base == nnz, "nnz != iA[n] - iA[0]");
+    // the device side wants n-long columns back to back
+    std::vector<double> b_packed, x0_packed, x_packed;
+    const double *b = B, *x0p = x0;
+    if (ldb != n) {
+        b_packed.resize((size_t)n * (size_t)nrhs);
+        for (int j = 0; j < nrhs; j++) memcpy(&b_packed[(size_t)j * n], B + (size_t)j * ldb, sizeof(double) * (size_t)n);
+        b = b_packed.data();
+    }
+    if (x0 && ldx != n) {
+        x0_packed.resize((size_t)n * (size_t)nrhs);
+        for (int j = 0; j < nrhs; j++) memcpy(&x0_packed[(size_t)j * n], x0 + (size_t)j * ldx, sizeof(double) * (size_t)n);
+        x0p = x0_packed.data();
+    }
+    double *x = X;
+    if (ldx != n) {
+        x_packed.resize((size_t)n * (size_t)nrhs);
+        x = x_packed.data();
+    }
+    std::vector<cudamat_stats> st((size_t)nrhs);
+    Config cfg = config_from_env();
+    cfg.pb_place = cfg.pb_place >= 2 ? 1 : 0;                    // (as cudamat_solve)
+    HostSystem h{n, nnz, base, (int64_t)n, A, iA, jA, d, x0p, b};
+    h.nrhs = nrhs;
+    std::lock_guard<std::mutex> cache_lock(g_cache.mu);
+    int rc = solve_host_locked(cfg, h, true, precond, loop, maxit, tol, 0, x, st.data(), true, form);
+    if (rc == CUDAMAT_ERR_NOMEM) {
+        cache_drop_locked();
+        pool_trim();
+        rc = solve_host_locked(cfg, h, false, precond, loop, maxit, tol, 0, x, st.data(), true, form);
+    }
+    if (rc) return rc;
+    if (x != X)
+        for (int j = 0; j < nrhs; j++) memcpy(X + (size_t)j * ldx, x + (size_t)j * n, sizeof(double) * (size_t)n);
+    if (out) memcpy(out, st.data(), sizeof(cudamat_stats) * (size_t)nrhs);
+    return CUDAMAT_OK;
 }
 
 // cudamat_solver_create from HOST arrays: the same staged creation, run beside the upload (what cudamat_solve does for its

@@ -1,0 +1,366 @@
+// loops_batch.hip -- several right-hand sides for one resident matrix: cudamat_solver_spmm, cudamat_solver_solve_many,
+// cudamat_solver_history_col.
+//
+// Each column is an INDEPENDENT run of the reference loop (pbicgstab.cu:45-154; :581-754 for the (A0 + I d) variant) with its
+// own rho, alpha, omega, stopping tests, breakdown guard and history; nothing of one column enters another (this is not
+// block-BiCGSTAB).  The batched form runs up to 8 columns through the same launches: per iteration
+//   k_update_p_b | SpMM (+ rw.v) | k_half_b | SpMM (+ t.r, t.t; half-step tests in its prologue) | k_full_b
+// with the vectors interleaved (batch.h), so each SpMM streams the matrix once for all of them.  The host loop is run_host_loop's
+// (loops.hip): iteration k is enqueued while the progress word of iteration k - kLag, (k+1) << 32 | every column stopped, is
+// looked at; a stopped column is frozen by the kernels, so the lagged look costs no accuracy.
+// Form choice (MANY_FORM = auto): the first batched solve of a solver times a few iterations of the batched loop (K columns)
+// against the same number of iterations of the loop a single solve uses (cudamat_solver_solve, which picks the one- or
+// three-launch loops of small systems), and runs batched only when that is faster than kc single solves.  Everything the batched
+// form does not cover (preconditioners, the pipelined loop, sharded solvers, the DEBUG / PROFILE flags) and a failed allocation
+// of its buffers run column by column: cudamat_solver_solve once per column, bit for bit what a caller's loop would do.
+#include <chrono>
+#include <math.h>
+#include <string.h>
+
+#include "batch.h"
+#include "solver.h"
+
+using namespace cm;
+
+static double now_s()
+{
+    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+namespace cm {
+
+void many_release(cudamat_solver *s)
+{
+    double **vs[] = {&s->m_r, &s->m_rw, &s->m_p, &s->m_v, &s->m_t, &s->m_b, &s->m_x, &s->m_parts_full, &s->m_parts_rv,
+                     &s->m_parts_half, &s->m_parts_tt, &s->m_hist};
+    for (double **q : vs) {
+        if (*q) CM_DROP(hipFree(*q));
+        *q = nullptr;
+    }
+    if (s->m_st) CM_DROP(hipFree(s->m_st));
+    s->m_st = nullptr;
+    s->m_cap = 0;
+    s->m_hist_bytes = 0;
+}
+
+}  // namespace cm
+
+namespace {
+
+int pow2_cols(int kc) { return kc <= 1 ? 1 : kc <= 2 ? 2 : kc <= 4 ? 4 : 8; }
+int log2_cols(int K) { return K == 1 ? 0 : K == 2 ? 1 : K == 4 ? 2 : 3; }
+
+int64_t many_rows(const cudamat_solver *s)
+{
+    int64_t rows = s->n_pad > s->n ? s->n_pad : s->n;
+    if (s->n_cols > rows) rows = s->n_cols;
+    return rows > 0 ? rows : 1;
+}
+
+// the interleaved buffers for K columns: seven vectors (r, rw, p, v, t, b, x), the partial sums, the K loop states.
+// CUDAMAT_ERR_NOMEM leaves nothing allocated.
+int ensure_many(cudamat_solver *s, int K)
+{
+    if (s->m_cap >= K) return CUDAMAT_OK;
+    hipStream_t st = s->ctx->stream;
+    CM_HIP(hipStreamSynchronize(st));
+    many_release(s);
+    const size_t nb = sizeof(double) * (size_t)K * (size_t)many_rows(s);
+    double **vs[] = {&s->m_r, &s->m_rw, &s->m_p, &s->m_v, &s->m_t, &s->m_b, &s->m_x};
+    int rc = CUDAMAT_OK;
+    for (double **q : vs) {
+        if ((rc = dev_alloc((void **)q, nb))) break;
+        if ((rc = CM_RC(hipMemsetAsync(*q, 0, nb, st)))) break;
+    }
+    const size_t pv = sizeof(double) * 2 * (size_t)K * kVecGridMax, ps = sizeof(double) * 2 * (size_t)K * kSpmvGridMax;
+    if (!rc) rc = dev_alloc((void **)&s->m_parts_full, pv);
+    if (!rc) rc = dev_alloc((void **)&s->m_parts_half, pv);
+    if (!rc) rc = dev_alloc((void **)&s->m_parts_rv, ps);
+    if (!rc) rc = dev_alloc((void **)&s->m_parts_tt, ps);
+    if (!rc) rc = dev_alloc((void **)&s->m_st, sizeof(LoopState) * (size_t)K);
+    if (rc) {
+        CM_DROP(hipStreamSynchronize(st));
+        many_release(s);
+        return rc;
+    }
+    s->m_cap = K;
+    return CUDAMAT_OK;
+}
+
+SpmmArgs spmm_args(const cudamat_solver *s, const double *x, double *y)
+{
+    SpmmArgs a{};
+    a.n = s->n; a.rp = s->rp; a.ci = s->ci; a.val = s->val;
+    a.x = x; a.d = s->d; a.xd = x;
+    a.alpha = 1.0; a.beta = 0.0; a.y = y;
+    a.dot = 0; a.w = nullptr; a.parts = nullptr;
+    a.check = CHECK_NONE; a.half = nullptr; a.half_count = 0;
+    return a;
+}
+
+// One batch of kc <= K columns (K a power of two, the rest padding that starts stopped).  B / X column-major with leading
+// dimensions ldb / ldx; B == NULL: m_b and m_x are already filled (the timing of the form choice), X == NULL: the iterate stays
+// in m_x.  fin receives the K final states; hist_out (kc vectors, or NULL) the columns' residual histories.
+int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, double *X, int64_t ldx, int loop, int maxit,
+              double tol, int flags, LoopState *fin, std::vector<double> *hist_out, double *t_loop)
+{
+    hipStream_t st = s->ctx->stream;
+    const int n = s->n;
+    const int L = s->plan.lanes;
+    // residual history: as Solve::setup (loops.hip), per column
+    const long long want = (long long)(loop != CUDAMAT_LOOP_PBICGSTAB2 ? 2 : 1) * (maxit > 0 ? maxit : 1);
+    const int need = (int)(want < (1LL << 20) ? want : (1LL << 20));
+    double *hist = nullptr;
+    if (hist_out) {
+        const size_t bytes = sizeof(double) * (size_t)K * (size_t)need;
+        if (bytes > s->m_hist_bytes) {
+            if (s->m_hist) { CM_HIP(hipStreamSynchronize(st)); CM_DROP(hipFree(s->m_hist)); s->m_hist = nullptr; s->m_hist_bytes = 0; }
+            CM_TRY(dev_alloc((void **)&s->m_hist, bytes));
+            s->m_hist_bytes = bytes;
+        }
+        hist = s->m_hist;
+        CM_HIP(hipMemsetAsync(hist, 0xFF, bytes, st));              // NaN fill
+    }
+    BatchArgs la{s->m_st, hist, need, loop, (flags & CUDAMAT_FLAG_NO_EXIT) ? 1 : 0, s->snap_dev, kRing, 0};
+    for (int i = 0; i < kRing; i++) s->snap_host[i] = 0ULL;
+    const double t0 = now_s();
+    if (B) {
+        CM_TRY(launch_batch_in(st, K, kc, n, n, B, ldb, 0.0, s->m_b));
+        if (flags & CUDAMAT_FLAG_X0_ONES) CM_TRY(launch_fill(st, (int64_t)K * n, 1.0, s->m_x));
+        else CM_TRY(launch_batch_in(st, K, kc, n, n, X, ldx, 0.0, s->m_x));
+    }
+    // r = A x0; r = b - r, rw = r, p = r; the states                                        pbicgstab.cu:67-74 / :645-659
+    CM_TRY(launch_spmm(st, L, K, spmm_args(s, s->m_x, s->m_r)));
+    int np_full = 0, np_half = 0, np_spmm = 0, rpb = 0;
+    spmm_partition(L, n, &np_spmm, &rpb);
+    CM_TRY(launch_init_b(st, K, n, s->m_b, s->m_r, s->m_rw, s->m_p, s->m_parts_full, &np_full));
+    CM_TRY(launch_init_finish_b(st, K, kc, s->m_st, s->m_parts_full, np_full, tol));
+    for (int k = 0; k < maxit; k++) {
+        if (k >= kLag) {              // lagged look at the progress word of iteration k - kLag (run_host_loop, loops.hip)
+            const int j = k - kLag;
+            volatile unsigned long long *slot = &s->snap_host[j % kRing];
+            unsigned long long w = *slot;
+            if ((unsigned)(w >> 32) != (unsigned)(j + 1)) {
+                const double t_wait = now_s();
+                while ((unsigned)((w = *slot) >> 32) != (unsigned)(j + 1)) {
+                    __builtin_ia32_pause();
+                    if (now_s() - t_wait > 30.0) {
+                        const double t_drain = now_s();
+                        while (hipStreamQuery(st) == hipErrorNotReady && now_s() - t_drain < 5.0) __builtin_ia32_pause();
+                        set_error("batched iteration %d did not report progress within 30 s", j);
+                        return CUDAMAT_ERR_HIP;
+                    }
+                }
+            }
+            if ((unsigned)(w & 0xffffffffULL) != 0u) break;    // every column has stopped
+        }
+        la.k = k;
+        // rho, beta, full-step tests, p = r + beta (p - omega v)                            :80-89
+        CM_TRY(launch_update_p_b(st, K, la, s->m_parts_full, np_full, n, s->m_r, s->m_p, s->m_v));
+        // v = A p, rw.v                                                                       :104-106
+        SpmmArgs a1 = spmm_args(s, s->m_p, s->m_v);
+        a1.dot = 1; a1.w = s->m_rw; a1.parts = s->m_parts_rv; a1.loop = la;
+        CM_TRY(launch_spmm(st, L, K, a1));
+        // alpha, r -= alpha v, ||r||                                                          :107-111
+        CM_TRY(launch_half_b(st, K, la, s->m_parts_rv, np_spmm, n, s->m_r, s->m_v, s->m_parts_half, &np_half));
+        // half-step tests; t = A s (s = r), (t.r, t.t)                                        :116, :132-136
+        SpmmArgs a2 = spmm_args(s, s->m_r, s->m_t);
+        a2.dot = 2; a2.w = s->m_r; a2.parts = s->m_parts_tt; a2.loop = la;
+        a2.check = CHECK_HALF; a2.half = s->m_parts_half; a2.half_count = np_half;
+        CM_TRY(launch_spmm(st, L, K, a2));
+        // omega, x += alpha p, x += omega s, r -= omega t, (rw.r, ||r||), i++                :110, :137-151
+        CM_TRY(launch_full_b(st, K, la, s->m_parts_tt, np_spmm, n, s->m_x, s->m_r, s->m_r, s->m_t, s->m_rw, s->m_p,
+                             s->m_parts_full, &np_full));
+    }
+    // the last full-step tests; columns that left through the half step still owe x += alpha p (:110)
+    CM_TRY(launch_check_full_b(st, K, la, s->m_parts_full, np_full));
+    CM_TRY(launch_half_exit_b(st, K, s->m_st, n, s->m_p, s->m_x));
+    CM_HIP(hipMemcpyAsync(fin, s->m_st, sizeof(LoopState) * (size_t)K, hipMemcpyDeviceToHost, st));
+    if (X) CM_TRY(launch_batch_out(st, K, kc, n, s->m_x, X, ldx));
+    CM_HIP(hipStreamSynchronize(st));
+    if (t_loop) *t_loop = now_s() - t0;
+    if (hist_out) {
+        for (int j = 0; j < kc; j++) {
+            int c = loop != CUDAMAT_LOOP_PBICGSTAB2 ? 2 * fin[j].it + (fin[j].state == 1 ? 1 : 0) : fin[j].it;
+            if (c > need) c = need;
+            hist_out[j].assign((size_t)c, 0.0);
+            if (c > 0)
+                CM_HIP(hipMemcpy(hist_out[j].data(), hist + (size_t)j * (size_t)need, sizeof(double) * (size_t)c,
+                                 hipMemcpyDeviceToHost));
+        }
+    }
+    return CUDAMAT_OK;
+}
+
+// MANY_FORM = auto: is the batched loop with K columns faster than kc single solves?  Timed once per solver, loop and K
+// (FLAG_NO_EXIT iterations on scratch right-hand sides: b = 1, x0 = 0); what the timing takes is added to *t_tune.
+int prefer_batched(cudamat_solver *s, int K, int kc, int loop, bool *batched, double *t_tune)
+{
+    const double t0 = now_s();
+    hipStream_t st = s->ctx->stream;
+    const int n = s->n;
+    if (s->m_tune_loop != loop) {
+        s->m_tune_loop = loop;
+        s->m_t_single = -1.0;
+        for (double &t : s->m_t_batch) t = -1.0;
+        // a few iterations: enough that launch and set-up overheads do not decide (small systems run ~10 us per iteration)
+        const double it = 4e7 / (double)(s->nnz + 1);
+        s->m_tune_iters = it < 4.0 ? 4 : it > 64.0 ? 64 : (int)it;
+    }
+    const int N = s->m_tune_iters;
+    if (s->m_t_single < 0.0) {
+        CM_TRY(ensure_work(s));
+        CM_TRY(ensure_spmv_mode(s));
+        for (int rep = 0; rep < 2; rep++) {       // (the first run warms up: the loop forms allocate on first use)
+            CM_TRY(launch_fill(st, n, 1.0, s->m_b));
+            CM_TRY(launch_fill(st, n, 0.0, s->m_x));
+            CM_HIP(hipStreamSynchronize(st));
+            const double t = now_s();
+            cudamat_stats dummy;
+            CM_TRY(cudamat_solver_solve(s, s->m_b, s->m_x, CUDAMAT_PRECOND_NONE, loop, rep ? N : 2, 1e-8, CUDAMAT_FLAG_NO_EXIT,
+                                        &dummy));
+            CM_HIP(hipStreamSynchronize(st));
+            s->m_t_single = now_s() - t;
+        }
+    }
+    double &tb = s->m_t_batch[log2_cols(K)];
+    if (tb < 0.0) {
+        LoopState fin[kBatchMax];
+        for (int rep = 0; rep < 2; rep++) {
+            CM_TRY(launch_fill(st, (int64_t)K * n, 1.0, s->m_b));
+            CM_TRY(launch_fill(st, (int64_t)K * n, 0.0, s->m_x));
+            CM_HIP(hipStreamSynchronize(st));
+            const double t = now_s();
+            CM_TRY(run_group(s, K, K, nullptr, 0, nullptr, 0, loop, rep ? N : 2, 1e-8, CUDAMAT_FLAG_NO_EXIT, fin, nullptr,
+                             nullptr));
+            tb = now_s() - t;
+        }
+    }
+    // batched only when clearly faster (3 %: below that the two are within the noise of one timing)
+    *batched = tb < 0.97 * (double)kc * s->m_t_single;
+    if (s->ctx->cfg.verbose)
+        fprintf(stderr, "[cudamat] several right-hand sides: %d iterations, single loop %.3f ms x %d columns, batched (K = %d) "
+                        "%.3f ms -> %s\n", N, 1e3 * s->m_t_single, kc, K, 1e3 * tb, *batched ? "batched" : "columns");
+    *t_tune += now_s() - t0;
+    return CUDAMAT_OK;
+}
+
+void fill_stats(const cudamat_solver *s, const LoopState &f, cudamat_stats *o)
+{
+    memset(o, 0, sizeof(*o));
+    o->iters = f.it;
+    o->half_exit = f.state == 1;
+    o->converged = f.state == 1 || f.state == 2;
+    o->breakdown = f.state == 3;
+    o->nrm0 = f.nrm0;
+    o->nrm = f.nrm;
+    o->loop_form = 0;
+    o->spmv_mode = 0;                    // the SpMM runs on the CSR arrays
+    o->t_setup = s->t_create + s->t_spmv_setup;
+}
+
+}  // namespace
+
+extern "C" int cudamat_solver_spmm(cudamat_solver *s, int nrhs, const double *X, int ldx, double *Y, int ldy)
+{
+    CM_ARG(s, "solver is NULL");
+    CM_ARG(nrhs >= 0, "nrhs < 0");
+    if (nrhs == 0) return CUDAMAT_OK;
+    CM_ARG(X && Y, "null pointer");
+    CM_ARG((int64_t)ldx >= (s->sharded ? (int64_t)s->n : s->n_cols) && ldy >= s->n, "leading dimension below the rows");
+    CM_HIP(hipSetDevice(s->ctx->device));
+    int rc = s->sharded ? CUDAMAT_ERR_NOMEM : ensure_many(s, pow2_cols(nrhs < kBatchMax ? nrhs : kBatchMax));
+    if (rc == CUDAMAT_ERR_NOMEM) {       // sharded, or no room for the interleaved buffers: one SpMV per column
+        for (int j = 0; j < nrhs; j++) CM_TRY(cudamat_solver_spmv(s, X + (size_t)j * ldx, Y + (size_t)j * ldy));
+        return CUDAMAT_OK;
+    }
+    CM_TRY(rc);
+    hipStream_t st = s->ctx->stream;
+    for (int c0 = 0; c0 < nrhs; c0 += kBatchMax) {
+        const int kc = nrhs - c0 < kBatchMax ? nrhs - c0 : kBatchMax;
+        const int K = pow2_cols(kc);
+        CM_TRY(launch_batch_in(st, K, kc, s->n_cols, many_rows(s), X + (size_t)c0 * ldx, ldx, 0.0, s->m_x));
+        CM_TRY(launch_spmm(st, s->plan.lanes, K, spmm_args(s, s->m_x, s->m_t)));
+        CM_TRY(launch_batch_out(st, K, kc, s->n, s->m_t, Y + (size_t)c0 * ldy, ldy));
+    }
+    return CUDAMAT_OK;
+}
+
+extern "C" int cudamat_solver_solve_many(cudamat_solver *s, int nrhs, const double *B, int ldb, double *X, int ldx, int precond,
+                                         int loop, int maxit, double tol, int flags, cudamat_stats *st, int *form)
+{
+    CM_ARG(s, "solver is NULL");
+    CM_ARG(nrhs >= 0, "nrhs < 0");
+    if (form) *form = 0;
+    if (nrhs == 0) return CUDAMAT_OK;
+    CM_ARG(B && X, "null pointer");
+    CM_ARG(ldb >= s->n && ldx >= s->n, "leading dimension below the rows");
+    CM_ARG(maxit >= 0, "maxit");
+    CM_ARG(loop == CUDAMAT_LOOP_PBICGSTAB || loop == CUDAMAT_LOOP_PBICGSTAB2 || loop == CUDAMAT_LOOP_PIPELINED, "loop");
+    CM_HIP(hipSetDevice(s->ctx->device));
+    const double t0 = now_s();
+    const Config &cfg = s->ctx->cfg;
+    std::vector<cudamat_stats> out((size_t)nrhs);
+    std::vector<std::vector<double>> hists((size_t)nrhs);
+    double t_solve = 0.0, t_tune = 0.0;
+    bool any_batched = false;
+    const bool batchable = precond == CUDAMAT_PRECOND_NONE && (loop == CUDAMAT_LOOP_PBICGSTAB || loop == CUDAMAT_LOOP_PBICGSTAB2) &&
+                           !s->sharded && s->n_cols == s->n && s->n > 0 && !(flags & (CUDAMAT_FLAG_DEBUG | CUDAMAT_FLAG_PROFILE));
+    bool room = false;
+    if (batchable && cfg.many_form != 2) {
+        const int rc = ensure_many(s, pow2_cols(nrhs < kBatchMax ? nrhs : kBatchMax));
+        if (rc != CUDAMAT_OK && rc != CUDAMAT_ERR_NOMEM) return rc;
+        room = rc == CUDAMAT_OK;
+        if (!room && cfg.verbose) fprintf(stderr, "[cudamat] no room for the batched loop's buffers: column by column\n");
+    }
+    for (int c0 = 0; c0 < nrhs; c0 += kBatchMax) {
+        const int kc = nrhs - c0 < kBatchMax ? nrhs - c0 : kBatchMax;
+        const int K = pow2_cols(kc);
+        bool batched = room && cfg.many_form == 1;
+        if (room && cfg.many_form == 0) CM_TRY(prefer_batched(s, K, kc, loop, &batched, &t_tune));
+        if (batched) {
+            LoopState fin[kBatchMax];
+            double tl = 0.0;
+            CM_TRY(run_group(s, K, kc, B + (size_t)c0 * ldb, ldb, X + (size_t)c0 * ldx, ldx, loop, maxit, tol, flags, fin,
+                             hists.data() + c0, &tl));
+            t_solve += tl;
+            for (int j = 0; j < kc; j++) fill_stats(s, fin[j], &out[(size_t)(c0 + j)]);
+            any_batched = true;
+            continue;
+        }
+        for (int j = c0; j < c0 + kc; j++) {           // column by column: today's single solve
+            cudamat_stats &sj = out[(size_t)j];
+            CM_TRY(cudamat_solver_solve(s, B + (size_t)j * ldb, X + (size_t)j * ldx, precond, loop, maxit, tol, flags, &sj));
+            t_solve += sj.t_solve;
+            int cnt = 0;
+            std::vector<double> &h = hists[(size_t)j];
+            h.assign((size_t)(s->hist_count > 0 ? s->hist_count : 0), 0.0);
+            if (!h.empty()) CM_TRY(cudamat_solver_history(s, h.data(), (int)h.size(), &cnt));
+        }
+    }
+    s->m_hist_host.swap(hists);
+    const double t_total = now_s() - t0;
+    for (cudamat_stats &o : out) {
+        o.t_solve = t_solve;
+        o.t_total = t_total;
+        o.t_tune += t_tune;
+    }
+    if (st) memcpy(st, out.data(), sizeof(cudamat_stats) * (size_t)nrhs);
+    if (form) *form = any_batched ? 1 : 0;
+    return CUDAMAT_OK;
+}
+
+extern "C" int cudamat_solver_history_col(cudamat_solver *s, int col, double *hist_host, int cap, int *count)
+{
+    CM_ARG(s && count, "null pointer");
+    CM_ARG(col >= 0 && (size_t)col < s->m_hist_host.size(), "no such column in the last cudamat_solver_solve_many");
+    const std::vector<double> &h = s->m_hist_host[(size_t)col];
+    int c = (int)h.size() < cap ? (int)h.size() : cap;
+    if (c < 0) c = 0;
+    if (c > 0) {
+        CM_ARG(hist_host, "hist_host is NULL");
+        memcpy(hist_host, h.data(), sizeof(double) * (size_t)c);
+    }
+    *count = c;
+    return CUDAMAT_OK;
+}

@@ -144,6 +144,20 @@ struct cudamat_solver {
     bool resident_off = false;  // a barrier wait ran into its bound once: keep to the three-launch loop
     int device_cus = 0;         // compute units of the device (0: not asked yet)
     int loop_fallbacks = 0;     // solves redone with the three-launch loop for that reason
+
+    // several right-hand sides (loops_batch.hip): interleaved work vectors of the batched loop, K_cap columns each, allocated at
+    // the first batched solve or SpMM and released with the solver
+    int m_cap = 0;              // columns the buffers below hold (0: not allocated)
+    double *m_r = nullptr, *m_rw = nullptr, *m_p = nullptr, *m_v = nullptr, *m_t = nullptr, *m_b = nullptr, *m_x = nullptr;
+    double *m_parts_full = nullptr, *m_parts_rv = nullptr, *m_parts_half = nullptr, *m_parts_tt = nullptr;
+    cm::LoopState *m_st = nullptr;     // device, m_cap states
+    double *m_hist = nullptr;          // device: per column a history of the batch's length (m_hist_bytes in all)
+    size_t m_hist_bytes = 0;
+    bool m_failed = false;             // the buffers did not fit: solves with several right-hand sides run column by column
+    std::vector<std::vector<double>> m_hist_host;   // per column: the residual history of the last cudamat_solver_solve_many
+    // form choice (MANY_FORM = auto): seconds of m_tune_iters iterations, single loop (< 0: not timed) and batched by log2 K
+    double m_t_single = -1.0, m_t_batch[4] = {-1.0, -1.0, -1.0, -1.0};
+    int m_tune_loop = -1, m_tune_iters = 0;
 };
 
 namespace cm {
@@ -196,4 +210,5 @@ bool trsv_syncfree_active(cudamat_solver *s);
 int trsv_form_code(cudamat_solver *s);           // 0 level launches, 1 dependency-driven, 2 single workgroup in LDS
 void trsv_group_counts(cudamat_solver *s, int *groups_l, int *groups_u);   // hybrid factors: groups of levels (0: not split)
 void trsv_disable_syncfree(cudamat_solver *s);   // sticky: level-by-level kernels from now on
+void many_release(cudamat_solver *s);            // the buffers of the batched loop (loops_batch.hip)
 }  // namespace cm

@@ -267,6 +267,7 @@ extern "C" int cudamat_solver_destroy(cudamat_solver *s)
     sell_free(&s->sell);
     pat_free(&s->pat);
     free_work(s);
+    many_release(s);
     plan_spmv_free(&s->plan);
     void *ptrs[] = {s->rp, s->ci, s->val, s->parts_full, s->parts_rv, s->parts_half, s->parts_tt,
                     s->red, s->st, s->hist};

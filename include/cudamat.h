@@ -326,6 +326,24 @@ int cudamat_solver_solve(cudamat_solver *s, const double *b, double *x, int prec
  * Copies min(cap, available) doubles to the HOST buffer, returns the count in *count. */
 int cudamat_solver_history(cudamat_solver *s, double *hist_host, int cap, int *count);
 
+/* ---- several right-hand sides for one resident system (DESIGN.md section "Several right-hand sides") ------------------ */
+/* Y = (A + diag(d)) X for nrhs columns, column-major device blocks (leading dimensions ldx >= n_cols, ldy >= n_local).  Up
+ * to 8 columns share one pass over the matrix (CSR SpMM with the solver's lanes per row); column j is bit-identical to
+ * cudamat_solver_spmv of column j with the lanes-per-row CSR kernel.  nrhs == 0 is a no-op.                             */
+int cudamat_solver_spmm(cudamat_solver *s, int nrhs, const double *X, int ldx, double *Y, int ldy);
+/* Solve for nrhs right-hand sides B (column-major, ldb >= n) into X (column-major, ldx >= n; the initial guesses on entry
+ * unless CUDAMAT_FLAG_X0_ONES).  Every column is an independent run of cudamat_solver_solve's loop with its own scalars,
+ * stopping tests and history.  PRECOND_NONE with LOOP_PBICGSTAB / LOOP_PBICGSTAB2 on one GPU may run batched (up to 8
+ * columns per launch; a column's result then depends on its own data only, not on the batch); everything else, and the
+ * switch MANY_FORM = columns, runs cudamat_solver_solve once per column.  MANY_FORM = auto (default) times both forms at the
+ * first such call of the solver (per loop and batch width) and takes the faster.  st: nrhs entries or NULL -- per column
+ * iters, half_exit, converged, breakdown, nrm0, nrm, spmv_mode; t_solve / t_total are those of the whole call, t_tune
+ * includes the timing of the form choice.  *form (may be NULL): 1 when columns ran batched, 0 column by column.        */
+int cudamat_solver_solve_many(cudamat_solver *s, int nrhs, const double *B, int ldb, double *X, int ldx, int precond,
+                              int loop, int maxit, double tol, int flags, cudamat_stats *st, int *form);
+/* residual history of column `col` of the last cudamat_solver_solve_many, laid out as cudamat_solver_history's       */
+int cudamat_solver_history_col(cudamat_solver *s, int col, double *hist_host, int cap, int *count);
+
 /* ---- drop-in host-pointer solve ---------------------------------------------------- */
 /* One call = what the three reference entry points do: upload, (analyse, factor,)
  * iterate, download.  d / x0 may be NULL (x0 NULL => ones).  x receives the iterate
@@ -335,6 +353,14 @@ int cudamat_solve(int n, int nnz, const double *A, const int *iA, const int *jA,
                   const double *d, const double *x0, const double *b, int precond,
                   int loop, int maxit, double tol, int debug, double *x,
                   cudamat_stats *st);
+
+/* cudamat_solve for nrhs right-hand sides: B (ldb >= n) and X (ldx >= n) column-major in HOST memory; x0 (NULL => ones)
+ * laid out as X; d may be NULL.  The solve is cudamat_solver_solve_many on the solver cudamat_solve keeps (the same plan
+ * cache: a second call with the same matrix reuses it, st[j].plan_reused).  Arguments are checked before any device is
+ * touched; nrhs == 0 is a successful no-op.  st: nrhs entries or NULL; *form as cudamat_solver_solve_many.              */
+int cudamat_solve_many(int n, int nnz, const double *A, const int *iA, const int *jA, const double *d, int nrhs,
+                       const double *B, int ldb, const double *x0, double *X, int ldx, int precond, int loop, int maxit,
+                       double tol, cudamat_stats *st, int *form);
 
 /* cudamat_solve keeps the solver of its LAST call (CSR copies, SpMV plan, ILU(0) factors: device memory on device 0 --
  * about 16 GB at 1e7 rows x 50 entries, 50 GB with ILU(0)) so that a caller who solves with the same matrix again --

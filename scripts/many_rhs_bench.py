@@ -1,0 +1,103 @@
+"""Several right-hand sides: the batched loop against k sequential solves, per config and batch width K.
+
+One JSON line per (config, K): per-column iterations per second of the batched loop (MANY_FORM = batched) and of K
+sequential Solver.solve calls (both FLAG_NO_EXIT, the same iteration count), the SpMM's time and its fraction of the HBM
+roofline (bytes = 12 nnz + 4 (n + 1) + 8 K (n_cols + n)), and the form MANY_FORM = auto chose.
+    python scripts/many_rhs_bench.py [--c4]        (--c4 adds the 1e7 x 50 random system, ~35 GB of device memory)
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import cuda_mat_amd as cm  # noqa: E402
+
+HBM_PEAK = 8.0e12      # B/s, MI355X
+
+
+def make(ctx, name):
+    if name == "C2_mat10000":
+        err, m, n, nnz, val, row, col = cm.loadMMSparseMatrix(os.path.join(ROOT, "tests", "golden", "mat10000.mtx"))
+        rp, ci, v = ctx.array(row, np.int32), ctx.array(col, np.int32), ctx.array(val)
+        return cm.Solver(ctx, n, n, nnz, rp, ci, v, int(row[0])), n, nnz, (rp, ci, v)
+    if name.startswith("C3_poisson"):
+        nx, ny = 4000, 2500
+        n = nx * ny
+        nnz = int(cm.lib().cudamat_poisson5_nnz(nx, ny))
+        rp, ci, v = ctx.empty(n + 1, np.int32), ctx.empty(nnz, np.int32), ctx.empty(nnz)
+        ctx.gen_poisson5(nx, ny, 0, n, 0, rp, ci, v)
+    else:
+        n = 2_000_000 if name.startswith("rand2e6") else 10_000_000
+        nnz = n * int(cm.lib().cudamat_rand_row_nnz(n, 50))
+        rp, ci, v = ctx.empty(n + 1, np.int32), ctx.empty(nnz, np.int32), ctx.empty(nnz)
+        ctx.gen_rand_rows(n, 50, 0x5EED, 0, n, 0, rp, ci, v)
+    return cm.Solver(ctx, n, n, nnz, rp, ci, v, 0), n, nnz, (rp, ci, v)
+
+
+def run(name, iters):
+    ctx = cm.Context(0)
+    s, n, nnz, keep = make(ctx, name)
+    out = []
+    B, X, Y = ctx.empty(8 * n), ctx.empty(8 * n), ctx.empty(8 * n)
+    for j in range(8):
+        ctx.gen_xstar(0, n, 100 + j, X.ptr + 8 * j * n)
+    s.spmm(8, X, n, B, n)
+    tm = ctx.timer()
+    for K in (1, 2, 4, 8):
+        # SpMM
+        s.spmm(K, X, n, Y, n)
+        reps = 10
+        tm.start()
+        for _ in range(reps):
+            s.spmm(K, X, n, Y, n)
+        tm.stop()
+        ms = tm.elapsed_ms() / reps
+        nbytes = 12 * nnz + 4 * (n + 1) + 8 * K * (n + n)
+        # batched
+        ctx.set_option("MANY_FORM", "batched")
+        check_x = ctx.empty(K * n)
+        check_x.zero()
+        s.solve_many(K, B, n, check_x, n, loop=cm.LOOP_PBICGSTAB, maxit=2, tol=1e-8, flags=cm.FLAG_NO_EXIT)   # warm-up
+        check_x.zero()
+        sts, form_b = s.solve_many(K, B, n, check_x, n, loop=cm.LOOP_PBICGSTAB, maxit=iters, tol=1e-8, flags=cm.FLAG_NO_EXIT)
+        t_b = sts[0].t_solve
+        # K sequential single solves
+        t_s = 0.0
+        for j in range(K):
+            xj = check_x.ptr + 8 * j * n
+            ctx.sync()
+            st = s.solve(B.ptr + 8 * j * n, xj, loop=cm.LOOP_PBICGSTAB, maxit=iters, tol=1e-8, flags=cm.FLAG_NO_EXIT)
+            t_s += st.t_solve
+        # what auto picks (the first auto call of this solver times both forms)
+        ctx.set_option("MANY_FORM", "auto")
+        check_x.zero()
+        sts_a, form_a = s.solve_many(K, B, n, check_x, n, loop=cm.LOOP_PBICGSTAB, maxit=iters, tol=1e-8, flags=cm.FLAG_NO_EXIT)
+        check_x.free()
+        line = {"config": name, "n": n, "nnz": nnz, "K": K, "iters": iters,
+                "batched_col_it_s": K * iters / t_b, "sequential_col_it_s": K * iters / t_s,
+                "gain_per_column": t_s / t_b, "spmm_ms": ms, "spmm_bytes": nbytes,
+                "spmm_roofline": nbytes / (ms * 1e-3) / HBM_PEAK, "auto_form": "batched" if form_a else "columns",
+                "auto_t_tune_s": sts_a[0].t_tune, "auto_col_it_s": K * iters / sts_a[0].t_solve}
+        print(json.dumps(line), flush=True)
+        out.append(line)
+    for a in (B, X, Y):
+        a.free()
+    s.close()
+    ctx.close()
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--c4", action="store_true")
+    a = ap.parse_args()
+    configs = [("C2_mat10000", 500), ("C3_poisson4000x2500", 30), ("rand2e6x50", 30)]
+    if a.c4:
+        configs.append(("C4_rand1e7x50", 10))
+    for name, it in configs:
+        run(name, it)
