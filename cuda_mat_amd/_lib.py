@@ -129,6 +129,8 @@ _SIGS = {
     "cudamat_solver_spmm": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int]),
     "cudamat_solver_solve_many": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                             C.c_int, _P, C.POINTER(C.c_int)]),
+    "cudamat_solver_precond_apply_many": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int]),
+    "cudamat_solver_trsm_kernel": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_int]),
     "cudamat_solver_history_col": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
     "cudamat_solve_many": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_double, _P, C.POINTER(C.c_int)]),

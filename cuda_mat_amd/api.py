@@ -5,6 +5,7 @@ Names and argument meaning follow pbicgstab.h / mmio_wrapper.h of the reference:
   bicgstab_d(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug)      pbicgstab.h:116 (overload)
   bicgstab_lu_precond(n, nnz, A, iA, jA, b, maxit, tol, debug)       pbicgstab.h:119
   bicgstab_many(n, nnz, A, iA, jA, B, maxit, tol, d, x0)             bicgstab / bicgstab_d for the columns of B (new)
+  bicgstab_lu_precond_many(n, nnz, A, iA, jA, B, maxit, tol)         bicgstab_lu_precond for the columns of B (new)
   loadMMSparseMatrix(filename, elem_type, csrFormat)                 mmio_wrapper.h:133
   toDenseVector(n, nnz, A, IA)                                       pbicgstab.cu:1101
 Each solver returns (ok, x, dtAlg, stats): `ok` is the reference's bool, x the
@@ -107,6 +108,29 @@ def bicgstab_many(n, nnz, A, iA, jA, B, maxit, tol, d=None, x0=None):
                                         PRECOND_NONE, LOOP_PBICGSTAB2, maxit, tol, st, C.byref(form)))
     stats = [st[j] for j in range(k)]
     return [bool(s.converged) for s in stats], np.ascontiguousarray(X), (stats[0].t_solve if k else 0.0), stats, form.value
+
+
+def bicgstab_lu_precond_many(n, nnz, A, iA, jA, B, maxit, tol):
+    """bicgstab_lu_precond for every column of B, shape (n, k), in one call (cudamat_solve_many with ILU(0)): the same loop
+    (LOOP_PBICGSTAB, x0 = ones), the same plan cache, the factors computed once.  The columns run one solve each unless the
+    switch CUDAMAT_MANY_PRECOND = batched | auto sends them through the multi-column triangular solves.  Returns
+    (ok, X, dtAlg, stats, form) as bicgstab_many does, with ok[j] True whenever the solve ran (bicgstab_lu_precond's
+    convention; convergence is in stats[j].converged)."""
+    A, iA, jA = _np(A, np.float64), _np(iA, np.int32), _np(jA, np.int32)
+    B = np.asarray(B, dtype=np.float64)
+    if B.ndim == 1:
+        B = B[:, None]
+    if len(iA) != n + 1 or len(A) < nnz or len(jA) < nnz or B.ndim != 2 or B.shape[0] != n:
+        raise ValueError("array sizes do not match n / nnz")
+    k = B.shape[1]
+    Bf = np.asfortranarray(B)
+    X = np.zeros((n, k), order="F")
+    st = (Stats * max(k, 1))()
+    form = C.c_int(0)
+    check(_lib.lib().cudamat_solve_many(n, nnz, _vp(A), _vp(iA), _vp(jA), None, k, _vp(Bf), n, None, _vp(X), n,
+                                        PRECOND_ILU0, LOOP_PBICGSTAB, maxit, tol, st, C.byref(form)))
+    stats = [st[j] for j in range(k)]
+    return [True] * k, np.ascontiguousarray(X), (stats[0].t_solve if k else 0.0), stats, form.value
 
 
 def loadMMSparseMatrix(filename, elem_type="d", csrFormat=True):
@@ -357,6 +381,19 @@ class Solver:
 
     def precond_apply(self, vin, vout):
         check(_lib.lib().cudamat_solver_precond_apply(self.h, _ptr(vin), _ptr(vout)))
+
+    def precond_apply_many(self, nrhs, In, ldin, Out, ldout):
+        """Out_j = U^-1 L^-1 In_j for nrhs column-major device blocks (leading dimensions ldin, ldout): up to 8 columns per
+        pass over the factors; column j is bit-identical to precond_apply of column j"""
+        check(_lib.lib().cudamat_solver_precond_apply_many(self.h, int(nrhs), _ptr(In), int(ldin), _ptr(Out), int(ldout)))
+
+    def trsm_kernel(self, nrhs):
+        """name(s) of the kernel(s) precond_apply_many launches per factor for a batch of nrhs columns, e.g.
+        "L: k_trsm_lds<8, 4>; U: k_trsm_level<8, 4> + k_trsm_small_levels<8, 4>"; "" when the factors are not covered and
+        run column by column"""
+        buf = C.create_string_buffer(160)
+        check(_lib.lib().cudamat_solver_trsm_kernel(self.h, int(nrhs), buf, 160))
+        return buf.value.decode()
 
     def spmv(self, x, y):
         check(_lib.lib().cudamat_solver_spmv(self.h, _ptr(x), _ptr(y)))

@@ -65,6 +65,8 @@ int launch_half_b(hipStream_t s, int K, BatchArgs la, const double *rv, int rv_c
 // x += alpha pw, x += omega s, r -= omega t, (rw.r, r.r), it++; publishes the progress word
 int launch_full_b(hipStream_t s, int K, BatchArgs la, const double *tt, int tt_count, int64_t n, double *x, const double *sv,
                   double *r, const double *t, const double *rw, const double *pw, double *parts, int *nparts);
+// the half-step test of every running column from k_half_b's partials (stride K), where it cannot ride in an SpMM's prologue
+int launch_check_half_b(hipStream_t s, int K, BatchArgs la, const double *half, int half_count);
 // the last full-step test of every running column
 int launch_check_full_b(hipStream_t s, int K, BatchArgs la, const double *full, int full_count);
 // columns that left through the half step: x += alpha pw (pbicgstab.cu:110)

@@ -57,42 +57,6 @@ __device__ __forceinline__ void load_parts(const double *parts, int count, doubl
     block_sum<N>(out, lds);
 }
 
-template <int K>
-__device__ __forceinline__ void load_row(const double *p, int64_t i, double (&v)[K])
-{
-    if constexpr (K == 1) {
-        v[0] = p[i];
-    } else {
-        const double2 *q = (const double2 *)(p + (size_t)i * K);
-#pragma unroll
-        for (int h = 0; h < K / 2; h++) {
-            const double2 t = q[h];
-            v[2 * h] = t.x;
-            v[2 * h + 1] = t.y;
-        }
-    }
-}
-
-// the columns of `mask` only
-template <int K>
-__device__ __forceinline__ void store_row(double *p, int64_t i, const double (&v)[K], unsigned mask)
-{
-    if constexpr (K == 1) {
-        if (mask & 1u) p[i] = v[0];
-    } else {
-        double *row = p + (size_t)i * K;
-#pragma unroll
-        for (int h = 0; h < K / 2; h++) {
-            const unsigned m = (mask >> (2 * h)) & 3u;
-            if (m == 3u) ((double2 *)row)[h] = make_double2(v[2 * h], v[2 * h + 1]);
-            else if (m == 1u) row[2 * h] = v[2 * h];
-            else if (m == 2u) row[2 * h + 1] = v[2 * h + 1];
-        }
-    }
-}
-
-constexpr unsigned kAll = 0xffu;
-
 __device__ __forceinline__ void publish_b(const BatchArgs &la, int all_stopped)
 {
     if (la.snap && leader())
@@ -597,6 +561,20 @@ __global__ __launch_bounds__(kBlock) void k_check_full_b(BatchArgs la, const dou
 int launch_check_full_b(hipStream_t s, int K, BatchArgs la, const double *full, int full_count)
 {
     CM_BATCH_DISPATCH(k_check_full_b, 1, la, full, full_count)
+}
+
+// the half-step tests of every column on their own (one workgroup): the preconditioned loop must decide them before it
+// computes M^-1 r, so they cannot ride in the second SpMM's prologue; the same check_half per column, from the same partials
+template <int K>
+__global__ __launch_bounds__(kBlock) void k_check_half_b(BatchArgs la, const double *half, int half_count)
+{
+    __shared__ double lds[8 * K];
+    for (int j = 0; j < K; j++) (void)check_half(col_args(la, j), ScalarSrc{half + j, half_count, K}, lds);
+}
+
+int launch_check_half_b(hipStream_t s, int K, BatchArgs la, const double *half, int half_count)
+{
+    CM_BATCH_DISPATCH(k_check_half_b, 1, la, half, half_count)
 }
 
 template <int K>

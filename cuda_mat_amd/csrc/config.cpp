@@ -80,6 +80,8 @@ const Option kOptions[] = {
     OPT_FLAG("PLAN_CACHE", plan_cache, "0: cudamat_solve does not keep the solver of its last call"),
     OPT_ENUM("MANY_FORM", many_form, "auto=0,batched=1,columns=2",
              "several right-hand sides: batched (one SpMM per step for up to 8 columns) / columns (one solve per column); auto: the faster as timed at the first solve"),
+    OPT_ENUM("MANY_PRECOND", many_precond, "columns=0,auto=1,batched=2",
+             "several right-hand sides with ILU(0): columns (one preconditioned solve per column, default) / batched (multi-column triangular solves and one SpMM per step for up to 8 columns, where the factors are covered) / auto: the faster as timed at the first such solve; MANY_FORM = columns overrides"),
     {"TEST_COMM_FAIL", K_FAIL, nullptr, nullptr, 0, 0, nullptr, "rank:k -- fault injection: that rank's k-th all-reduce reports an error (tests)"},
 };
 

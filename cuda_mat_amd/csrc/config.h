@@ -62,6 +62,7 @@ struct Config {
     int plan_cache = 1;           // PLAN_CACHE         0: cudamat_solve does not keep the solver of its last call
     // ---- several right-hand sides
     int many_form = 0;            // MANY_FORM          auto | batched | columns: how cudamat_solver_solve_many runs its columns (0: by timing)
+    int many_precond = 0;         // MANY_PRECOND       columns | auto | batched: the same with CUDAMAT_PRECOND_ILU0 (0: column by column; 1: by timing)
     // ---- fault injection (tests)
     int fail_rank = -1, fail_call = -1;   // TEST_COMM_FAIL = rank:k   that rank's k-th all-reduce reports an error
 

@@ -144,6 +144,44 @@ __device__ __forceinline__ bool check_full(const LoopArgs &la, const double (&sc
     return false;
 }
 
+// ------------------------------------------------- interleaved vectors (batch.h)
+// row i of an n x K row-major block (K in {1, 2, 4, 8}): K contiguous doubles, moved 16 bytes at a time for K >= 2
+template <int K>
+__device__ __forceinline__ void load_row(const double *p, int64_t i, double (&v)[K])
+{
+    if constexpr (K == 1) {
+        v[0] = p[i];
+    } else {
+        const double2 *q = (const double2 *)(p + (size_t)i * K);
+#pragma unroll
+        for (int h = 0; h < K / 2; h++) {
+            const double2 t = q[h];
+            v[2 * h] = t.x;
+            v[2 * h + 1] = t.y;
+        }
+    }
+}
+
+// the columns of `mask` only
+template <int K>
+__device__ __forceinline__ void store_row(double *p, int64_t i, const double (&v)[K], unsigned mask)
+{
+    if constexpr (K == 1) {
+        if (mask & 1u) p[i] = v[0];
+    } else {
+        double *row = p + (size_t)i * K;
+#pragma unroll
+        for (int h = 0; h < K / 2; h++) {
+            const unsigned m = (mask >> (2 * h)) & 3u;
+            if (m == 3u) ((double2 *)row)[h] = make_double2(v[2 * h], v[2 * h + 1]);
+            else if (m == 1u) row[2 * h] = v[2 * h];
+            else if (m == 2u) row[2 * h + 1] = v[2 * h + 1];
+        }
+    }
+}
+
+constexpr unsigned kAll = 0xffu;       // store_row: every column
+
 // entries of one stream tile (kernels.h: SpmvPlan.stream_rows); LDS: kStreamNnz products + R+1 row pointers
 constexpr int kStreamNnz = 2048;
 

@@ -1,5 +1,5 @@
-// loops_batch.hip -- several right-hand sides for one resident matrix: cudamat_solver_spmm, cudamat_solver_solve_many,
-// cudamat_solver_history_col.
+// loops_batch.hip -- several right-hand sides for one resident matrix: cudamat_solver_spmm, cudamat_solver_precond_apply_many,
+// cudamat_solver_solve_many, cudamat_solver_history_col.
 //
 // Each column is an INDEPENDENT run of the reference loop (pbicgstab.cu:45-154; :581-754 for the (A0 + I d) variant) with its
 // own rho, alpha, omega, stopping tests, breakdown guard and history; nothing of one column enters another (this is not
@@ -8,17 +8,26 @@
 // with the vectors interleaved (batch.h), so each SpMM streams the matrix once for all of them.  The host loop is run_host_loop's
 // (loops.hip): iteration k is enqueued while the progress word of iteration k - kLag, (k+1) << 32 | every column stopped, is
 // looked at; a stopped column is frozen by the kernels, so the lagged look costs no accuracy.
+// With CUDAMAT_PRECOND_ILU0 and the switch MANY_PRECOND = batched | auto (default: columns) the reference loop runs batched too
+// (Solve::iterate_reference per column, pbicgstab.cu:92-98, :116, :121-127):
+//   k_update_p_b | ph = U^-1 L^-1 p | SpMM v = A ph (+ rw.v) | k_half_b | half-step tests | sh = U^-1 L^-1 r |
+//   SpMM t = A sh (+ t.r, t.t) | k_full_b(x, sv = sh, r, t, rw, pw = ph)
+// with the multi-column triangular solves of trsm.hip: one gathered index yields K doubles, one level hop serves K columns, the
+// factors are read once.  The half-step tests get a launch of their own (they must be decided before sh is computed).  The
+// triangular solves write ph, sh and a scratch block only, for every column of the block: a stopped column's x, r, p and history
+// keep their bits, and its ph -- which a half-step exit still owes to x -- is recomputed from its frozen p to the same bits.
 // Form choice (MANY_FORM = auto): the first batched solve of a solver times a few iterations of the batched loop (K columns)
 // against the same number of iterations of the loop a single solve uses (cudamat_solver_solve, which picks the one- or
 // three-launch loops of small systems), and runs batched only when that is faster than kc single solves.  Everything the batched
-// form does not cover (preconditioners, the pipelined loop, sharded solvers, the DEBUG / PROFILE flags) and a failed allocation
-// of its buffers run column by column: cudamat_solver_solve once per column, bit for bit what a caller's loop would do.
+// form does not cover (ILU(0) unless MANY_PRECOND asks for it, and then hybrid factors in level-major spaces; block-Jacobi ILU(0),
+// the pipelined loop, sharded solvers, the DEBUG / PROFILE flags) and a failed allocation of its buffers run column by column: cudamat_solver_solve once per column, bit for bit what a caller's loop would do.
 #include <chrono>
 #include <math.h>
 #include <string.h>
 
 #include "batch.h"
 #include "solver.h"
+#include "trsm.h"
 
 using namespace cm;
 
@@ -32,7 +41,7 @@ namespace cm {
 void many_release(cudamat_solver *s)
 {
     double **vs[] = {&s->m_r, &s->m_rw, &s->m_p, &s->m_v, &s->m_t, &s->m_b, &s->m_x, &s->m_parts_full, &s->m_parts_rv,
-                     &s->m_parts_half, &s->m_parts_tt, &s->m_hist};
+                     &s->m_parts_half, &s->m_parts_tt, &s->m_hist, &s->m_pw, &s->m_s, &s->m_lt};
     for (double **q : vs) {
         if (*q) CM_DROP(hipFree(*q));
         *q = nullptr;
@@ -40,6 +49,7 @@ void many_release(cudamat_solver *s)
     if (s->m_st) CM_DROP(hipFree(s->m_st));
     s->m_st = nullptr;
     s->m_cap = 0;
+    s->m_pcap = 0;
     s->m_hist_bytes = 0;
 }
 
@@ -87,6 +97,37 @@ int ensure_many(cudamat_solver *s, int K)
     return CUDAMAT_OK;
 }
 
+// the three further blocks of the preconditioned loop: ph = M^-1 p, sh = M^-1 r and the scratch of L^-1.  Allocated only when a
+// preconditioned batch runs; CUDAMAT_ERR_NOMEM leaves none of the three allocated (the seven of ensure_many stay).
+int ensure_many_precond(cudamat_solver *s, int K)
+{
+    if (s->m_pcap >= K) return CUDAMAT_OK;
+    hipStream_t st = s->ctx->stream;
+    CM_HIP(hipStreamSynchronize(st));
+    double **vs[] = {&s->m_pw, &s->m_s, &s->m_lt};
+    for (double **q : vs) {
+        if (*q) CM_DROP(hipFree(*q));
+        *q = nullptr;
+    }
+    s->m_pcap = 0;
+    const size_t nb = sizeof(double) * (size_t)K * (size_t)many_rows(s);
+    int rc = CUDAMAT_OK;
+    for (double **q : vs) {
+        if ((rc = dev_alloc((void **)q, nb))) break;
+        if ((rc = CM_RC(hipMemsetAsync(*q, 0, nb, st)))) break;
+    }
+    if (rc) {
+        CM_DROP(hipStreamSynchronize(st));
+        for (double **q : vs) {
+            if (*q) CM_DROP(hipFree(*q));
+            *q = nullptr;
+        }
+        return rc;
+    }
+    s->m_pcap = K;
+    return CUDAMAT_OK;
+}
+
 SpmmArgs spmm_args(const cudamat_solver *s, const double *x, double *y)
 {
     SpmmArgs a{};
@@ -101,9 +142,12 @@ SpmmArgs spmm_args(const cudamat_solver *s, const double *x, double *y)
 // One batch of kc <= K columns (K a power of two, the rest padding that starts stopped).  B / X column-major with leading
 // dimensions ldb / ldx; B == NULL: m_b and m_x are already filled (the timing of the form choice), X == NULL: the iterate stays
 // in m_x.  fin receives the K final states; hist_out (kc vectors, or NULL) the columns' residual histories.
-int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, double *X, int64_t ldx, int loop, int maxit,
-              double tol, int flags, LoopState *fin, std::vector<double> *hist_out, double *t_loop)
+// precond: CUDAMAT_PRECOND_NONE, or CUDAMAT_PRECOND_ILU0 with covered factors (trsm_covered), the reference loop and
+// ensure_many_precond done.
+int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, double *X, int64_t ldx, int precond, int loop,
+              int maxit, double tol, int flags, LoopState *fin, std::vector<double> *hist_out, double *t_loop)
 {
+    const bool pc = precond != CUDAMAT_PRECOND_NONE;
     hipStream_t st = s->ctx->stream;
     const int n = s->n;
     const int L = s->plan.lanes;
@@ -157,24 +201,35 @@ int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, do
         la.k = k;
         // rho, beta, full-step tests, p = r + beta (p - omega v)                            :80-89
         CM_TRY(launch_update_p_b(st, K, la, s->m_parts_full, np_full, n, s->m_r, s->m_p, s->m_v));
-        // v = A p, rw.v                                                                       :104-106
-        SpmmArgs a1 = spmm_args(s, s->m_p, s->m_v);
+        const double *pw = s->m_p;
+        if (pc) {                                                                           // :92-98
+            CM_TRY(precond_apply_b(s, K, s->m_p, s->m_lt, s->m_pw));
+            pw = s->m_pw;
+        }
+        // v = A pw, rw.v                                                                      :104-106
+        SpmmArgs a1 = spmm_args(s, pw, s->m_v);
         a1.dot = 1; a1.w = s->m_rw; a1.parts = s->m_parts_rv; a1.loop = la;
         CM_TRY(launch_spmm(st, L, K, a1));
         // alpha, r -= alpha v, ||r||                                                          :107-111
         CM_TRY(launch_half_b(st, K, la, s->m_parts_rv, np_spmm, n, s->m_r, s->m_v, s->m_parts_half, &np_half));
-        // half-step tests; t = A s (s = r), (t.r, t.t)                                        :116, :132-136
-        SpmmArgs a2 = spmm_args(s, s->m_r, s->m_t);
+        // half-step tests; t = A sv (sv = r, or M^-1 r), (t.r, t.t)                           :116, :121-127, :132-136
+        const double *sv = s->m_r;
+        if (pc) {              // the tests are decided before M^-1 r is computed, as in Solve::iterate_reference
+            CM_TRY(launch_check_half_b(st, K, la, s->m_parts_half, np_half));
+            CM_TRY(precond_apply_b(s, K, s->m_r, s->m_lt, s->m_s));
+            sv = s->m_s;
+        }
+        SpmmArgs a2 = spmm_args(s, sv, s->m_t);
         a2.dot = 2; a2.w = s->m_r; a2.parts = s->m_parts_tt; a2.loop = la;
-        a2.check = CHECK_HALF; a2.half = s->m_parts_half; a2.half_count = np_half;
+        if (!pc) { a2.check = CHECK_HALF; a2.half = s->m_parts_half; a2.half_count = np_half; }
         CM_TRY(launch_spmm(st, L, K, a2));
-        // omega, x += alpha p, x += omega s, r -= omega t, (rw.r, ||r||), i++                :110, :137-151
-        CM_TRY(launch_full_b(st, K, la, s->m_parts_tt, np_spmm, n, s->m_x, s->m_r, s->m_r, s->m_t, s->m_rw, s->m_p,
+        // omega, x += alpha pw, x += omega sv, r -= omega t, (rw.r, ||r||), i++              :110, :137-151
+        CM_TRY(launch_full_b(st, K, la, s->m_parts_tt, np_spmm, n, s->m_x, sv, s->m_r, s->m_t, s->m_rw, pw,
                              s->m_parts_full, &np_full));
     }
-    // the last full-step tests; columns that left through the half step still owe x += alpha p (:110)
+    // the last full-step tests; columns that left through the half step still owe x += alpha pw (:110)
     CM_TRY(launch_check_full_b(st, K, la, s->m_parts_full, np_full));
-    CM_TRY(launch_half_exit_b(st, K, s->m_st, n, s->m_p, s->m_x));
+    CM_TRY(launch_half_exit_b(st, K, s->m_st, n, pc ? s->m_pw : s->m_p, s->m_x));
     CM_HIP(hipMemcpyAsync(fin, s->m_st, sizeof(LoopState) * (size_t)K, hipMemcpyDeviceToHost, st));
     if (X) CM_TRY(launch_batch_out(st, K, kc, n, s->m_x, X, ldx));
     CM_HIP(hipStreamSynchronize(st));
@@ -192,15 +247,17 @@ int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, do
     return CUDAMAT_OK;
 }
 
-// MANY_FORM = auto: is the batched loop with K columns faster than kc single solves?  Timed once per solver, loop and K
-// (FLAG_NO_EXIT iterations on scratch right-hand sides: b = 1, x0 = 0); what the timing takes is added to *t_tune.
-int prefer_batched(cudamat_solver *s, int K, int kc, int loop, bool *batched, double *t_tune)
+// MANY_FORM / MANY_PRECOND = auto: is the batched loop with K columns faster than kc single solves?  Timed once per solver,
+// loop, preconditioner and K (FLAG_NO_EXIT iterations on scratch right-hand sides: b = 1, x0 = 0); what the timing takes is
+// added to *t_tune.
+int prefer_batched(cudamat_solver *s, int K, int kc, int precond, int loop, bool *batched, double *t_tune)
 {
     const double t0 = now_s();
     hipStream_t st = s->ctx->stream;
     const int n = s->n;
-    if (s->m_tune_loop != loop) {
+    if (s->m_tune_loop != loop || s->m_tune_precond != precond) {
         s->m_tune_loop = loop;
+        s->m_tune_precond = precond;
         s->m_t_single = -1.0;
         for (double &t : s->m_t_batch) t = -1.0;
         // a few iterations: enough that launch and set-up overheads do not decide (small systems run ~10 us per iteration)
@@ -217,8 +274,7 @@ int prefer_batched(cudamat_solver *s, int K, int kc, int loop, bool *batched, do
             CM_HIP(hipStreamSynchronize(st));
             const double t = now_s();
             cudamat_stats dummy;
-            CM_TRY(cudamat_solver_solve(s, s->m_b, s->m_x, CUDAMAT_PRECOND_NONE, loop, rep ? N : 2, 1e-8, CUDAMAT_FLAG_NO_EXIT,
-                                        &dummy));
+            CM_TRY(cudamat_solver_solve(s, s->m_b, s->m_x, precond, loop, rep ? N : 2, 1e-8, CUDAMAT_FLAG_NO_EXIT, &dummy));
             CM_HIP(hipStreamSynchronize(st));
             s->m_t_single = now_s() - t;
         }
@@ -231,21 +287,22 @@ int prefer_batched(cudamat_solver *s, int K, int kc, int loop, bool *batched, do
             CM_TRY(launch_fill(st, (int64_t)K * n, 0.0, s->m_x));
             CM_HIP(hipStreamSynchronize(st));
             const double t = now_s();
-            CM_TRY(run_group(s, K, K, nullptr, 0, nullptr, 0, loop, rep ? N : 2, 1e-8, CUDAMAT_FLAG_NO_EXIT, fin, nullptr,
-                             nullptr));
+            CM_TRY(run_group(s, K, K, nullptr, 0, nullptr, 0, precond, loop, rep ? N : 2, 1e-8, CUDAMAT_FLAG_NO_EXIT, fin,
+                             nullptr, nullptr));
             tb = now_s() - t;
         }
     }
     // batched only when clearly faster (3 %: below that the two are within the noise of one timing)
     *batched = tb < 0.97 * (double)kc * s->m_t_single;
     if (s->ctx->cfg.verbose)
-        fprintf(stderr, "[cudamat] several right-hand sides: %d iterations, single loop %.3f ms x %d columns, batched (K = %d) "
-                        "%.3f ms -> %s\n", N, 1e3 * s->m_t_single, kc, K, 1e3 * tb, *batched ? "batched" : "columns");
+        fprintf(stderr, "[cudamat] several right-hand sides%s: %d iterations, single loop %.3f ms x %d columns, batched (K = %d) "
+                        "%.3f ms -> %s\n", precond ? " with ILU(0)" : "", N, 1e3 * s->m_t_single, kc, K, 1e3 * tb,
+                *batched ? "batched" : "columns");
     *t_tune += now_s() - t0;
     return CUDAMAT_OK;
 }
 
-void fill_stats(const cudamat_solver *s, const LoopState &f, cudamat_stats *o)
+void fill_stats(cudamat_solver *s, const LoopState &f, int precond, cudamat_stats *o)
 {
     memset(o, 0, sizeof(*o));
     o->iters = f.it;
@@ -257,6 +314,14 @@ void fill_stats(const cudamat_solver *s, const LoopState &f, cudamat_stats *o)
     o->loop_form = 0;
     o->spmv_mode = 0;                    // the SpMM runs on the CSR arrays
     o->t_setup = s->t_create + s->t_spmv_setup;
+    if (precond) {                       // as Solve::finish reports them; the level-scheduled kernels have no fall-back
+        o->t_analysis = s->t_analysis;
+        o->t_factor = s->t_factor;
+        o->n_levels_l = s->L.nlevels;
+        o->n_levels_u = s->U.nlevels;
+        o->trsv_form = trsv_form_code(s);
+        o->trsv_fallbacks = 0;
+    }
 }
 
 }  // namespace
@@ -286,6 +351,33 @@ extern "C" int cudamat_solver_spmm(cudamat_solver *s, int nrhs, const double *X,
     return CUDAMAT_OK;
 }
 
+extern "C" int cudamat_solver_precond_apply_many(cudamat_solver *s, int nrhs, const double *In, int ldin, double *Out, int ldout)
+{
+    CM_ARG(s, "solver is NULL");
+    CM_ARG(nrhs >= 0, "nrhs < 0");
+    if (nrhs == 0) return CUDAMAT_OK;
+    CM_ARG(In && Out, "null pointer");
+    CM_ARG(ldin >= s->n && ldout >= s->n, "leading dimension below the rows");
+    CM_ARG(s->has_ilu, "call cudamat_solver_ilu0 / cudamat_solver_block_ilu0 first");
+    CM_HIP(hipSetDevice(s->ctx->device));
+    int rc = trsm_covered(s) ? ensure_many(s, pow2_cols(nrhs < kBatchMax ? nrhs : kBatchMax)) : CUDAMAT_ERR_NOMEM;
+    if (rc == CUDAMAT_ERR_NOMEM) {       // factors the multi-column kernels do not cover, or no room: one application per column
+        CM_TRY(ensure_work(s));
+        for (int j = 0; j < nrhs; j++) CM_TRY(precond_apply(s, In + (size_t)j * ldin, s->t, Out + (size_t)j * ldout));
+        return CUDAMAT_OK;
+    }
+    CM_TRY(rc);
+    hipStream_t st = s->ctx->stream;
+    for (int c0 = 0; c0 < nrhs; c0 += kBatchMax) {
+        const int kc = nrhs - c0 < kBatchMax ? nrhs - c0 : kBatchMax;
+        const int K = pow2_cols(kc);
+        CM_TRY(launch_batch_in(st, K, kc, s->n, s->n, In + (size_t)c0 * ldin, ldin, 0.0, s->m_b));
+        CM_TRY(precond_apply_b(s, K, s->m_b, s->m_t, s->m_x));
+        CM_TRY(launch_batch_out(st, K, kc, s->n, s->m_x, Out + (size_t)c0 * ldout, ldout));
+    }
+    return CUDAMAT_OK;
+}
+
 extern "C" int cudamat_solver_solve_many(cudamat_solver *s, int nrhs, const double *B, int ldb, double *X, int ldx, int precond,
                                          int loop, int maxit, double tol, int flags, cudamat_stats *st, int *form)
 {
@@ -304,27 +396,43 @@ extern "C" int cudamat_solver_solve_many(cudamat_solver *s, int nrhs, const doub
     std::vector<std::vector<double>> hists((size_t)nrhs);
     double t_solve = 0.0, t_tune = 0.0;
     bool any_batched = false;
-    const bool batchable = precond == CUDAMAT_PRECOND_NONE && (loop == CUDAMAT_LOOP_PBICGSTAB || loop == CUDAMAT_LOOP_PBICGSTAB2) &&
-                           !s->sharded && s->n_cols == s->n && s->n > 0 && !(flags & (CUDAMAT_FLAG_DEBUG | CUDAMAT_FLAG_PROFILE));
+    const bool one_gpu = !s->sharded && s->n_cols == s->n && s->n > 0 && !(flags & (CUDAMAT_FLAG_DEBUG | CUDAMAT_FLAG_PROFILE));
+    const bool plain = precond == CUDAMAT_PRECOND_NONE && (loop == CUDAMAT_LOOP_PBICGSTAB || loop == CUDAMAT_LOOP_PBICGSTAB2) && one_gpu;
+    // ILU(0): only when MANY_PRECOND asks for it (0 = columns, the default: today's behaviour bit for bit), the reference loop,
+    // and factors the multi-column triangular solves cover (trsm.h); set up on first use as Solve::setup does it
+    bool pc = precond == CUDAMAT_PRECOND_ILU0 && loop == CUDAMAT_LOOP_PBICGSTAB && one_gpu && cfg.many_precond != 0 &&
+              cfg.many_form != 2;
+    if (pc) {
+        CM_ARG(!s->d, "the (A0 + I d) variant has no preconditioner (pbicgstab.h:110)");
+        if (!s->has_ilu) CM_TRY(ilu0_setup(s, false));
+        pc = trsm_covered(s);
+        if (!pc && cfg.verbose) fprintf(stderr, "[cudamat] ILU(0) factors not covered by the multi-column solves: column by column\n");
+    }
+    const bool batchable = plain || pc;
     bool room = false;
     if (batchable && cfg.many_form != 2) {
-        const int rc = ensure_many(s, pow2_cols(nrhs < kBatchMax ? nrhs : kBatchMax));
+        const int Kmax = pow2_cols(nrhs < kBatchMax ? nrhs : kBatchMax);
+        int rc = ensure_many(s, Kmax);
+        if (rc == CUDAMAT_OK && pc) rc = ensure_many_precond(s, Kmax);
         if (rc != CUDAMAT_OK && rc != CUDAMAT_ERR_NOMEM) return rc;
         room = rc == CUDAMAT_OK;
         if (!room && cfg.verbose) fprintf(stderr, "[cudamat] no room for the batched loop's buffers: column by column\n");
     }
+    const int pc_precond = pc ? CUDAMAT_PRECOND_ILU0 : CUDAMAT_PRECOND_NONE;
+    const bool force_batched = pc ? cfg.many_precond == 2 : cfg.many_form == 1;
+    const bool by_timing = pc ? cfg.many_precond == 1 : cfg.many_form == 0;
     for (int c0 = 0; c0 < nrhs; c0 += kBatchMax) {
         const int kc = nrhs - c0 < kBatchMax ? nrhs - c0 : kBatchMax;
         const int K = pow2_cols(kc);
-        bool batched = room && cfg.many_form == 1;
-        if (room && cfg.many_form == 0) CM_TRY(prefer_batched(s, K, kc, loop, &batched, &t_tune));
+        bool batched = room && force_batched;
+        if (room && by_timing) CM_TRY(prefer_batched(s, K, kc, pc_precond, loop, &batched, &t_tune));
         if (batched) {
             LoopState fin[kBatchMax];
             double tl = 0.0;
-            CM_TRY(run_group(s, K, kc, B + (size_t)c0 * ldb, ldb, X + (size_t)c0 * ldx, ldx, loop, maxit, tol, flags, fin,
-                             hists.data() + c0, &tl));
+            CM_TRY(run_group(s, K, kc, B + (size_t)c0 * ldb, ldb, X + (size_t)c0 * ldx, ldx, pc_precond, loop, maxit, tol, flags,
+                             fin, hists.data() + c0, &tl));
             t_solve += tl;
-            for (int j = 0; j < kc; j++) fill_stats(s, fin[j], &out[(size_t)(c0 + j)]);
+            for (int j = 0; j < kc; j++) fill_stats(s, fin[j], pc_precond, &out[(size_t)(c0 + j)]);
             any_batched = true;
             continue;
         }

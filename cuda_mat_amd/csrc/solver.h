@@ -150,14 +150,17 @@ struct cudamat_solver {
     int m_cap = 0;              // columns the buffers below hold (0: not allocated)
     double *m_r = nullptr, *m_rw = nullptr, *m_p = nullptr, *m_v = nullptr, *m_t = nullptr, *m_b = nullptr, *m_x = nullptr;
     double *m_parts_full = nullptr, *m_parts_rv = nullptr, *m_parts_half = nullptr, *m_parts_tt = nullptr;
+    // the preconditioned batched loop: M^-1 p, M^-1 r and the scratch of L^-1 (m_pcap columns; allocated at its first use)
+    int m_pcap = 0;
+    double *m_pw = nullptr, *m_s = nullptr, *m_lt = nullptr;
     cm::LoopState *m_st = nullptr;     // device, m_cap states
     double *m_hist = nullptr;          // device: per column a history of the batch's length (m_hist_bytes in all)
     size_t m_hist_bytes = 0;
     bool m_failed = false;             // the buffers did not fit: solves with several right-hand sides run column by column
     std::vector<std::vector<double>> m_hist_host;   // per column: the residual history of the last cudamat_solver_solve_many
-    // form choice (MANY_FORM = auto): seconds of m_tune_iters iterations, single loop (< 0: not timed) and batched by log2 K
+    // form choice (MANY_FORM / MANY_PRECOND = auto): seconds of m_tune_iters iterations, single loop (< 0: not timed) and batched by log2 K
     double m_t_single = -1.0, m_t_batch[4] = {-1.0, -1.0, -1.0, -1.0};
-    int m_tune_loop = -1, m_tune_iters = 0;
+    int m_tune_loop = -1, m_tune_precond = -1, m_tune_iters = 0;
 };
 
 namespace cm {

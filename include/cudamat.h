@@ -334,13 +334,24 @@ int cudamat_solver_spmm(cudamat_solver *s, int nrhs, const double *X, int ldx, d
 /* Solve for nrhs right-hand sides B (column-major, ldb >= n) into X (column-major, ldx >= n; the initial guesses on entry
  * unless CUDAMAT_FLAG_X0_ONES).  Every column is an independent run of cudamat_solver_solve's loop with its own scalars,
  * stopping tests and history.  PRECOND_NONE with LOOP_PBICGSTAB / LOOP_PBICGSTAB2 on one GPU may run batched (up to 8
- * columns per launch; a column's result then depends on its own data only, not on the batch); everything else, and the
- * switch MANY_FORM = columns, runs cudamat_solver_solve once per column.  MANY_FORM = auto (default) times both forms at the
+ * columns per launch; a column's result then depends on its own data only, not on the batch); so may PRECOND_ILU0 with
+ * LOOP_PBICGSTAB when the switch MANY_PRECOND = batched | auto asks for it (default: columns) and the factors are covered
+ * (see cudamat_solver_precond_apply_many); everything else, and the switch MANY_FORM = columns, runs cudamat_solver_solve
+ * once per column.  MANY_FORM = auto (default) times both forms at the
  * first such call of the solver (per loop and batch width) and takes the faster.  st: nrhs entries or NULL -- per column
  * iters, half_exit, converged, breakdown, nrm0, nrm, spmv_mode; t_solve / t_total are those of the whole call, t_tune
  * includes the timing of the form choice.  *form (may be NULL): 1 when columns ran batched, 0 column by column.        */
 int cudamat_solver_solve_many(cudamat_solver *s, int nrhs, const double *B, int ldb, double *X, int ldx, int precond,
                               int loop, int maxit, double tol, int flags, cudamat_stats *st, int *form);
+/* Out_j = U^-1 L^-1 In_j for nrhs columns, column-major device blocks (ldin, ldout >= n_local): what cudamat_solver_precond_apply
+ * does, for up to 8 columns per pass over the factors (multi-column level-scheduled triangular solves: one gathered index
+ * yields 8 contiguous values, one level serves all columns).  Column j is bit-identical to cudamat_solver_precond_apply of
+ * column j, whatever nrhs is.  Factors the multi-column kernels do not cover (hybrid factors in level-major spaces, block-Jacobi
+ * ILU(0), sharded solvers) are applied column by column.  Needs cudamat_solver_ilu0 first; nrhs == 0 is a no-op.        */
+int cudamat_solver_precond_apply_many(cudamat_solver *s, int nrhs, const double *In, int ldin, double *Out, int ldout);
+/* name(s) of the HIP kernel(s) that call launches per factor for a batch of nrhs (<= 8) columns, e.g.
+ * "L: k_trsm_lds<8, 8>; U: k_trsm_level<16, 8> + k_trsm_small_levels<16, 8>"; "" when the factors run column by column   */
+int cudamat_solver_trsm_kernel(cudamat_solver *s, int nrhs, char *name, int cap);
 /* residual history of column `col` of the last cudamat_solver_solve_many, laid out as cudamat_solver_history's       */
 int cudamat_solver_history_col(cudamat_solver *s, int col, double *hist_host, int cap, int *count);
 

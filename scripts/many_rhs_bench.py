@@ -4,6 +4,12 @@ One JSON line per (config, K): per-column iterations per second of the batched l
 sequential Solver.solve calls (both FLAG_NO_EXIT, the same iteration count), the SpMM's time and its fraction of the HBM
 roofline (bytes = 12 nnz + 4 (n + 1) + 8 K (n_cols + n)), and the form MANY_FORM = auto chose.
     python scripts/many_rhs_bench.py [--c4]        (--c4 adds the 1e7 x 50 random system, ~35 GB of device memory)
+
+--precond ilu0: the same comparison for the preconditioned loop -- MANY_PRECOND = batched (multi-column triangular solves,
+csrc/trsm.hip) against K sequential Solver.solve calls with ILU(0), on mat10000, the 4000 x 2500 stencil and a random
+2e5 x 50 system (TRSV_HYBRID = 0 throughout: hybrid factors are not covered by the batched form), and what MANY_PRECOND = auto
+picks.  --sequential-only measures just the K sequential solves and uses nothing newer than Solver.solve, so the same file
+can be run against an older build of the library to take the sequential figure there.
 """
 import argparse
 import json
@@ -32,7 +38,7 @@ def make(ctx, name):
         rp, ci, v = ctx.empty(n + 1, np.int32), ctx.empty(nnz, np.int32), ctx.empty(nnz)
         ctx.gen_poisson5(nx, ny, 0, n, 0, rp, ci, v)
     else:
-        n = 2_000_000 if name.startswith("rand2e6") else 10_000_000
+        n = 200_000 if name.startswith("rand2e5") else 2_000_000 if name.startswith("rand2e6") else 10_000_000
         nnz = n * int(cm.lib().cudamat_rand_row_nnz(n, 50))
         rp, ci, v = ctx.empty(n + 1, np.int32), ctx.empty(nnz, np.int32), ctx.empty(nnz)
         ctx.gen_rand_rows(n, 50, 0x5EED, 0, n, 0, rp, ci, v)
@@ -92,10 +98,65 @@ def run(name, iters):
     return out
 
 
+def run_precond(name, iters, sequential_only, build):
+    ctx = cm.Context(0)
+    ctx.set_option("TRSV_HYBRID", "0")
+    s, n, nnz, keep = make(ctx, name)
+    s.ilu0()
+    B, X = ctx.empty(8 * n), ctx.empty(8 * n)
+    for j in range(8):
+        ctx.gen_xstar(0, n, 100 + j, X.ptr + 8 * j * n)
+    for j in range(8):                       # (one SpMV per column: nothing newer than the single-vector interface)
+        s.spmv(X.ptr + 8 * j * n, B.ptr + 8 * j * n)
+    kw = dict(precond=cm.PRECOND_ILU0, loop=cm.LOOP_PBICGSTAB, tol=1e-8, flags=cm.FLAG_NO_EXIT)
+    x = ctx.empty(8 * n)
+    x.zero()
+    st = s.solve(B, x, maxit=2, **kw)                                                            # warm-up
+    for K in (1, 2, 4, 8):
+        t_s = 0.0
+        for j in range(K):
+            x.zero()
+            ctx.sync()
+            st = s.solve(B.ptr + 8 * j * n, x.ptr + 8 * j * n, maxit=iters, **kw)
+            t_s += st.t_solve
+        line = {"config": name, "precond": "ilu0", "build": build, "n": n, "nnz": nnz, "K": K, "iters": iters,
+                "levels": [st.n_levels_l, st.n_levels_u], "trsv_form_single": st.trsv_form,
+                "sequential_col_it_s": K * iters / t_s, "sequential_s": t_s}
+        if not sequential_only:
+            ctx.set_option("MANY_PRECOND", "batched")
+            x.zero()
+            s.solve_many(K, B, n, x, n, maxit=2, **kw)                                           # warm-up
+            x.zero()
+            sts, form_b = s.solve_many(K, B, n, x, n, maxit=iters, **kw)
+            t_b = sts[0].t_solve
+            ctx.set_option("MANY_PRECOND", "auto")        # (the first auto call per K times both forms: t_tune)
+            x.zero()
+            sts_a, form_a = s.solve_many(K, B, n, x, n, maxit=iters, **kw)
+            ctx.set_option("MANY_PRECOND", "columns")
+            line.update({"batched_form": form_b, "batched_col_it_s": K * iters / t_b, "batched_s": t_b,
+                         "gain_per_column_same_build": t_s / t_b, "trsm_kernel": s.trsm_kernel(K),
+                         "auto_form": "batched" if form_a else "columns", "auto_t_tune_s": sts_a[0].t_tune,
+                         "auto_col_it_s": K * iters / sts_a[0].t_solve})
+        print(json.dumps(line), flush=True)
+    for a in (B, X, x):
+        a.free()
+    s.close()
+    ctx.close()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--c4", action="store_true")
+    ap.add_argument("--precond", choices=["none", "ilu0"], default="none")
+    ap.add_argument("--sequential-only", action="store_true")
+    ap.add_argument("--build", default="this", help="label of the library build in the output lines")
+    ap.add_argument("--only", default="", help="run the configs whose name contains this")
     a = ap.parse_args()
+    if a.precond == "ilu0":
+        for name, it in [("C2_mat10000", 100), ("C3_poisson4000x2500", 3), ("rand2e5x50", 30)]:
+            if a.only in name:
+                run_precond(name, it, a.sequential_only, a.build)
+        sys.exit(0)
     configs = [("C2_mat10000", 500), ("C3_poisson4000x2500", 30), ("rand2e6x50", 30)]
     if a.c4:
         configs.append(("C4_rand1e7x50", 10))
