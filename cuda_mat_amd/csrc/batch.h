@@ -11,6 +11,8 @@
 namespace cm {
 
 constexpr int kBatchMax = 8;       // columns of one batch
+// the width K of the batch that holds kc columns: the next power of two, the rest is padding
+inline int pow2_cols(int kc) { return kc <= 1 ? 1 : kc <= 2 ? 2 : kc <= 4 ? 4 : kBatchMax; }
 
 // the loop arguments of a batch: column j uses st[j] and hist + j * hist_cap
 struct BatchArgs {

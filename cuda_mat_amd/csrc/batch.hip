@@ -65,14 +65,6 @@ __device__ __forceinline__ void publish_b(const BatchArgs &la, int all_stopped)
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-int vec_grid_rows(int64_t rows)
-{
-    int64_t g = (rows + kBlock - 1) / kBlock;
-    if (g < 1) g = 1;
-    if (g > 4096) g = 4096;
-    return (int)g;
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------- SpMM
@@ -293,13 +285,13 @@ __global__ __launch_bounds__(kBlock) void k_batch_out(int kc, int64_t rows, cons
 int launch_batch_in(hipStream_t s, int K, int kc, int64_t rows, int64_t rows_out, const double *src, int64_t ld, double fill,
                     double *dst)
 {
-    const int g = vec_grid_rows(rows_out);
+    const int g = row_grid(rows_out);
     CM_BATCH_DISPATCH(k_batch_in, g, kc, rows, rows_out, src, ld, fill, dst)
 }
 
 int launch_batch_out(hipStream_t s, int K, int kc, int64_t rows, const double *src, double *dst, int64_t ld)
 {
-    const int g = vec_grid_rows(rows);
+    const int g = row_grid(rows);
     CM_BATCH_DISPATCH(k_batch_out, g, kc, rows, src, dst, ld)
 }
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <chrono>
 #include <string>
 
 #include "cudamat.h"
@@ -28,6 +29,12 @@ size_t pool_free_bytes();         // what the current device's pool could hand o
 #define hipFree(p) cm::pool_free((void *)(p))
 
 namespace cm {
+
+// seconds on the steady clock (host-side timings and the bounds of host-side waits)
+inline double now_s()
+{
+    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
 
 void set_error(const char *fmt, ...);
 int fail_hip(hipError_t e, const char *what, const char *file, int line);

@@ -29,11 +29,6 @@
 
 using namespace cm;
 
-static double now_s()
-{
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 namespace {
 
 // A two-socket host reaches a GPU through ONE socket's PCIe root: a thread that feeds the runtime's pageable copies from the
@@ -214,9 +209,7 @@ static int device_equal(hipStream_t st, const void *a, const void *b, size_t byt
 {
     const long long words = (long long)(bytes / 4);
     if (words == 0) return CUDAMAT_OK;
-    long long g = (words + kBlock * 8LL - 1) / (kBlock * 8LL);
-    if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(k_differs, dim3((unsigned)g), dim3(kBlock), 0, st, words, (const unsigned *)a, (const unsigned *)b, flag_dev);
+    hipLaunchKernelGGL(k_differs, dim3(row_grid(words, kBlock * 8LL)), dim3(kBlock), 0, st, words, (const unsigned *)a, (const unsigned *)b, flag_dev);
     CM_HIP(hipGetLastError());
     return CUDAMAT_OK;
 }

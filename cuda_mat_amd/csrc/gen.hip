@@ -159,10 +159,7 @@ extern "C" int cudamat_gen_poisson5(cudamat_ctx *ctx, int nx, int ny, int64_t ro
 extern "C" int cudamat_gen_xstar(cudamat_ctx *ctx, int64_t i0, int64_t i1, uint64_t seed, double *x)
 {
     CM_ARG(ctx && x && i0 <= i1, "bad range");
-    int64_t g = (i1 - i0 + kBlock - 1) / kBlock;
-    if (g < 1) g = 1;
-    if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(k_gen_xstar, dim3((int)g), dim3(kBlock), 0, ctx->stream, i0, i1, seed, x);
+    hipLaunchKernelGGL(k_gen_xstar, dim3(row_grid(i1 - i0)), dim3(kBlock), 0, ctx->stream, i0, i1, seed, x);
     CM_HIP(hipGetLastError());
     return CUDAMAT_OK;
 }

@@ -46,6 +46,14 @@ struct TriHost {   // host-side launch plan kept next to the TriFactor
     int pb_strict = 0;                     // Config::pb_strict at set-up: passed to the far parts' phase 2
 };
 
+// Which launch segment g of the level-by-level plan takes: a single level wider than kSmallLevel is a launch of its own
+// (true), everything else -- a run of narrow levels -- one single-workgroup launch.
+inline bool segment_is_wide(const TriFactor &F, const TriHost &H, size_t g)
+{
+    const int l0 = H.seg_begin[g], l1 = H.seg_end[g];
+    return l1 - l0 == 1 && F.level_ptr[(size_t)l1] - F.level_ptr[(size_t)l0] > kSmallLevel;
+}
+
 }  // namespace cm
 
 // the launch plans hang off the solver as an opaque pointer (keeps solver.h light)

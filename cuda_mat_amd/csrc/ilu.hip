@@ -22,7 +22,6 @@
 // Block-Jacobi (row-sharded runs): the same machinery on the rank's diagonal block (select_precond_matrix).
 // Algorithmic bytes per preconditioner application: 12 nnz + 8 (n+1) + 32 n.
 #include <algorithm>
-#include <chrono>
 #include <vector>
 
 #include "ilu.h"
@@ -30,11 +29,6 @@
 using namespace cm;
 
 namespace cm {
-
-static double now_s()
-{
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 #define CM_STAMP(label)                                                                       \
     do {                                                                                      \

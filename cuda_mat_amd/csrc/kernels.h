@@ -118,6 +118,12 @@ int plan_spmv_dict(hipStream_t s, int n_rows, int64_t nnz, const int *rp, const 
                    SpmvPlan *plan);
 
 int vec_grid(int64_t n);
+// workgroups of a grid-stride kernel over `rows` items, `per_block` of them per workgroup and sweep: at least 1, at most 4096
+inline int row_grid(int64_t rows, int64_t per_block = kBlock)
+{
+    const int64_t g = (rows + per_block - 1) / per_block;
+    return (int)(g < 1 ? 1 : g > 4096 ? 4096 : g);
+}
 
 // r = b - r (r holds A x0 on entry), rw = r, p = r; parts[2b] = parts[2b+1] = sum r^2
 int launch_init(hipStream_t s, int64_t n, const double *b, double *r, double *rw, double *p,

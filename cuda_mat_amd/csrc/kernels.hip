@@ -424,10 +424,7 @@ __global__ __launch_bounds__(kBlock) void k_rebase(int64_t n, const int *in, int
 
 int launch_rebase(hipStream_t s, int64_t n, const int *in, int shift, int *out)
 {
-    int64_t g = (n + kBlock - 1) / kBlock;
-    if (g < 1) g = 1;
-    if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(k_rebase, dim3((int)g), dim3(kBlock), 0, s, n, in, shift, out);
+    hipLaunchKernelGGL(k_rebase, dim3(row_grid(n)), dim3(kBlock), 0, s, n, in, shift, out);
     CM_HIP(hipGetLastError());
     return CUDAMAT_OK;
 }

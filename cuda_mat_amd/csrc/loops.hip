@@ -13,10 +13,10 @@
 //   iterate_reference five launches per iteration                       (everything else; + M^-1, + exchanges when sharded)
 //   iterate_pipelined four launches per iteration, reductions beside the SpMVs (sharded runs)
 // The host-side loop (run_host_loop) is shared by the last three: it enqueues iteration k and looks at the progress
-// word iteration k - kLag published through pinned memory, so the stream never drains; once a stopping test fires on
+// word iteration k - kLag published through pinned memory (wait_progress, which the batched loop of loops_batch.hip
+// calls too, as it does the history and statistics rules below), so the stream never drains; once a stopping test fires on
 // the device every later kernel returns immediately ("freeze on exit"), so the lagged look costs no accuracy and the
 // iterate is exactly the one the reference would return.
-#include <chrono>
 #include <utility>
 #include <math.h>
 #include <stdlib.h>
@@ -26,10 +26,64 @@
 
 using namespace cm;
 
-static double now_s()
+namespace cm {
+
+int wait_progress(cudamat_solver *s, hipStream_t st, int j, const char *what, unsigned long long *word)
 {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    volatile unsigned long long *slot = &s->snap_host[j % kRing];
+    unsigned long long w = *slot;
+    if ((unsigned)(w >> 32) != (unsigned)(j + 1)) {
+        const double t_wait = now_s();
+        while ((unsigned)((w = *slot) >> 32) != (unsigned)(j + 1)) {
+            __builtin_ia32_pause();
+            if (now_s() - t_wait > 30.0) {
+                // give queued work a bounded chance to drain (a query, not a wait: the device may be wedged),
+                // then fail the solve; in a sharded run the caller must exit so that its peers are torn down
+                const double t_drain = now_s();
+                while (hipStreamQuery(st) == hipErrorNotReady && now_s() - t_drain < 5.0) __builtin_ia32_pause();
+                set_error("%siteration %d did not report progress within 30 s%s", what, j,
+                          s->sharded ? " (sharded run: this rank must exit, its peers are waiting in a collective)" : "");
+                return CUDAMAT_ERR_HIP;
+            }
+        }
+    }
+    *word = w;
+    return CUDAMAT_OK;
 }
+
+int history_need(int loop, int maxit)
+{
+    const long long want = (long long)(loop != CUDAMAT_LOOP_PBICGSTAB2 ? 2 : 1) * (maxit > 0 ? maxit : 1);
+    return (int)(want < (1LL << 20) ? want : (1LL << 20));
+}
+
+int history_count(int loop, const LoopState &f, int cap)
+{
+    const int c = loop != CUDAMAT_LOOP_PBICGSTAB2 ? 2 * f.it + (f.state == 1 ? 1 : 0) : f.it;
+    return c < cap ? c : cap;
+}
+
+void stats_from_state(const LoopState &f, cudamat_stats *o)
+{
+    memset(o, 0, sizeof(*o));
+    o->iters = f.it;
+    o->half_exit = f.state == 1;
+    o->converged = f.state == 1 || f.state == 2;
+    o->breakdown = f.state == 3;
+    o->nrm0 = f.nrm0;
+    o->nrm = f.nrm;
+}
+
+void stats_ilu0(cudamat_solver *s, bool applied, cudamat_stats *o)
+{
+    o->t_analysis = s->t_analysis;
+    o->t_factor = s->t_factor;
+    o->n_levels_l = s->L.nlevels;
+    o->n_levels_u = s->U.nlevels;
+    o->trsv_form = applied ? trsv_form_code(s) : 0;
+}
+
+}  // namespace cm
 
 namespace {
 
@@ -134,8 +188,7 @@ int Solve::setup()
 
     // residual history: two entries per iteration (half / full step) or one; capped at 2^20 entries (8 MB) -- a solve
     // with a larger maxit keeps the first 2^20 (the kernels check the capacity)
-    const long long want_hist = (long long)(loop != CUDAMAT_LOOP_PBICGSTAB2 ? 2 : 1) * (maxit > 0 ? maxit : 1);
-    const int need_hist = (int)(want_hist < (1LL << 20) ? want_hist : (1LL << 20));
+    const int need_hist = history_need(loop, maxit);
     // a restart segment (abs_tol > 0) appends to the history of the segments before it (the kernels check the capacity)
     hist_base = abs_tol > 0.0 ? (s->hist_count < s->hist_cap ? s->hist_count : s->hist_cap) : 0;
     if (hist_base == 0 && need_hist > s->hist_cap) {
@@ -486,25 +539,9 @@ int Solve::iterate_reference()
 int Solve::run_host_loop()
 {
     for (int k = 0; k < maxit; k++) {
-        if (k >= kLag) {   // lagged, deterministic look at the device state: the progress word of
-            const int j = k - kLag;   // iteration j, published by its k_full through pinned memory
-            volatile unsigned long long *slot = &s->snap_host[j % kRing];
-            unsigned long long w = *slot;
-            if ((unsigned)(w >> 32) != (unsigned)(j + 1)) {
-                const double t_wait = now_s();
-                while ((unsigned)((w = *slot) >> 32) != (unsigned)(j + 1)) {
-                    __builtin_ia32_pause();
-                    if (now_s() - t_wait > 30.0) {
-                        // give queued work a bounded chance to drain (a query, not a wait: the device may be wedged),
-                        // then fail the solve; in a sharded run the caller must exit so that its peers are torn down
-                        const double t_drain = now_s();
-                        while (hipStreamQuery(st) == hipErrorNotReady && now_s() - t_drain < 5.0) __builtin_ia32_pause();
-                        set_error("iteration %d did not report progress within 30 s%s", j,
-                                  sharded ? " (sharded run: this rank must exit, its peers are waiting in a collective)" : "");
-                        return CUDAMAT_ERR_HIP;
-                    }
-                }
-            }
+        if (k >= kLag) {   // lagged, deterministic look at the device state: the progress word of iteration k - kLag,
+            unsigned long long w = 0;          // published by its k_full
+            CM_TRY(wait_progress(s, st, k - kLag, "", &w));
             if ((unsigned)(w & 0xffffffffULL) != 0u) break;
         }
         la.k = k;
@@ -558,23 +595,12 @@ int Solve::finish(bool *precond_gave_up, cudamat_stats *out)
         CM_HIP(hipMemcpyAsync(x, s->pxh, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
         CM_HIP(hipStreamSynchronize(st));
     }
-    s->hist_count = hist_base + ((loop != CUDAMAT_LOOP_PBICGSTAB2) ? 2 * fin.it + (fin.state == 1 ? 1 : 0) : fin.it);
-    if (s->hist_count > s->hist_cap) s->hist_count = s->hist_cap;
+    s->hist_count = hist_base + history_count(loop, fin, s->hist_cap - hist_base);      // (hist_base <= hist_cap: setup)
 
     cudamat_stats stt;
-    memset(&stt, 0, sizeof(stt));
-    stt.iters = fin.it;
-    stt.half_exit = fin.state == 1;
-    stt.converged = fin.state == 1 || fin.state == 2;
-    stt.breakdown = fin.state == 3;
-    stt.nrm0 = fin.nrm0;
-    stt.nrm = fin.nrm;
-    stt.t_analysis = s->t_analysis;
-    stt.t_factor = s->t_factor;
+    stats_from_state(fin, &stt);
+    stats_ilu0(s, precond != CUDAMAT_PRECOND_NONE, &stt);
     stt.t_solve = t_loop1 - t_loop0;
-    stt.n_levels_l = s->L.nlevels;
-    stt.n_levels_u = s->U.nlevels;
-    stt.trsv_form = precond ? trsv_form_code(s) : 0;
     stt.trsv_fallbacks = s->trsv_fallbacks;
     if (precond) trsv_group_counts(s, &stt.trsv_groups_l, &stt.trsv_groups_u);
     stt.loop_form = loop_form;

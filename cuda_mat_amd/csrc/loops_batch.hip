@@ -5,9 +5,10 @@
 // own rho, alpha, omega, stopping tests, breakdown guard and history; nothing of one column enters another (this is not
 // block-BiCGSTAB).  The batched form runs up to 8 columns through the same launches: per iteration
 //   k_update_p_b | SpMM (+ rw.v) | k_half_b | SpMM (+ t.r, t.t; half-step tests in its prologue) | k_full_b
-// with the vectors interleaved (batch.h), so each SpMM streams the matrix once for all of them.  The host loop is run_host_loop's
-// (loops.hip): iteration k is enqueued while the progress word of iteration k - kLag, (k+1) << 32 | every column stopped, is
-// looked at; a stopped column is frozen by the kernels, so the lagged look costs no accuracy.
+// with the vectors interleaved (batch.h), so each SpMM streams the matrix once for all of them.  The host loop has the shape of
+// Solve::run_host_loop and shares its pieces (solver.h: wait_progress, history_need / history_count, stats_from_state / stats_ilu0;
+// defined in loops.hip): iteration k is enqueued while the progress word of iteration k - kLag, (k+1) << 32 | every column
+// stopped, is looked at; a stopped column is frozen by the kernels, so the lagged look costs no accuracy.
 // With CUDAMAT_PRECOND_ILU0 and the switch MANY_PRECOND = batched | auto (default: columns) the reference loop runs batched too
 // (Solve::iterate_reference per column, pbicgstab.cu:92-98, :116, :121-127):
 //   k_update_p_b | ph = U^-1 L^-1 p | SpMM v = A ph (+ rw.v) | k_half_b | half-step tests | sh = U^-1 L^-1 r |
@@ -21,7 +22,6 @@
 // three-launch loops of small systems), and runs batched only when that is faster than kc single solves.  Everything the batched
 // form does not cover (ILU(0) unless MANY_PRECOND asks for it, and then hybrid factors in level-major spaces; block-Jacobi ILU(0),
 // the pipelined loop, sharded solvers, the DEBUG / PROFILE flags) and a failed allocation of its buffers run column by column: cudamat_solver_solve once per column, bit for bit what a caller's loop would do.
-#include <chrono>
 #include <math.h>
 #include <string.h>
 
@@ -31,33 +31,8 @@
 
 using namespace cm;
 
-static double now_s()
-{
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-namespace cm {
-
-void many_release(cudamat_solver *s)
-{
-    double **vs[] = {&s->m_r, &s->m_rw, &s->m_p, &s->m_v, &s->m_t, &s->m_b, &s->m_x, &s->m_parts_full, &s->m_parts_rv,
-                     &s->m_parts_half, &s->m_parts_tt, &s->m_hist, &s->m_pw, &s->m_s, &s->m_lt};
-    for (double **q : vs) {
-        if (*q) CM_DROP(hipFree(*q));
-        *q = nullptr;
-    }
-    if (s->m_st) CM_DROP(hipFree(s->m_st));
-    s->m_st = nullptr;
-    s->m_cap = 0;
-    s->m_pcap = 0;
-    s->m_hist_bytes = 0;
-}
-
-}  // namespace cm
-
 namespace {
 
-int pow2_cols(int kc) { return kc <= 1 ? 1 : kc <= 2 ? 2 : kc <= 4 ? 4 : 8; }
 int log2_cols(int K) { return K == 1 ? 0 : K == 2 ? 1 : K == 4 ? 2 : 3; }
 
 int64_t many_rows(const cudamat_solver *s)
@@ -67,65 +42,103 @@ int64_t many_rows(const cudamat_solver *s)
     return rows > 0 ? rows : 1;
 }
 
-// the interleaved buffers for K columns: seven vectors (r, rw, p, v, t, b, x), the partial sums, the K loop states.
-// CUDAMAT_ERR_NOMEM leaves nothing allocated.
-int ensure_many(cudamat_solver *s, int K)
+// The interleaved buffers come in two groups, each a list of (pointer, bytes for K columns, zeroed at allocation?): the plain
+// loop's -- seven vectors (r, rw, p, v, t, b, x), the partial sums, the K loop states -- and the three further blocks of the
+// preconditioned loop: ph = M^-1 p, sh = M^-1 r and the scratch of L^-1.
+struct Buf {
+    void **p;
+    size_t bytes;
+    bool zero;
+};
+
+std::vector<Buf> many_group(cudamat_solver *s, bool precond, int K)
 {
-    if (s->m_cap >= K) return CUDAMAT_OK;
+    ManyWork &m = s->many;
+    const size_t nb = sizeof(double) * (size_t)K * (size_t)many_rows(s);
+    if (precond) return {{(void **)&m.pw, nb, true}, {(void **)&m.s, nb, true}, {(void **)&m.lt, nb, true}};
+    const size_t pv = sizeof(double) * 2 * (size_t)K * kVecGridMax, ps = sizeof(double) * 2 * (size_t)K * kSpmvGridMax;
+    return {{(void **)&m.r, nb, true}, {(void **)&m.rw, nb, true}, {(void **)&m.p, nb, true}, {(void **)&m.v, nb, true},
+            {(void **)&m.t, nb, true}, {(void **)&m.b, nb, true}, {(void **)&m.x, nb, true},
+            {(void **)&m.parts_full, pv, false}, {(void **)&m.parts_half, pv, false}, {(void **)&m.parts_rv, ps, false},
+            {(void **)&m.parts_tt, ps, false}, {(void **)&m.st, sizeof(LoopState) * (size_t)K, false}};
+}
+
+void free_group(cudamat_solver *s, bool precond)
+{
+    for (const Buf &b : many_group(s, precond, 0)) {
+        if (*b.p) CM_DROP(hipFree(*b.p));
+        *b.p = nullptr;
+    }
+    (precond ? s->many.pcap : s->many.cap) = 0;
+}
+
+}  // namespace
+
+namespace cm {
+
+void many_release(cudamat_solver *s)
+{
+    ManyWork &m = s->many;
+    free_group(s, false);
+    free_group(s, true);
+    if (m.hist) CM_DROP(hipFree(m.hist));
+    m.hist = nullptr;
+    m.hist_bytes = 0;
+}
+
+}  // namespace cm
+
+namespace {
+
+// One group holds K columns: allocated (and zeroed) as a whole, or -- CUDAMAT_ERR_NOMEM -- not at all.  A wider plain group
+// replaces everything (the preconditioned group and the histories go with it); a failed preconditioned group leaves the plain
+// one in place.  The stream is drained before anything is freed.
+int ensure_many(cudamat_solver *s, bool precond, int K)
+{
+    if ((precond ? s->many.pcap : s->many.cap) >= K) return CUDAMAT_OK;
     hipStream_t st = s->ctx->stream;
     CM_HIP(hipStreamSynchronize(st));
-    many_release(s);
-    const size_t nb = sizeof(double) * (size_t)K * (size_t)many_rows(s);
-    double **vs[] = {&s->m_r, &s->m_rw, &s->m_p, &s->m_v, &s->m_t, &s->m_b, &s->m_x};
+    if (precond) free_group(s, true);
+    else many_release(s);
     int rc = CUDAMAT_OK;
-    for (double **q : vs) {
-        if ((rc = dev_alloc((void **)q, nb))) break;
-        if ((rc = CM_RC(hipMemsetAsync(*q, 0, nb, st)))) break;
+    for (const Buf &b : many_group(s, precond, K)) {
+        if ((rc = dev_alloc(b.p, b.bytes))) break;
+        if (b.zero && (rc = CM_RC(hipMemsetAsync(*b.p, 0, b.bytes, st)))) break;
     }
-    const size_t pv = sizeof(double) * 2 * (size_t)K * kVecGridMax, ps = sizeof(double) * 2 * (size_t)K * kSpmvGridMax;
-    if (!rc) rc = dev_alloc((void **)&s->m_parts_full, pv);
-    if (!rc) rc = dev_alloc((void **)&s->m_parts_half, pv);
-    if (!rc) rc = dev_alloc((void **)&s->m_parts_rv, ps);
-    if (!rc) rc = dev_alloc((void **)&s->m_parts_tt, ps);
-    if (!rc) rc = dev_alloc((void **)&s->m_st, sizeof(LoopState) * (size_t)K);
     if (rc) {
         CM_DROP(hipStreamSynchronize(st));
-        many_release(s);
+        free_group(s, precond);
         return rc;
     }
-    s->m_cap = K;
+    (precond ? s->many.pcap : s->many.cap) = K;
     return CUDAMAT_OK;
 }
 
-// the three further blocks of the preconditioned loop: ph = M^-1 p, sh = M^-1 r and the scratch of L^-1.  Allocated only when a
-// preconditioned batch runs; CUDAMAT_ERR_NOMEM leaves none of the three allocated (the seven of ensure_many stay).
-int ensure_many_precond(cudamat_solver *s, int K)
+// Is there room for the batched form of a call with nrhs columns (the plain group, with `precond` the other one too, for its
+// widest block)?  Buffers that do not fit are not an error of the call -- *room = false, it runs column by column --; any other
+// failure is.
+int many_room(cudamat_solver *s, int nrhs, bool precond, bool *room)
 {
-    if (s->m_pcap >= K) return CUDAMAT_OK;
-    hipStream_t st = s->ctx->stream;
-    CM_HIP(hipStreamSynchronize(st));
-    double **vs[] = {&s->m_pw, &s->m_s, &s->m_lt};
-    for (double **q : vs) {
-        if (*q) CM_DROP(hipFree(*q));
-        *q = nullptr;
+    const int K = pow2_cols(nrhs < kBatchMax ? nrhs : kBatchMax);
+    int rc = ensure_many(s, false, K);
+    if (rc == CUDAMAT_OK && precond) rc = ensure_many(s, true, K);
+    *room = rc == CUDAMAT_OK;
+    return rc == CUDAMAT_ERR_NOMEM ? CUDAMAT_OK : rc;
+}
+
+// the columns of a call in blocks of at most kBatchMax: kc columns from c0 on, in a batch of width K (the rest is padding)
+struct ColBlock {
+    int c0, kc, K;
+};
+
+std::vector<ColBlock> col_blocks(int nrhs)
+{
+    std::vector<ColBlock> blocks;
+    for (int c0 = 0; c0 < nrhs; c0 += kBatchMax) {
+        const int kc = nrhs - c0 < kBatchMax ? nrhs - c0 : kBatchMax;
+        blocks.push_back({c0, kc, pow2_cols(kc)});
     }
-    s->m_pcap = 0;
-    const size_t nb = sizeof(double) * (size_t)K * (size_t)many_rows(s);
-    int rc = CUDAMAT_OK;
-    for (double **q : vs) {
-        if ((rc = dev_alloc((void **)q, nb))) break;
-        if ((rc = CM_RC(hipMemsetAsync(*q, 0, nb, st)))) break;
-    }
-    if (rc) {
-        CM_DROP(hipStreamSynchronize(st));
-        for (double **q : vs) {
-            if (*q) CM_DROP(hipFree(*q));
-            *q = nullptr;
-        }
-        return rc;
-    }
-    s->m_pcap = K;
-    return CUDAMAT_OK;
+    return blocks;
 }
 
 SpmmArgs spmm_args(const cudamat_solver *s, const double *x, double *y)
@@ -140,104 +153,89 @@ SpmmArgs spmm_args(const cudamat_solver *s, const double *x, double *y)
 }
 
 // One batch of kc <= K columns (K a power of two, the rest padding that starts stopped).  B / X column-major with leading
-// dimensions ldb / ldx; B == NULL: m_b and m_x are already filled (the timing of the form choice), X == NULL: the iterate stays
-// in m_x.  fin receives the K final states; hist_out (kc vectors, or NULL) the columns' residual histories.
+// dimensions ldb / ldx; B == NULL: many.b and many.x are already filled (the timing of the form choice), X == NULL: the iterate
+// stays in many.x.  fin receives the K final states; hist_out (kc vectors, or NULL) the columns' residual histories.
 // precond: CUDAMAT_PRECOND_NONE, or CUDAMAT_PRECOND_ILU0 with covered factors (trsm_covered), the reference loop and
-// ensure_many_precond done.
+// the preconditioned group allocated (many_room).
 int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, double *X, int64_t ldx, int precond, int loop,
               int maxit, double tol, int flags, LoopState *fin, std::vector<double> *hist_out, double *t_loop)
 {
+    ManyWork &m = s->many;
     const bool pc = precond != CUDAMAT_PRECOND_NONE;
     hipStream_t st = s->ctx->stream;
     const int n = s->n;
     const int L = s->plan.lanes;
-    // residual history: as Solve::setup (loops.hip), per column
-    const long long want = (long long)(loop != CUDAMAT_LOOP_PBICGSTAB2 ? 2 : 1) * (maxit > 0 ? maxit : 1);
-    const int need = (int)(want < (1LL << 20) ? want : (1LL << 20));
+    const int need = history_need(loop, maxit);      // residual history, per column
     double *hist = nullptr;
     if (hist_out) {
         const size_t bytes = sizeof(double) * (size_t)K * (size_t)need;
-        if (bytes > s->m_hist_bytes) {
-            if (s->m_hist) { CM_HIP(hipStreamSynchronize(st)); CM_DROP(hipFree(s->m_hist)); s->m_hist = nullptr; s->m_hist_bytes = 0; }
-            CM_TRY(dev_alloc((void **)&s->m_hist, bytes));
-            s->m_hist_bytes = bytes;
+        if (bytes > m.hist_bytes) {
+            if (m.hist) { CM_HIP(hipStreamSynchronize(st)); CM_DROP(hipFree(m.hist)); m.hist = nullptr; m.hist_bytes = 0; }
+            CM_TRY(dev_alloc((void **)&m.hist, bytes));
+            m.hist_bytes = bytes;
         }
-        hist = s->m_hist;
+        hist = m.hist;
         CM_HIP(hipMemsetAsync(hist, 0xFF, bytes, st));              // NaN fill
     }
-    BatchArgs la{s->m_st, hist, need, loop, (flags & CUDAMAT_FLAG_NO_EXIT) ? 1 : 0, s->snap_dev, kRing, 0};
+    BatchArgs la{m.st, hist, need, loop, (flags & CUDAMAT_FLAG_NO_EXIT) ? 1 : 0, s->snap_dev, kRing, 0};
     for (int i = 0; i < kRing; i++) s->snap_host[i] = 0ULL;
     const double t0 = now_s();
     if (B) {
-        CM_TRY(launch_batch_in(st, K, kc, n, n, B, ldb, 0.0, s->m_b));
-        if (flags & CUDAMAT_FLAG_X0_ONES) CM_TRY(launch_fill(st, (int64_t)K * n, 1.0, s->m_x));
-        else CM_TRY(launch_batch_in(st, K, kc, n, n, X, ldx, 0.0, s->m_x));
+        CM_TRY(launch_batch_in(st, K, kc, n, n, B, ldb, 0.0, m.b));
+        if (flags & CUDAMAT_FLAG_X0_ONES) CM_TRY(launch_fill(st, (int64_t)K * n, 1.0, m.x));
+        else CM_TRY(launch_batch_in(st, K, kc, n, n, X, ldx, 0.0, m.x));
     }
     // r = A x0; r = b - r, rw = r, p = r; the states                                        pbicgstab.cu:67-74 / :645-659
-    CM_TRY(launch_spmm(st, L, K, spmm_args(s, s->m_x, s->m_r)));
+    CM_TRY(launch_spmm(st, L, K, spmm_args(s, m.x, m.r)));
     int np_full = 0, np_half = 0, np_spmm = 0, rpb = 0;
     spmm_partition(L, n, &np_spmm, &rpb);
-    CM_TRY(launch_init_b(st, K, n, s->m_b, s->m_r, s->m_rw, s->m_p, s->m_parts_full, &np_full));
-    CM_TRY(launch_init_finish_b(st, K, kc, s->m_st, s->m_parts_full, np_full, tol));
+    CM_TRY(launch_init_b(st, K, n, m.b, m.r, m.rw, m.p, m.parts_full, &np_full));
+    CM_TRY(launch_init_finish_b(st, K, kc, m.st, m.parts_full, np_full, tol));
     for (int k = 0; k < maxit; k++) {
-        if (k >= kLag) {              // lagged look at the progress word of iteration k - kLag (run_host_loop, loops.hip)
-            const int j = k - kLag;
-            volatile unsigned long long *slot = &s->snap_host[j % kRing];
-            unsigned long long w = *slot;
-            if ((unsigned)(w >> 32) != (unsigned)(j + 1)) {
-                const double t_wait = now_s();
-                while ((unsigned)((w = *slot) >> 32) != (unsigned)(j + 1)) {
-                    __builtin_ia32_pause();
-                    if (now_s() - t_wait > 30.0) {
-                        const double t_drain = now_s();
-                        while (hipStreamQuery(st) == hipErrorNotReady && now_s() - t_drain < 5.0) __builtin_ia32_pause();
-                        set_error("batched iteration %d did not report progress within 30 s", j);
-                        return CUDAMAT_ERR_HIP;
-                    }
-                }
-            }
+        if (k >= kLag) {              // lagged look at the progress word of iteration k - kLag
+            unsigned long long w = 0;
+            CM_TRY(wait_progress(s, st, k - kLag, "batched ", &w));
             if ((unsigned)(w & 0xffffffffULL) != 0u) break;    // every column has stopped
         }
         la.k = k;
         // rho, beta, full-step tests, p = r + beta (p - omega v)                            :80-89
-        CM_TRY(launch_update_p_b(st, K, la, s->m_parts_full, np_full, n, s->m_r, s->m_p, s->m_v));
-        const double *pw = s->m_p;
+        CM_TRY(launch_update_p_b(st, K, la, m.parts_full, np_full, n, m.r, m.p, m.v));
+        const double *pw = m.p;
         if (pc) {                                                                           // :92-98
-            CM_TRY(precond_apply_b(s, K, s->m_p, s->m_lt, s->m_pw));
-            pw = s->m_pw;
+            CM_TRY(precond_apply_b(s, K, m.p, m.lt, m.pw));
+            pw = m.pw;
         }
         // v = A pw, rw.v                                                                      :104-106
-        SpmmArgs a1 = spmm_args(s, pw, s->m_v);
-        a1.dot = 1; a1.w = s->m_rw; a1.parts = s->m_parts_rv; a1.loop = la;
+        SpmmArgs a1 = spmm_args(s, pw, m.v);
+        a1.dot = 1; a1.w = m.rw; a1.parts = m.parts_rv; a1.loop = la;
         CM_TRY(launch_spmm(st, L, K, a1));
         // alpha, r -= alpha v, ||r||                                                          :107-111
-        CM_TRY(launch_half_b(st, K, la, s->m_parts_rv, np_spmm, n, s->m_r, s->m_v, s->m_parts_half, &np_half));
+        CM_TRY(launch_half_b(st, K, la, m.parts_rv, np_spmm, n, m.r, m.v, m.parts_half, &np_half));
         // half-step tests; t = A sv (sv = r, or M^-1 r), (t.r, t.t)                           :116, :121-127, :132-136
-        const double *sv = s->m_r;
+        const double *sv = m.r;
         if (pc) {              // the tests are decided before M^-1 r is computed, as in Solve::iterate_reference
-            CM_TRY(launch_check_half_b(st, K, la, s->m_parts_half, np_half));
-            CM_TRY(precond_apply_b(s, K, s->m_r, s->m_lt, s->m_s));
-            sv = s->m_s;
+            CM_TRY(launch_check_half_b(st, K, la, m.parts_half, np_half));
+            CM_TRY(precond_apply_b(s, K, m.r, m.lt, m.s));
+            sv = m.s;
         }
-        SpmmArgs a2 = spmm_args(s, sv, s->m_t);
-        a2.dot = 2; a2.w = s->m_r; a2.parts = s->m_parts_tt; a2.loop = la;
-        if (!pc) { a2.check = CHECK_HALF; a2.half = s->m_parts_half; a2.half_count = np_half; }
+        SpmmArgs a2 = spmm_args(s, sv, m.t);
+        a2.dot = 2; a2.w = m.r; a2.parts = m.parts_tt; a2.loop = la;
+        if (!pc) { a2.check = CHECK_HALF; a2.half = m.parts_half; a2.half_count = np_half; }
         CM_TRY(launch_spmm(st, L, K, a2));
         // omega, x += alpha pw, x += omega sv, r -= omega t, (rw.r, ||r||), i++              :110, :137-151
-        CM_TRY(launch_full_b(st, K, la, s->m_parts_tt, np_spmm, n, s->m_x, sv, s->m_r, s->m_t, s->m_rw, pw,
-                             s->m_parts_full, &np_full));
+        CM_TRY(launch_full_b(st, K, la, m.parts_tt, np_spmm, n, m.x, sv, m.r, m.t, m.rw, pw,
+                             m.parts_full, &np_full));
     }
     // the last full-step tests; columns that left through the half step still owe x += alpha pw (:110)
-    CM_TRY(launch_check_full_b(st, K, la, s->m_parts_full, np_full));
-    CM_TRY(launch_half_exit_b(st, K, s->m_st, n, pc ? s->m_pw : s->m_p, s->m_x));
-    CM_HIP(hipMemcpyAsync(fin, s->m_st, sizeof(LoopState) * (size_t)K, hipMemcpyDeviceToHost, st));
-    if (X) CM_TRY(launch_batch_out(st, K, kc, n, s->m_x, X, ldx));
+    CM_TRY(launch_check_full_b(st, K, la, m.parts_full, np_full));
+    CM_TRY(launch_half_exit_b(st, K, m.st, n, pc ? m.pw : m.p, m.x));
+    CM_HIP(hipMemcpyAsync(fin, m.st, sizeof(LoopState) * (size_t)K, hipMemcpyDeviceToHost, st));
+    if (X) CM_TRY(launch_batch_out(st, K, kc, n, m.x, X, ldx));
     CM_HIP(hipStreamSynchronize(st));
     if (t_loop) *t_loop = now_s() - t0;
     if (hist_out) {
         for (int j = 0; j < kc; j++) {
-            int c = loop != CUDAMAT_LOOP_PBICGSTAB2 ? 2 * fin[j].it + (fin[j].state == 1 ? 1 : 0) : fin[j].it;
-            if (c > need) c = need;
+            const int c = history_count(loop, fin[j], need);
             hist_out[j].assign((size_t)c, 0.0);
             if (c > 0)
                 CM_HIP(hipMemcpy(hist_out[j].data(), hist + (size_t)j * (size_t)need, sizeof(double) * (size_t)c,
@@ -252,39 +250,40 @@ int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, do
 // added to *t_tune.
 int prefer_batched(cudamat_solver *s, int K, int kc, int precond, int loop, bool *batched, double *t_tune)
 {
+    ManyWork &m = s->many;
     const double t0 = now_s();
     hipStream_t st = s->ctx->stream;
     const int n = s->n;
-    if (s->m_tune_loop != loop || s->m_tune_precond != precond) {
-        s->m_tune_loop = loop;
-        s->m_tune_precond = precond;
-        s->m_t_single = -1.0;
-        for (double &t : s->m_t_batch) t = -1.0;
+    if (m.tune_loop != loop || m.tune_precond != precond) {
+        m.tune_loop = loop;
+        m.tune_precond = precond;
+        m.t_single = -1.0;
+        for (double &t : m.t_batch) t = -1.0;
         // a few iterations: enough that launch and set-up overheads do not decide (small systems run ~10 us per iteration)
         const double it = 4e7 / (double)(s->nnz + 1);
-        s->m_tune_iters = it < 4.0 ? 4 : it > 64.0 ? 64 : (int)it;
+        m.tune_iters = it < 4.0 ? 4 : it > 64.0 ? 64 : (int)it;
     }
-    const int N = s->m_tune_iters;
-    if (s->m_t_single < 0.0) {
+    const int N = m.tune_iters;
+    if (m.t_single < 0.0) {
         CM_TRY(ensure_work(s));
         CM_TRY(ensure_spmv_mode(s));
         for (int rep = 0; rep < 2; rep++) {       // (the first run warms up: the loop forms allocate on first use)
-            CM_TRY(launch_fill(st, n, 1.0, s->m_b));
-            CM_TRY(launch_fill(st, n, 0.0, s->m_x));
+            CM_TRY(launch_fill(st, n, 1.0, m.b));
+            CM_TRY(launch_fill(st, n, 0.0, m.x));
             CM_HIP(hipStreamSynchronize(st));
             const double t = now_s();
             cudamat_stats dummy;
-            CM_TRY(cudamat_solver_solve(s, s->m_b, s->m_x, precond, loop, rep ? N : 2, 1e-8, CUDAMAT_FLAG_NO_EXIT, &dummy));
+            CM_TRY(cudamat_solver_solve(s, m.b, m.x, precond, loop, rep ? N : 2, 1e-8, CUDAMAT_FLAG_NO_EXIT, &dummy));
             CM_HIP(hipStreamSynchronize(st));
-            s->m_t_single = now_s() - t;
+            m.t_single = now_s() - t;
         }
     }
-    double &tb = s->m_t_batch[log2_cols(K)];
+    double &tb = m.t_batch[log2_cols(K)];
     if (tb < 0.0) {
         LoopState fin[kBatchMax];
         for (int rep = 0; rep < 2; rep++) {
-            CM_TRY(launch_fill(st, (int64_t)K * n, 1.0, s->m_b));
-            CM_TRY(launch_fill(st, (int64_t)K * n, 0.0, s->m_x));
+            CM_TRY(launch_fill(st, (int64_t)K * n, 1.0, m.b));
+            CM_TRY(launch_fill(st, (int64_t)K * n, 0.0, m.x));
             CM_HIP(hipStreamSynchronize(st));
             const double t = now_s();
             CM_TRY(run_group(s, K, K, nullptr, 0, nullptr, 0, precond, loop, rep ? N : 2, 1e-8, CUDAMAT_FLAG_NO_EXIT, fin,
@@ -293,10 +292,10 @@ int prefer_batched(cudamat_solver *s, int K, int kc, int precond, int loop, bool
         }
     }
     // batched only when clearly faster (3 %: below that the two are within the noise of one timing)
-    *batched = tb < 0.97 * (double)kc * s->m_t_single;
+    *batched = tb < 0.97 * (double)kc * m.t_single;
     if (s->ctx->cfg.verbose)
         fprintf(stderr, "[cudamat] several right-hand sides%s: %d iterations, single loop %.3f ms x %d columns, batched (K = %d) "
-                        "%.3f ms -> %s\n", precond ? " with ILU(0)" : "", N, 1e3 * s->m_t_single, kc, K, 1e3 * tb,
+                        "%.3f ms -> %s\n", precond ? " with ILU(0)" : "", N, 1e3 * m.t_single, kc, K, 1e3 * tb,
                 *batched ? "batched" : "columns");
     *t_tune += now_s() - t0;
     return CUDAMAT_OK;
@@ -304,22 +303,12 @@ int prefer_batched(cudamat_solver *s, int K, int kc, int precond, int loop, bool
 
 void fill_stats(cudamat_solver *s, const LoopState &f, int precond, cudamat_stats *o)
 {
-    memset(o, 0, sizeof(*o));
-    o->iters = f.it;
-    o->half_exit = f.state == 1;
-    o->converged = f.state == 1 || f.state == 2;
-    o->breakdown = f.state == 3;
-    o->nrm0 = f.nrm0;
-    o->nrm = f.nrm;
+    stats_from_state(f, o);
     o->loop_form = 0;
     o->spmv_mode = 0;                    // the SpMM runs on the CSR arrays
     o->t_setup = s->t_create + s->t_spmv_setup;
     if (precond) {                       // as Solve::finish reports them; the level-scheduled kernels have no fall-back
-        o->t_analysis = s->t_analysis;
-        o->t_factor = s->t_factor;
-        o->n_levels_l = s->L.nlevels;
-        o->n_levels_u = s->U.nlevels;
-        o->trsv_form = trsv_form_code(s);
+        stats_ilu0(s, true, o);
         o->trsv_fallbacks = 0;
     }
 }
@@ -334,19 +323,18 @@ extern "C" int cudamat_solver_spmm(cudamat_solver *s, int nrhs, const double *X,
     CM_ARG(X && Y, "null pointer");
     CM_ARG((int64_t)ldx >= (s->sharded ? (int64_t)s->n : s->n_cols) && ldy >= s->n, "leading dimension below the rows");
     CM_HIP(hipSetDevice(s->ctx->device));
-    int rc = s->sharded ? CUDAMAT_ERR_NOMEM : ensure_many(s, pow2_cols(nrhs < kBatchMax ? nrhs : kBatchMax));
-    if (rc == CUDAMAT_ERR_NOMEM) {       // sharded, or no room for the interleaved buffers: one SpMV per column
+    bool batched = !s->sharded;
+    if (batched) CM_TRY(many_room(s, nrhs, false, &batched));
+    if (!batched) {                      // sharded, or no room for the interleaved buffers: one SpMV per column
         for (int j = 0; j < nrhs; j++) CM_TRY(cudamat_solver_spmv(s, X + (size_t)j * ldx, Y + (size_t)j * ldy));
         return CUDAMAT_OK;
     }
-    CM_TRY(rc);
+    ManyWork &m = s->many;
     hipStream_t st = s->ctx->stream;
-    for (int c0 = 0; c0 < nrhs; c0 += kBatchMax) {
-        const int kc = nrhs - c0 < kBatchMax ? nrhs - c0 : kBatchMax;
-        const int K = pow2_cols(kc);
-        CM_TRY(launch_batch_in(st, K, kc, s->n_cols, many_rows(s), X + (size_t)c0 * ldx, ldx, 0.0, s->m_x));
-        CM_TRY(launch_spmm(st, s->plan.lanes, K, spmm_args(s, s->m_x, s->m_t)));
-        CM_TRY(launch_batch_out(st, K, kc, s->n, s->m_t, Y + (size_t)c0 * ldy, ldy));
+    for (const ColBlock &c : col_blocks(nrhs)) {
+        CM_TRY(launch_batch_in(st, c.K, c.kc, s->n_cols, many_rows(s), X + (size_t)c.c0 * ldx, ldx, 0.0, m.x));
+        CM_TRY(launch_spmm(st, s->plan.lanes, c.K, spmm_args(s, m.x, m.t)));
+        CM_TRY(launch_batch_out(st, c.K, c.kc, s->n, m.t, Y + (size_t)c.c0 * ldy, ldy));
     }
     return CUDAMAT_OK;
 }
@@ -360,20 +348,19 @@ extern "C" int cudamat_solver_precond_apply_many(cudamat_solver *s, int nrhs, co
     CM_ARG(ldin >= s->n && ldout >= s->n, "leading dimension below the rows");
     CM_ARG(s->has_ilu, "call cudamat_solver_ilu0 / cudamat_solver_block_ilu0 first");
     CM_HIP(hipSetDevice(s->ctx->device));
-    int rc = trsm_covered(s) ? ensure_many(s, pow2_cols(nrhs < kBatchMax ? nrhs : kBatchMax)) : CUDAMAT_ERR_NOMEM;
-    if (rc == CUDAMAT_ERR_NOMEM) {       // factors the multi-column kernels do not cover, or no room: one application per column
+    bool batched = trsm_covered(s);
+    if (batched) CM_TRY(many_room(s, nrhs, false, &batched));
+    if (!batched) {                      // factors the multi-column kernels do not cover, or no room: one application per column
         CM_TRY(ensure_work(s));
         for (int j = 0; j < nrhs; j++) CM_TRY(precond_apply(s, In + (size_t)j * ldin, s->t, Out + (size_t)j * ldout));
         return CUDAMAT_OK;
     }
-    CM_TRY(rc);
+    ManyWork &m = s->many;
     hipStream_t st = s->ctx->stream;
-    for (int c0 = 0; c0 < nrhs; c0 += kBatchMax) {
-        const int kc = nrhs - c0 < kBatchMax ? nrhs - c0 : kBatchMax;
-        const int K = pow2_cols(kc);
-        CM_TRY(launch_batch_in(st, K, kc, s->n, s->n, In + (size_t)c0 * ldin, ldin, 0.0, s->m_b));
-        CM_TRY(precond_apply_b(s, K, s->m_b, s->m_t, s->m_x));
-        CM_TRY(launch_batch_out(st, K, kc, s->n, s->m_x, Out + (size_t)c0 * ldout, ldout));
+    for (const ColBlock &c : col_blocks(nrhs)) {
+        CM_TRY(launch_batch_in(st, c.K, c.kc, s->n, s->n, In + (size_t)c.c0 * ldin, ldin, 0.0, m.b));
+        CM_TRY(precond_apply_b(s, c.K, m.b, m.t, m.x));
+        CM_TRY(launch_batch_out(st, c.K, c.kc, s->n, m.x, Out + (size_t)c.c0 * ldout, ldout));
     }
     return CUDAMAT_OK;
 }
@@ -411,19 +398,14 @@ extern "C" int cudamat_solver_solve_many(cudamat_solver *s, int nrhs, const doub
     const bool batchable = plain || pc;
     bool room = false;
     if (batchable && cfg.many_form != 2) {
-        const int Kmax = pow2_cols(nrhs < kBatchMax ? nrhs : kBatchMax);
-        int rc = ensure_many(s, Kmax);
-        if (rc == CUDAMAT_OK && pc) rc = ensure_many_precond(s, Kmax);
-        if (rc != CUDAMAT_OK && rc != CUDAMAT_ERR_NOMEM) return rc;
-        room = rc == CUDAMAT_OK;
+        CM_TRY(many_room(s, nrhs, pc, &room));
         if (!room && cfg.verbose) fprintf(stderr, "[cudamat] no room for the batched loop's buffers: column by column\n");
     }
     const int pc_precond = pc ? CUDAMAT_PRECOND_ILU0 : CUDAMAT_PRECOND_NONE;
     const bool force_batched = pc ? cfg.many_precond == 2 : cfg.many_form == 1;
     const bool by_timing = pc ? cfg.many_precond == 1 : cfg.many_form == 0;
-    for (int c0 = 0; c0 < nrhs; c0 += kBatchMax) {
-        const int kc = nrhs - c0 < kBatchMax ? nrhs - c0 : kBatchMax;
-        const int K = pow2_cols(kc);
+    for (const ColBlock &c : col_blocks(nrhs)) {
+        const int c0 = c.c0, kc = c.kc, K = c.K;
         bool batched = room && force_batched;
         if (room && by_timing) CM_TRY(prefer_batched(s, K, kc, pc_precond, loop, &batched, &t_tune));
         if (batched) {
@@ -446,7 +428,7 @@ extern "C" int cudamat_solver_solve_many(cudamat_solver *s, int nrhs, const doub
             if (!h.empty()) CM_TRY(cudamat_solver_history(s, h.data(), (int)h.size(), &cnt));
         }
     }
-    s->m_hist_host.swap(hists);
+    s->many.hist_host.swap(hists);
     const double t_total = now_s() - t0;
     for (cudamat_stats &o : out) {
         o.t_solve = t_solve;
@@ -461,8 +443,8 @@ extern "C" int cudamat_solver_solve_many(cudamat_solver *s, int nrhs, const doub
 extern "C" int cudamat_solver_history_col(cudamat_solver *s, int col, double *hist_host, int cap, int *count)
 {
     CM_ARG(s && count, "null pointer");
-    CM_ARG(col >= 0 && (size_t)col < s->m_hist_host.size(), "no such column in the last cudamat_solver_solve_many");
-    const std::vector<double> &h = s->m_hist_host[(size_t)col];
+    CM_ARG(col >= 0 && (size_t)col < s->many.hist_host.size(), "no such column in the last cudamat_solver_solve_many");
+    const std::vector<double> &h = s->many.hist_host[(size_t)col];
     int c = (int)h.size() < cap ? (int)h.size() : cap;
     if (c < 0) c = 0;
     if (c > 0) {

@@ -15,7 +15,6 @@
 #include <string.h>
 
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -24,11 +23,6 @@
 #include "common.h"
 
 namespace {
-
-double now_s()
-{
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // A barrier a failed rank can BREAK: every thread waiting in it, or arriving later, returns false.  (With a
 // pthread barrier a rank thread that left after an error would leave its peers waiting for ever.)
@@ -269,7 +263,7 @@ extern "C" int cudamat_solve_sharded(int ngpu, int n, int nnz, const double *A, 
     CM_ARG((base == 0 || base == 1) && iA[n] - base == nnz, "iA[0] must be 0 or 1 and nnz == iA[n] - iA[0]");
     CM_ARG(precond != CUDAMAT_PRECOND_ILU0, "ILU(0) of the whole matrix does not shard: use CUDAMAT_PRECOND_BLOCK_ILU0");
     CM_ARG(ngpu <= n, "more ranks than rows");
-    const double t0 = now_s();
+    const double t0 = cm::now_s();
     cudamat_plan_cache_clear();          // what cudamat_solve keeps on device 0 (several GB) is needed by the ranks
     Shared sh;
     sh.world = ngpu;
@@ -308,7 +302,7 @@ extern "C" int cudamat_solve_sharded(int ngpu, int n, int nnz, const double *A, 
         }
     if (out) {
         *out = jobs[0].st;                       // every rank takes the same decisions (all-reduced scalars)
-        out->t_total = now_s() - t0;
+        out->t_total = cm::now_s() - t0;
     }
     return rc;
 }

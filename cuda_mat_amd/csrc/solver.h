@@ -30,6 +30,25 @@ struct TriFactor {                 // one triangular factor in level-major stora
     bool lm = false;
 };
 
+// several right-hand sides (loops_batch.hip): the work of the batched loop, allocated at the first batched solve or SpMM and
+// released with the solver.  Two groups of interleaved buffers, each allocated and released as a whole.
+struct ManyWork {
+    // the plain loop: seven vectors of `cap` columns, the partial sums, `cap` loop states (device)
+    int cap = 0;                // columns the group holds (0: not allocated)
+    double *r = nullptr, *rw = nullptr, *p = nullptr, *v = nullptr, *t = nullptr, *b = nullptr, *x = nullptr;
+    double *parts_full = nullptr, *parts_rv = nullptr, *parts_half = nullptr, *parts_tt = nullptr;
+    LoopState *st = nullptr;
+    // the preconditioned loop: M^-1 p, M^-1 r and the scratch of L^-1 (`pcap` columns; allocated at its first use)
+    int pcap = 0;
+    double *pw = nullptr, *s = nullptr, *lt = nullptr;
+    double *hist = nullptr;     // device: per column a history of the batch's length (hist_bytes in all)
+    size_t hist_bytes = 0;
+    std::vector<std::vector<double>> hist_host;   // per column: the residual history of the last cudamat_solver_solve_many
+    // form choice (MANY_FORM / MANY_PRECOND = auto): seconds of tune_iters iterations, single loop (< 0: not timed) and batched by log2 K
+    double t_single = -1.0, t_batch[4] = {-1.0, -1.0, -1.0, -1.0};
+    int tune_loop = -1, tune_precond = -1, tune_iters = 0;
+};
+
 }  // namespace cm
 
 struct cudamat_solver {
@@ -145,22 +164,7 @@ struct cudamat_solver {
     int device_cus = 0;         // compute units of the device (0: not asked yet)
     int loop_fallbacks = 0;     // solves redone with the three-launch loop for that reason
 
-    // several right-hand sides (loops_batch.hip): interleaved work vectors of the batched loop, K_cap columns each, allocated at
-    // the first batched solve or SpMM and released with the solver
-    int m_cap = 0;              // columns the buffers below hold (0: not allocated)
-    double *m_r = nullptr, *m_rw = nullptr, *m_p = nullptr, *m_v = nullptr, *m_t = nullptr, *m_b = nullptr, *m_x = nullptr;
-    double *m_parts_full = nullptr, *m_parts_rv = nullptr, *m_parts_half = nullptr, *m_parts_tt = nullptr;
-    // the preconditioned batched loop: M^-1 p, M^-1 r and the scratch of L^-1 (m_pcap columns; allocated at its first use)
-    int m_pcap = 0;
-    double *m_pw = nullptr, *m_s = nullptr, *m_lt = nullptr;
-    cm::LoopState *m_st = nullptr;     // device, m_cap states
-    double *m_hist = nullptr;          // device: per column a history of the batch's length (m_hist_bytes in all)
-    size_t m_hist_bytes = 0;
-    bool m_failed = false;             // the buffers did not fit: solves with several right-hand sides run column by column
-    std::vector<std::vector<double>> m_hist_host;   // per column: the residual history of the last cudamat_solver_solve_many
-    // form choice (MANY_FORM / MANY_PRECOND = auto): seconds of m_tune_iters iterations, single loop (< 0: not timed) and batched by log2 K
-    double m_t_single = -1.0, m_t_batch[4] = {-1.0, -1.0, -1.0, -1.0};
-    int m_tune_loop = -1, m_tune_precond = -1, m_tune_iters = 0;
+    cm::ManyWork many;          // several right-hand sides (loops_batch.hip)
 };
 
 namespace cm {
@@ -214,4 +218,17 @@ int trsv_form_code(cudamat_solver *s);           // 0 level launches, 1 dependen
 void trsv_group_counts(cudamat_solver *s, int *groups_l, int *groups_u);   // hybrid factors: groups of levels (0: not split)
 void trsv_disable_syncfree(cudamat_solver *s);   // sticky: level-by-level kernels from now on
 void many_release(cudamat_solver *s);            // the buffers of the batched loop (loops_batch.hip)
+// ---- loops.hip: what the single and the batched host loop (loops_batch.hip) share
+// The lagged look at the progress word of iteration j, published through pinned memory by that iteration's last kernel:
+// *word = the word once its upper half says j + 1.  Waits at most 30 s for that, then gives the stream's queued work a
+// bounded chance to drain and fails the solve ("<what>iteration j did not report progress within 30 s").
+int wait_progress(cudamat_solver *s, hipStream_t st, int j, const char *what, unsigned long long *word);
+// residual history: the entries a solve of `maxit` iterations may write (two per iteration, half / full step, or one;
+// capped at 2^20), and the entries a loop that ended in state `f` has written (at most cap)
+int history_need(int loop, int maxit);
+int history_count(int loop, const LoopState &f, int cap);
+// statistics: *o zeroed, then what the final LoopState says (iters, exits, norms); the ILU(0) figures (trsv_form only when
+// the factors were `applied`)
+void stats_from_state(const LoopState &f, cudamat_stats *o);
+void stats_ilu0(cudamat_solver *s, bool applied, cudamat_stats *o);
 }  // namespace cm

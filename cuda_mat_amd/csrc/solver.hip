@@ -20,7 +20,6 @@
 //     kernels; the dot products ride on the kernels that stream the operands.
 //   * row-sharded operation: the same loop, with the SpMV input gathered and the
 //     scalar partials all-reduced through caller-supplied collectives (RCCL).
-#include <chrono>
 #include <mutex>
 #include <utility>
 #include <math.h>
@@ -30,11 +29,6 @@
 #include "solver.h"
 
 using namespace cm;
-
-static double now_s()
-{
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 namespace cm {
 
@@ -775,9 +769,7 @@ static int compute_windows(cudamat_solver *s)
         for (int q = 0; q < W; q++) { h[(size_t)q] = per; h[(size_t)W + q] = 0; }
         hipError_t e = hipMemcpyAsync(d_lohi, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st);
         if (e == hipSuccess && s->nnz > 0) {
-            int grid = (int)((s->nnz + 4096LL * kBlock - 1) / (4096LL * kBlock));
-            grid = grid < 1 ? 1 : grid > 4096 ? 4096 : grid;
-            hipLaunchKernelGGL(k_col_windows, dim3(grid), dim3(kBlock), sizeof(int) * 2 * (size_t)W, st, (long long)s->nnz, s->ci, per, W,
+            hipLaunchKernelGGL(k_col_windows, dim3(row_grid(s->nnz, 4096LL * kBlock)), dim3(kBlock), sizeof(int) * 2 * (size_t)W, st, (long long)s->nnz, s->ci, per, W,
                                d_lohi, d_lohi + W);
         }
         if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_lohi, sizeof(int) * h.size(), hipMemcpyDeviceToHost, st);

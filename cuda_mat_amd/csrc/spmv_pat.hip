@@ -24,7 +24,6 @@
 // row with its table entry -- a hash collision or a row the table cannot describe makes the builder give up, it never
 // produces a wrong copy.  Chosen per matrix by timing it against the other forms (solver.hip, ensure_spmv_mode).
 #include <algorithm>
-#include <chrono>
 #include <vector>
 
 #include "device.h"
@@ -36,11 +35,6 @@ constexpr int kPatChunk = 64;
 constexpr int kPatSlots = 4096;                                  // hash table slots (>= 16 x the patterns it may hold)
 constexpr unsigned long long kPatEmpty = 0xFFFFFFFFFFFFFFFFull;
 constexpr int kPatRow = kPatMaxLen + 1;                          // ints per table row
-
-static double now_s()
-{
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 template <typename T>
 static int dalloc(T **p, size_t count)

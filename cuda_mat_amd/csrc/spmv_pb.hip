@@ -20,7 +20,6 @@
 // one wave, so the result is deterministic (no inter-wave races, no global atomics).
 // HBM traffic per SpMV: 10 B/nnz read + 8 B/nnz written (phase 1), 10 B/nnz read (phase 2).
 #include <algorithm>
-#include <chrono>
 #include <map>
 #include <mutex>
 #include <string>
@@ -40,11 +39,6 @@ constexpr int kTileMax = 13312;        // doubles per y tile of a row block / x 
 constexpr int kPbAlign = 64;           // every column block's entries start on a 64-entry boundary: the 1 KB product stores, the 1 KB value
                                        // loads and the 256-byte column loads of a phase-1 wave then cover whole 128-byte lines (<= 63 idle
                                        // slots per block: value 0 x column 0, never read by phase 2; -4.5 % per C4 SpMV against packed blocks)
-
-static double now_s()
-{
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 template <typename T>
 static int dalloc(T **p, size_t count)

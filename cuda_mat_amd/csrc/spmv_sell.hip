@@ -12,7 +12,6 @@
 // The window sort bounds both the padding and the distance between a row and its output (good for banded x).
 // Chosen per matrix by timing it against the other forms (solver.hip, ensure_spmv_mode).
 #include <algorithm>
-#include <chrono>
 #include <vector>
 
 #include "spmv_sell.h"
@@ -21,11 +20,6 @@ namespace cm {
 
 constexpr int kSigma = 1024;          // rows per sorting window (16 chunks)
 constexpr int kChunk = 64;
-
-static double now_s()
-{
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 template <typename T>
 static int dalloc(T **p, size_t count)

@@ -221,11 +221,8 @@ int launch_trsm_segments(hipStream_t st, const TriFactor &F, const TriHost &H, c
     for (size_t g = 0; g < H.seg_begin.size(); g++) {
         const int l0 = H.seg_begin[g], l1 = H.seg_end[g];
         const int r0 = F.level_ptr[(size_t)l0], r1 = F.level_ptr[(size_t)l1];
-        const bool big = (l1 - l0 == 1) && (r1 - r0 > kSmallLevel);
-        if (big) {
-            int grid = (r1 - r0 + RPB - 1) / RPB;
-            if (grid > 4096) grid = 4096;
-            hipLaunchKernelGGL((k_trsm_level<LANES, K>), dim3(grid), dim3(kBlock), 0, st, r0, r1, F.rp, F.ci, F.val, F.row_of,
+        if (segment_is_wide(F, H, g)) {
+            hipLaunchKernelGGL((k_trsm_level<LANES, K>), dim3(row_grid(r1 - r0, RPB)), dim3(kBlock), 0, st, r0, r1, F.rp, F.ci, F.val, F.row_of,
                                F.dinv, rhs, out);
         } else {
             hipLaunchKernelGGL((k_trsm_small_levels<LANES, K>), dim3(1), dim3(kBlock), 0, st, l0, l1, H.level_ptr_dev, F.rp,
@@ -314,7 +311,7 @@ extern "C" int cudamat_solver_trsm_kernel(cudamat_solver *s, int nrhs, char *nam
     name[0] = 0;
     if (!trsm_covered(s)) return CUDAMAT_OK;          // "": the factors run column by column (trsv.hip)
     IluPlans *pl = plans_of(s, false);
-    const int K = nrhs <= 1 ? 1 : nrhs <= 2 ? 2 : nrhs <= 4 ? 4 : kBatchMax;
+    const int K = pow2_cols(nrhs);
     int used = 0;
     for (int u = 0; u < 2 && used < cap; u++) {
         const TriHost &H = u ? pl->U : pl->L;
@@ -327,8 +324,7 @@ extern "C" int cudamat_solver_trsm_kernel(cudamat_solver *s, int nrhs, char *nam
         }
         bool big = false, small = false;
         for (size_t g = 0; g < H.seg_begin.size(); g++) {
-            const int l0 = H.seg_begin[g], l1 = H.seg_end[g];
-            const bool b = (l1 - l0 == 1) && (F.level_ptr[(size_t)l1] - F.level_ptr[(size_t)l0] > kSmallLevel);
+            const bool b = segment_is_wide(F, H, g);
             big = big || b;
             small = small || !b;
         }

@@ -296,11 +296,8 @@ static int launch_trsv_segments(hipStream_t st, const TriFactor &F, const TriHos
         cur_group = grp;
         const int l0 = H.seg_begin[g], l1 = H.seg_end[g];
         const int r0 = F.level_ptr[(size_t)l0], r1 = F.level_ptr[(size_t)l1];
-        const bool big = (l1 - l0 == 1) && (r1 - r0 > kSmallLevel);
-        if (big) {
-            int grid = (r1 - r0 + RPB - 1) / RPB;
-            if (grid > 4096) grid = 4096;
-            hipLaunchKernelGGL(k_trsv_level<LANES>, dim3(grid), dim3(kBlock), 0, st, r0, r1, F.rp, F.ci, F.val,
+        if (segment_is_wide(F, H, g)) {
+            hipLaunchKernelGGL(k_trsv_level<LANES>, dim3(row_grid(r1 - r0, RPB)), dim3(kBlock), 0, st, r0, r1, F.rp, F.ci, F.val,
                                F.rhs_of, F.out_of, F.dinv, far, rhs, out);
         } else {
             hipLaunchKernelGGL(k_trsv_small_levels<LANES>, dim3(1), dim3(kBlock), 0, st, l0, l1, H.level_ptr_dev,
@@ -465,17 +462,11 @@ __global__ __launch_bounds__(kBlock) void k_perm_scatter(long long n, const int 
     for (long long i = blockIdx.x * (long long)kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) out[map[i]] = in[i];
 }
 
-static unsigned perm_grid(int n)
-{
-    long long g = ((long long)n + kBlock - 1) / kBlock;
-    return (unsigned)(g < 1 ? 1 : g > 4096 ? 4096 : g);
-}
-
 // out[pr] = in[row at position pr of L's (upper: U's) level-major order]
 int perm_to_space(cudamat_solver *s, bool upper, const double *in, double *out)
 {
     const TriFactor &F = upper ? s->U : s->L;
-    hipLaunchKernelGGL(k_perm_gather, dim3(perm_grid(s->n)), dim3(kBlock), 0, s->ctx->stream, (long long)s->n, F.row_of, in, out);
+    hipLaunchKernelGGL(k_perm_gather, dim3(row_grid(s->n)), dim3(kBlock), 0, s->ctx->stream, (long long)s->n, F.row_of, in, out);
     CM_HIP(hipGetLastError());
     return CUDAMAT_OK;
 }
@@ -484,7 +475,7 @@ int perm_to_space(cudamat_solver *s, bool upper, const double *in, double *out)
 int perm_from_space(cudamat_solver *s, bool upper, const double *in, double *out)
 {
     const TriFactor &F = upper ? s->U : s->L;
-    hipLaunchKernelGGL(k_perm_scatter, dim3(perm_grid(s->n)), dim3(kBlock), 0, s->ctx->stream, (long long)s->n, F.row_of, in, out);
+    hipLaunchKernelGGL(k_perm_scatter, dim3(row_grid(s->n)), dim3(kBlock), 0, s->ctx->stream, (long long)s->n, F.row_of, in, out);
     CM_HIP(hipGetLastError());
     return CUDAMAT_OK;
 }
