@@ -5,7 +5,9 @@
 // 8K-byte piece, dwordx4 loads for K >= 2) instead of one double per column and SpMV.  Every column keeps the arithmetic of
 // the single-vector kernels: the same operations in the same order (k_spmv<L>, k_init, k_update_p, k_half, k_full), so that
 // column j of k_spmm_csr<L, K> is bit-identical to k_spmv<L> on column j alone.  A thread owns whole rows (all K columns), the
-// grid and the row partition depend on n and L only: the reduction order of a column does not depend on K.
+// grid and the row partition depend on n and L only: the reduction order of a column does not depend on K.  Within a column
+// the reduction order of a ROW depends on the row's own length and L only: rows of at most 4096 entries are summed by their
+// L lanes, every longer one by the whole workgroup -- however many long rows share a partition (device.h: LongRows).
 // A column whose state is not 0 is never written again: its x, r, p and history keep their bits (stores are masked by
 // column; the mask is uniform over the workgroup, so the branches do not diverge).
 #include "batch.h"
@@ -68,8 +70,8 @@ __device__ __forceinline__ void publish_b(const BatchArgs &la, int all_stopped)
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------- SpMM
-constexpr int kLongRowB = 4096;       // as k_spmv (spmv_csr.hip): rows beyond this are swept by the whole workgroup
-constexpr int kLongRowSlotsB = 32;
+// Long rows as in k_spmv (spmv_csr.hip), through the same helpers (device.h: LongRows): never summed by their group, swept by the
+// whole workgroup in increasing row order however many a partition holds.
 
 template <int L, int K>
 __global__ __launch_bounds__(kBlock) void k_spmm_csr(SpmmArgs a, int rows_per_block)
@@ -93,9 +95,8 @@ __global__ __launch_bounds__(kBlock) void k_spmm_csr(SpmmArgs a, int rows_per_bl
     const int row_begin = (int)(r0 < a.n ? r0 : a.n);
     const int row_end = (int)(r0 + rows_per_block < a.n ? r0 + rows_per_block : a.n);
 
-    __shared__ int long_rows[kLongRowSlotsB];
-    __shared__ int n_long;
-    if (threadIdx.x == 0) n_long = 0;
+    __shared__ LongRows lr;
+    if (threadIdx.x == 0) lr.noted = 0;
     __syncthreads();
 
     double acc[2 * K];
@@ -103,14 +104,9 @@ __global__ __launch_bounds__(kBlock) void k_spmm_csr(SpmmArgs a, int rows_per_bl
     for (int q = 0; q < 2 * K; q++) acc[q] = 0.0;
     for (int row = row_begin + group; row < row_end; row += RPB) {
         const int s = a.rp[row], e = a.rp[row + 1];
-        if (e - s > kLongRowB) {
-            int took = 0;
-            if (lane == 0) {
-                const int slot = atomicAdd(&n_long, 1);
-                if (slot < kLongRowSlotsB) { long_rows[slot] = row; took = 1; }
-            }
-            took = __shfl(took, (int)(threadIdx.x & 63) & ~(L - 1), 64);
-            if (took) continue;
+        if (e - s > kLongRow) {
+            if (lane == 0) long_rows_note(lr, row);
+            continue;
         }
         double sum[K];
 #pragma unroll
@@ -145,19 +141,9 @@ __global__ __launch_bounds__(kBlock) void k_spmm_csr(SpmmArgs a, int rows_per_bl
         }
     }
     __syncthreads();
-    const int nl = n_long < kLongRowSlotsB ? n_long : kLongRowSlotsB;
-    if (nl > 0) {
-        if (threadIdx.x == 0) {            // increasing row order
-            for (int i = 1; i < nl; i++) {
-                const int r = long_rows[i];
-                int j = i - 1;
-                while (j >= 0 && long_rows[j] > r) { long_rows[j + 1] = long_rows[j]; j--; }
-                long_rows[j + 1] = r;
-            }
-        }
-        __syncthreads();
+    for (int done = 0, nl; (nl = long_rows_round(lr, a.rp, row_begin, row_end, done)) > 0; done += nl) {
         for (int i = 0; i < nl; i++) {
-            const int row = long_rows[i];
+            const int row = lr.rows[i];
             const int s = a.rp[row], e = a.rp[row + 1];
             double part[K];
 #pragma unroll

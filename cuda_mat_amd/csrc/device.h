@@ -42,6 +42,58 @@ __device__ __forceinline__ void block_sum(double (&v)[K], double *lds)
         v[k] = ((lds[0 * K + k] + lds[1 * K + k]) + lds[2 * K + k]) + lds[3 * K + k];
 }
 
+// ------------------------------------ long rows of the lanes-per-row kernels (k_spmv<L>, k_spmm_csr<L, K>)
+// A row with more than kLongRow entries is NEVER summed by its group of L lanes: the group's first lane notes it
+// (long_rows_note), and after the short rows the whole workgroup sweeps every noted row with its 256 lanes (lane-strided
+// partial sums, block_sum) in increasing row order.  The contract: the reduction order of a row depends on its own length
+// and L only -- not on how many long rows share its partition, nor on the order in which the waves met them.
+// The table holds kLongRowSlots ids.  A partition with more long rows than that (rows_per_block >= 64: L <= 4, or
+// n > 2048 * 256 / L) takes them in rounds: the ids the groups wrote are dropped (which rows found a slot depends on wave
+// scheduling) and thread 0 lists the partition's long rows straight from rp, in order, kLongRowSlots per round.
+constexpr int kLongRow = 4096;
+constexpr int kLongRowSlots = 32;
+
+struct LongRows {                 // one per workgroup, in LDS; noted = 0 before the short-row loop
+    int rows[kLongRowSlots];
+    int noted;                    // long rows the groups met (may exceed the slots)
+    int count;                    // ids in rows[] for the round being swept
+    int next;                     // more long rows than slots: the first row not examined yet
+};
+
+__device__ __forceinline__ void long_rows_note(LongRows &t, int row)
+{
+    const int slot = atomicAdd(&t.noted, 1);
+    if (slot < kLongRowSlots) t.rows[slot] = row;
+}
+
+// Called by the whole workgroup after the barrier that ends the short-row loop, and again after each round's sweep (`done` =
+// long rows swept so far; a sweep of >= 1 row passes block_sum's barriers, so nobody still reads the previous round's ids).
+// Returns the number of ids now in t.rows, increasing; 0: every long row has been swept.  Uniform over the workgroup.
+__device__ __forceinline__ int long_rows_round(LongRows &t, const int *rp, int row_begin, int row_end, int done)
+{
+    const int total = t.noted;
+    if (done >= total) return 0;
+    if (threadIdx.x == 0) {
+        if (total <= kLongRowSlots) {      // insertion sort of a handful of ids
+            for (int i = 1; i < total; i++) {
+                const int r = t.rows[i];
+                int j = i - 1;
+                while (j >= 0 && t.rows[j] > r) { t.rows[j + 1] = t.rows[j]; j--; }
+                t.rows[j + 1] = r;
+            }
+            t.count = total;
+        } else {
+            int r = done == 0 ? row_begin : t.next, m = 0;
+            for (; r < row_end && m < kLongRowSlots; r++)
+                if (rp[r + 1] - rp[r] > kLongRow) t.rows[m++] = r;
+            t.count = m;
+            t.next = r;
+        }
+    }
+    __syncthreads();
+    return t.count;
+}
+
 template <int K>
 __device__ __forceinline__ void load_scalars(const ScalarSrc &s, double (&out)[K], double *lds)
 {

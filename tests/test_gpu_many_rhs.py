@@ -168,7 +168,8 @@ def test_spmm_real_data_tolerance(cm, ctx, oracle):
 @pytest.mark.parametrize("lanes", [2, 8, 32])
 def test_spmm_column_is_the_single_spmv(cm, ctx, oracle, lanes, sw):
     """SPMV_MODE = csr, SPMV_LANES = L: column j of the SpMM is bit-identical to Solver.spmv of column j (k_spmv<L>), on
-    real-valued data (with rows long enough for the whole-workgroup sweep)"""
+    real-valued data with 12 entries per row: every row is summed by its group of L lanes.  (Rows above 4096 entries, which the
+    whole workgroup sweeps, are in tests/test_gpu_long_rows.py::test_spmm_sweep_is_the_spmv_sweep.)"""
     sw("SPMV_MODE", "csr")
     sw("SPMV_LANES", str(lanes))
     rng = np.random.default_rng(lanes)
