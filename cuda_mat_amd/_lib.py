@@ -134,6 +134,11 @@ _SIGS = {
     "cudamat_solver_history_col": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
     "cudamat_solve_many": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_double, _P, C.POINTER(C.c_int)]),
+    "cudamat_solver_spmm_shifts": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int]),
+    "cudamat_solver_solve_shifts": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.c_double, C.c_int, _P, C.POINTER(C.c_int)]),
+    "cudamat_solve_shifts": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int,
+                                       C.c_int, C.c_int, C.c_double, _P, C.POINTER(C.c_int)]),
     "cudamat_solve": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int,
                                 C.c_double, C.c_int, _P, C.POINTER(Stats)]),
     "cudamat_plan_cache_clear": (C.c_int, []),

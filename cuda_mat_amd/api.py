@@ -6,6 +6,7 @@ Names and argument meaning follow pbicgstab.h / mmio_wrapper.h of the reference:
   bicgstab_lu_precond(n, nnz, A, iA, jA, b, maxit, tol, debug)       pbicgstab.h:119
   bicgstab_many(n, nnz, A, iA, jA, B, maxit, tol, d, x0)             bicgstab / bicgstab_d for the columns of B (new)
   bicgstab_lu_precond_many(n, nnz, A, iA, jA, B, maxit, tol)         bicgstab_lu_precond for the columns of B (new)
+  bicgstab_d_many(n, nnz, A0, iA0, jA0, D, x0, B, maxit, tol)        bicgstab_d with shift D[:, j] for column j of B (new)
   loadMMSparseMatrix(filename, elem_type, csrFormat)                 mmio_wrapper.h:133
   toDenseVector(n, nnz, A, IA)                                       pbicgstab.cu:1101
 Each solver returns (ok, x, dtAlg, stats): `ok` is the reference's bool, x the
@@ -106,6 +107,40 @@ def bicgstab_many(n, nnz, A, iA, jA, B, maxit, tol, d=None, x0=None):
     form = C.c_int(0)
     check(_lib.lib().cudamat_solve_many(n, nnz, _vp(A), _vp(iA), _vp(jA), _vp(d), k, _vp(Bf), n, _vp(x0f), _vp(X), n,
                                         PRECOND_NONE, LOOP_PBICGSTAB2, maxit, tol, st, C.byref(form)))
+    stats = [st[j] for j in range(k)]
+    return [bool(s.converged) for s in stats], np.ascontiguousarray(X), (stats[0].t_solve if k else 0.0), stats, form.value
+
+
+def bicgstab_d_many(n, nnz, A0, iA0, jA0, D, x0, B, maxit, tol):
+    """bicgstab_d for a family of shifted systems (A0 + I*d_j) x_j = b_j in one call (cudamat_solve_shifts): the matrix is
+    shared, column j of B is solved with the shift D[:, j].  D: shape (n, k), or k scalars sigma_j meaning d_j = sigma_j * 1
+    (broadcast here; the library sees a block).  x0: shape (n, k), or None for ones.  The same loop (LOOP_PBICGSTAB2) and plan
+    cache as bicgstab_many -- the cache compares the matrix, not the shifts, so a call with the same A0 and other shifts reuses
+    the plan.  Returns what bicgstab_many returns: (ok, X, dtAlg, stats, form)."""
+    A0, iA0, jA0 = _np(A0, np.float64), _np(iA0, np.int32), _np(jA0, np.int32)
+    B = np.asarray(B, dtype=np.float64)
+    if B.ndim == 1:
+        B = B[:, None]
+    if len(iA0) != n + 1 or len(A0) < nnz or len(jA0) < nnz or B.ndim != 2 or B.shape[0] != n:
+        raise ValueError("array sizes do not match n / nnz")
+    k = B.shape[1]
+    D = np.asarray(D, dtype=np.float64)
+    if D.ndim == 1 and D.shape[0] == k:
+        D = np.broadcast_to(D[None, :], (n, k))
+    if D.shape != (n, k):
+        raise ValueError("D must have shape (n, k) = (%d, %d), or hold k scalars; got %s" % (n, k, D.shape))
+    Df, Bf = np.asfortranarray(D), np.asfortranarray(B)
+    x0f = None
+    if x0 is not None:
+        x0f = np.asarray(x0, dtype=np.float64)
+        if x0f.size != n * k:
+            raise ValueError("x0 must have shape (n, k)")
+        x0f = np.asfortranarray(x0f.reshape(n, k))
+    X = np.zeros((n, k), order="F")
+    st = (Stats * max(k, 1))()
+    form = C.c_int(0)
+    check(_lib.lib().cudamat_solve_shifts(n, nnz, _vp(A0), _vp(iA0), _vp(jA0), k, _vp(Df), n, _vp(Bf), n, _vp(x0f), _vp(X), n,
+                                          LOOP_PBICGSTAB2, maxit, tol, st, C.byref(form)))
     stats = [st[j] for j in range(k)]
     return [bool(s.converged) for s in stats], np.ascontiguousarray(X), (stats[0].t_solve if k else 0.0), stats, form.value
 
@@ -455,4 +490,18 @@ class Solver:
         form = C.c_int(0)
         check(_lib.lib().cudamat_solver_solve_many(self.h, int(nrhs), _ptr(B), int(ldb), _ptr(X), int(ldx), precond, loop,
                                                    maxit, tol, flags, st, C.byref(form)))
+        return [st[j] for j in range(int(nrhs))], form.value
+
+    def spmm_shifts(self, nrhs, X, ldx, D, ldd, Y, ldy):
+        """Y_j = (A0 + diag D_j) X_j for nrhs column-major device blocks: one shift vector per column, which replaces the
+        solver's own shift for this call only"""
+        check(_lib.lib().cudamat_solver_spmm_shifts(self.h, int(nrhs), _ptr(X), int(ldx), _ptr(D), int(ldd), _ptr(Y), int(ldy)))
+
+    def solve_shifts(self, nrhs, D, ldd, B, ldb, X, ldx, precond=PRECOND_NONE, loop=LOOP_PBICGSTAB, maxit=2000, tol=1e-8,
+                     flags=0):
+        """(A0 + diag D_j) x_j = b_j for nrhs column-major device blocks, otherwise as solve_many: returns (list of Stats, form)"""
+        st = (Stats * max(int(nrhs), 1))()
+        form = C.c_int(0)
+        check(_lib.lib().cudamat_solver_solve_shifts(self.h, int(nrhs), _ptr(D), int(ldd), _ptr(B), int(ldb), _ptr(X), int(ldx),
+                                                     precond, loop, maxit, tol, flags, st, C.byref(form)))
         return [st[j] for j in range(int(nrhs))], form.value

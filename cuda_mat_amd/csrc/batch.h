@@ -27,7 +27,8 @@ struct BatchArgs {
 };
 
 // Y = alpha (A + diag d) X + beta Y on the solver's 0-based CSR arrays, L lanes per row (the row partition of the lanes-per-row
-// SpMV plan with that L).  dot: 0 none, 1 parts (y.w) per column, 2 (y.w, y.y); check: CHECK_HALF evaluates every column's
+// SpMV plan with that L).  dk (never set together with d): one shift per COLUMN, Y_j = alpha (A + diag dk_j) X_j + beta Y_j --
+// column j is then bit-identical to the same launch with d = that column's shift.  dot: 0 none, 1 parts (y.w) per column, 2 (y.w, y.y); check: CHECK_HALF evaluates every column's
 // half-step test from `half` (stride K) in the prologue.
 struct SpmmArgs {
     int n;
@@ -35,6 +36,7 @@ struct SpmmArgs {
     const double *val;
     const double *x;       // interleaved, indexed by column id
     const double *d;       // optional shift (local rows)
+    const double *dk;      // optional per-column shifts, interleaved like x: column j of row i at dk[i*K + j]
     const double *xd;      // x of the local rows (for d .* x)
     double alpha, beta;
     double *y;

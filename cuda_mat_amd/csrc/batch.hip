@@ -72,8 +72,11 @@ __device__ __forceinline__ void publish_b(const BatchArgs &la, int all_stopped)
 // ------------------------------------------------------------------------------------------------------------- SpMM
 // Long rows as in k_spmv (spmv_csr.hip), through the same helpers (device.h: LongRows): never summed by their group, swept by the
 // whole workgroup in increasing row order however many a partition holds.
+// S: per-column shifts (a.dk, interleaved) in place of the shared a.d -- the same term at the same place in both epilogues, so
+// column j is what the S = false kernel gives with d = column j of the shifts.  A template parameter: the S = false
+// instantiations compile to what they were before the shifts existed.
 
-template <int L, int K>
+template <int L, int K, bool S>
 __global__ __launch_bounds__(kBlock) void k_spmm_csr(SpmmArgs a, int rows_per_block)
 {
     __shared__ double lds[8 * K];
@@ -121,14 +124,16 @@ __global__ __launch_bounds__(kBlock) void k_spmm_csr(SpmmArgs a, int rows_per_bl
 #pragma unroll
         for (int j = 0; j < K; j++) sum[j] = group_sum<L>(sum[j]);
         if (lane == 0) {
-            double out[K], yo[K], xd[K], w[K];
+            double out[K], yo[K], xd[K], w[K], dk[K];
             if (a.beta != 0.0) load_row<K>(a.y, row, yo);
-            if (a.d) load_row<K>(a.xd, row, xd);
+            if (S || a.d) load_row<K>(a.xd, row, xd);
+            if (S) load_row<K>(a.dk, row, dk);
             if (a.dot) load_row<K>(a.w, row, w);
 #pragma unroll
             for (int j = 0; j < K; j++) {
                 double sj = sum[j];
-                if (a.d) sj += a.d[row] * xd[j];
+                if (S) sj += dk[j] * xd[j];
+                else if (a.d) sj += a.d[row] * xd[j];
                 double o = a.alpha * sj;
                 if (a.beta != 0.0) o += a.beta * yo[j];
                 out[j] = o;
@@ -157,14 +162,16 @@ __global__ __launch_bounds__(kBlock) void k_spmm_csr(SpmmArgs a, int rows_per_bl
             }
             block_sum<K>(part, lds);
             if (threadIdx.x == 0) {
-                double out[K], yo[K], xd[K], w[K];
+                double out[K], yo[K], xd[K], w[K], dk[K];
                 if (a.beta != 0.0) load_row<K>(a.y, row, yo);
-                if (a.d) load_row<K>(a.xd, row, xd);
+                if (S || a.d) load_row<K>(a.xd, row, xd);
+                if (S) load_row<K>(a.dk, row, dk);
                 if (a.dot) load_row<K>(a.w, row, w);
 #pragma unroll
                 for (int j = 0; j < K; j++) {
                     double sj = part[j];
-                    if (a.d) sj += a.d[row] * xd[j];
+                    if (S) sj += dk[j] * xd[j];
+                    else if (a.d) sj += a.d[row] * xd[j];
                     double o = a.alpha * sj;
                     if (a.beta != 0.0) o += a.beta * yo[j];
                     out[j] = o;
@@ -200,34 +207,44 @@ void spmm_partition(int L, int n, int *grid, int *rows_per_block)
     if (*grid < 1) *grid = 1;
 }
 
-template <int L>
+template <int L, bool S>
 static int launch_spmm_l(hipStream_t s, int K, const SpmmArgs &a, int grid, int rpb)
 {
     switch (K) {
-    case 1: hipLaunchKernelGGL((k_spmm_csr<L, 1>), dim3(grid), dim3(kBlock), 0, s, a, rpb); break;
-    case 2: hipLaunchKernelGGL((k_spmm_csr<L, 2>), dim3(grid), dim3(kBlock), 0, s, a, rpb); break;
-    case 4: hipLaunchKernelGGL((k_spmm_csr<L, 4>), dim3(grid), dim3(kBlock), 0, s, a, rpb); break;
-    case 8: hipLaunchKernelGGL((k_spmm_csr<L, 8>), dim3(grid), dim3(kBlock), 0, s, a, rpb); break;
+    case 1: hipLaunchKernelGGL((k_spmm_csr<L, 1, S>), dim3(grid), dim3(kBlock), 0, s, a, rpb); break;
+    case 2: hipLaunchKernelGGL((k_spmm_csr<L, 2, S>), dim3(grid), dim3(kBlock), 0, s, a, rpb); break;
+    case 4: hipLaunchKernelGGL((k_spmm_csr<L, 4, S>), dim3(grid), dim3(kBlock), 0, s, a, rpb); break;
+    case 8: hipLaunchKernelGGL((k_spmm_csr<L, 8, S>), dim3(grid), dim3(kBlock), 0, s, a, rpb); break;
     default: set_error("SpMM: %d columns per batch", K); return CUDAMAT_ERR_ARG;
     }
     CM_HIP(hipGetLastError());
     return CUDAMAT_OK;
 }
 
-int launch_spmm(hipStream_t s, int L, int K, const SpmmArgs &a)
+template <bool S>
+static int launch_spmm_s(hipStream_t s, int L, int K, const SpmmArgs &a, int grid, int rpb)
 {
-    int grid = 1, rpb = 1;
-    spmm_partition(L, a.n, &grid, &rpb);
     switch (L) {
-    case 2: return launch_spmm_l<2>(s, K, a, grid, rpb);
-    case 4: return launch_spmm_l<4>(s, K, a, grid, rpb);
-    case 8: return launch_spmm_l<8>(s, K, a, grid, rpb);
-    case 16: return launch_spmm_l<16>(s, K, a, grid, rpb);
-    case 32: return launch_spmm_l<32>(s, K, a, grid, rpb);
-    case 64: return launch_spmm_l<64>(s, K, a, grid, rpb);
+    case 2: return launch_spmm_l<2, S>(s, K, a, grid, rpb);
+    case 4: return launch_spmm_l<4, S>(s, K, a, grid, rpb);
+    case 8: return launch_spmm_l<8, S>(s, K, a, grid, rpb);
+    case 16: return launch_spmm_l<16, S>(s, K, a, grid, rpb);
+    case 32: return launch_spmm_l<32, S>(s, K, a, grid, rpb);
+    case 64: return launch_spmm_l<64, S>(s, K, a, grid, rpb);
     }
     set_error("SpMM: %d lanes per row", L);
     return CUDAMAT_ERR_ARG;
+}
+
+int launch_spmm(hipStream_t s, int L, int K, const SpmmArgs &a)
+{
+    if (a.dk && a.d) {
+        set_error("SpMM: a shared shift and per-column shifts together");
+        return CUDAMAT_ERR_ARG;
+    }
+    int grid = 1, rpb = 1;
+    spmm_partition(L, a.n, &grid, &rpb);
+    return a.dk ? launch_spmm_s<true>(s, L, K, a, grid, rpb) : launch_spmm_s<false>(s, L, K, a, grid, rpb);
 }
 
 #define CM_BATCH_DISPATCH(KERNEL, GRID, ...)                                                                  \

@@ -252,6 +252,8 @@ struct HostSystem {
     const int *iA, *jA;
     const double *d, *x0, *b;
     int nrhs = 1;         // columns of b and x0 (n each, contiguous): cudamat_solve_many
+    bool shifts = false;  // d holds nrhs columns (n each, contiguous), one shift vector per column: cudamat_solve_shifts
+    size_t d_count() const { return (size_t)n * (size_t)(shifts ? nrhs : 1); }
 };
 
 // ---- a call whose shape matches the cached solver's: upload into scratch arrays, compare on the device, reuse or rebuild
@@ -277,7 +279,7 @@ int build_or_reuse_candidate(cudamat_ctx *ctx, const Config &cfg, const HostSyst
             up.add(d_val, h.A, sizeof(double) * (size_t)nnz);
             up.add(d_b, h.b, sizeof(double) * (size_t)n * (size_t)h.nrhs);
             if (h.x0) up.add(d_x, h.x0, sizeof(double) * (size_t)n * (size_t)h.nrhs);
-            if (h.d) up.add(d_d, h.d, sizeof(double) * (size_t)n);
+            if (h.d) up.add(d_d, h.d, sizeof(double) * h.d_count());
             if ((rc = up.start(ctx->device))) break;
             if ((rc = up.finish())) break;
         }
@@ -395,7 +397,7 @@ int build_beside_upload(cudamat_ctx *ctx, const Config &cfg, const HostSystem &h
         }
         if (h.b) up.add(d_b, h.b, sizeof(double) * (size_t)n * (size_t)h.nrhs);
         if (h.x0) up.add(d_x, h.x0, sizeof(double) * (size_t)n * (size_t)h.nrhs);
-        if (h.d) up.add(d_d, h.d, sizeof(double) * (size_t)n);
+        if (h.d) up.add(d_d, h.d, sizeof(double) * h.d_count());
         const int m_all = up.mark();
         do {
             if ((rc = up.start(ctx->device))) break;
@@ -524,14 +526,15 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
     do {
         if ((rc = cudamat_malloc(ctx, sizeof(double) * (size_t)n * (size_t)h.nrhs, (void **)&d_b))) break;
         if ((rc = cudamat_malloc(ctx, sizeof(double) * (size_t)n * (size_t)h.nrhs, (void **)&d_x))) break;
-        if (h.d && (rc = cudamat_malloc(ctx, sizeof(double) * (size_t)n, (void **)&d_d))) break;
+        if (h.d && (rc = cudamat_malloc(ctx, sizeof(double) * h.d_count(), (void **)&d_d))) break;
         if (candidate) {
             if ((rc = build_or_reuse_candidate(ctx, cfg, h, d_b, d_x, d_d, &s, &reused, &t_up))) break;
         } else {
             if ((rc = build_beside_upload(ctx, cfg, h, d_b, d_x, d_d, &s, &t_up, speculative, precond, loop))) break;
         }
         if (g_cache.d_d && !reused) { cudamat_free(ctx, g_cache.d_d); g_cache.d_d = nullptr; }
-        if ((rc = cudamat_solver_set_shift(s, d_d))) break;
+        // (per-column shifts travel with the call: the solver itself keeps none, and the block goes when the call returns)
+        if ((rc = cudamat_solver_set_shift(s, h.shifts ? nullptr : d_d))) break;
         if (precond != CUDAMAT_PRECOND_NONE && !(reused && s->has_ilu && !s->ilu_block)) {
             if ((rc = cudamat_solver_ilu0(s))) break;
             built_ilu = true;
@@ -542,7 +545,8 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
         }
         int flags = (debug ? CUDAMAT_FLAG_DEBUG : 0) | (h.x0 ? 0 : CUDAMAT_FLAG_X0_ONES);
         if (many) {
-            if ((rc = cudamat_solver_solve_many(s, h.nrhs, d_b, n, d_x, n, precond, loop, maxit, tol, flags, out, form))) break;
+            if ((rc = cudamat_solver_solve_shifts(s, h.nrhs, h.shifts ? d_d : nullptr, n, d_b, n, d_x, n, precond, loop, maxit, tol,
+                                                  flags, out, form))) break;
             st = out[0];
         } else if ((rc = cudamat_solver_solve(s, d_b, d_x, precond, loop, maxit, tol, flags, &st))) {
             break;
@@ -564,8 +568,11 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
         g_cache.ctx = ctx;
         g_cache.s = s;
         g_cache.n = n; g_cache.nnz = nnz; g_cache.base = base;
-        g_cache.d_d = d_d;               // the solver points at it (set_shift); replaced by the next call
-        d_d = nullptr;
+        g_cache.d_d = nullptr;
+        if (!h.shifts) {
+            g_cache.d_d = d_d;           // the solver points at it (set_shift); replaced by the next call
+            d_d = nullptr;
+        }
     } else {
         if (s) cudamat_solver_destroy(s);
         if (old && old != s) cudamat_solver_destroy(old);
@@ -623,24 +630,30 @@ extern "C" int cudamat_solve(int n, int nnz, const double *A, const int *iA, con
     return rc;
 }
 
-extern "C" int cudamat_solve_many(int n, int nnz, const double *A, const int *iA, const int *jA, const double *d, int nrhs,
-                                  const double *B, int ldb, const double *x0, double *X, int ldx, int precond, int loop, int maxit,
-                                  double tol, cudamat_stats *out, int *form)
+// cudamat_solve_many (shifts = false: d one vector or NULL) and cudamat_solve_shifts (shifts = true: d a block, ldd >= n)
+static int solve_many_host(int n, int nnz, const double *A, const int *iA, const int *jA, const double *d, int ldd, bool shifts,
+                           int nrhs, const double *B, int ldb, const double *x0, double *X, int ldx, int precond, int loop,
+                           int maxit, double tol, cudamat_stats *out, int *form)
 {
     // every argument is checked before a device is touched
     if (form) *form = 0;
     CM_ARG(nrhs >= 0, "nrhs < 0");
-    CM_ARG(ldb >= n && ldx >= n, "leading dimension below n");
+    CM_ARG(ldb >= n && ldx >= n && (!shifts || ldd >= n), "leading dimension below n");
     if (nrhs == 0) return CUDAMAT_OK;
-    CM_ARG(B && X, "null pointer");
+    CM_ARG(B && X && (!shifts || d), "null pointer");
     CM_ARG(n > 0 && nnz >= 0 && A && iA && jA, "null pointer or empty system");
     CM_ARG(maxit >= 0, "maxit");
     const int base = iA[0];
     CM_ARG(base == 0 || base == 1, "iA[0] must be 0 or 1");
     CM_ARG(iA[n] - base == nnz, "nnz != iA[n] - iA[0]");
     // the device side wants n-long columns back to back
-    std::vector<double> b_packed, x0_packed, x_packed;
+    std::vector<double> b_packed, x0_packed, x_packed, d_packed;
     const double *b = B, *x0p = x0;
+    if (shifts && ldd != n) {
+        d_packed.resize((size_t)n * (size_t)nrhs);
+        for (int j = 0; j < nrhs; j++) memcpy(&d_packed[(size_t)j * n], d + (size_t)j * ldd, sizeof(double) * (size_t)n);
+        d = d_packed.data();
+    }
     if (ldb != n) {
         b_packed.resize((size_t)n * (size_t)nrhs);
         for (int j = 0; j < nrhs; j++) memcpy(&b_packed[(size_t)j * n], B + (size_t)j * ldb, sizeof(double) * (size_t)n);
@@ -661,6 +674,7 @@ extern "C" int cudamat_solve_many(int n, int nnz, const double *A, const int *iA
     cfg.pb_place = cfg.pb_place >= 2 ? 1 : 0;                    // (as cudamat_solve)
     HostSystem h{n, nnz, base, (int64_t)n, A, iA, jA, d, x0p, b};
     h.nrhs = nrhs;
+    h.shifts = shifts;
     std::lock_guard<std::mutex> cache_lock(g_cache.mu);
     int rc = solve_host_locked(cfg, h, true, precond, loop, maxit, tol, 0, x, st.data(), true, form);
     if (rc == CUDAMAT_ERR_NOMEM) {
@@ -673,6 +687,21 @@ extern "C" int cudamat_solve_many(int n, int nnz, const double *A, const int *iA
         for (int j = 0; j < nrhs; j++) memcpy(X + (size_t)j * ldx, x + (size_t)j * n, sizeof(double) * (size_t)n);
     if (out) memcpy(out, st.data(), sizeof(cudamat_stats) * (size_t)nrhs);
     return CUDAMAT_OK;
+}
+
+extern "C" int cudamat_solve_many(int n, int nnz, const double *A, const int *iA, const int *jA, const double *d, int nrhs,
+                                  const double *B, int ldb, const double *x0, double *X, int ldx, int precond, int loop, int maxit,
+                                  double tol, cudamat_stats *out, int *form)
+{
+    return solve_many_host(n, nnz, A, iA, jA, d, 0, false, nrhs, B, ldb, x0, X, ldx, precond, loop, maxit, tol, out, form);
+}
+
+extern "C" int cudamat_solve_shifts(int n, int nnz, const double *A0, const int *iA0, const int *jA0, int nrhs, const double *D,
+                                    int ldd, const double *B, int ldb, const double *x0, double *X, int ldx, int loop, int maxit,
+                                    double tol, cudamat_stats *out, int *form)
+{
+    return solve_many_host(n, nnz, A0, iA0, jA0, D, ldd, true, nrhs, B, ldb, x0, X, ldx, CUDAMAT_PRECOND_NONE, loop, maxit, tol, out,
+                           form);
 }
 
 // cudamat_solver_create from HOST arrays: the same staged creation, run beside the upload (what cudamat_solve does for its

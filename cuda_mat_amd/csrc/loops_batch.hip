@@ -1,5 +1,6 @@
 // loops_batch.hip -- several right-hand sides for one resident matrix: cudamat_solver_spmm, cudamat_solver_precond_apply_many,
-// cudamat_solver_solve_many, cudamat_solver_history_col.
+// cudamat_solver_solve_many, cudamat_solver_history_col; and their forms with one shift vector per column,
+// (A0 + I d_j) x_j = b_j: cudamat_solver_spmm_shifts, cudamat_solver_solve_shifts.
 //
 // Each column is an INDEPENDENT run of the reference loop (pbicgstab.cu:45-154; :581-754 for the (A0 + I d) variant) with its
 // own rho, alpha, omega, stopping tests, breakdown guard and history; nothing of one column enters another (this is not
@@ -22,6 +23,10 @@
 // three-launch loops of small systems), and runs batched only when that is faster than kc single solves.  Everything the batched
 // form does not cover (ILU(0) unless MANY_PRECOND asks for it, and then hybrid factors in level-major spaces; block-Jacobi ILU(0),
 // the pipelined loop, sharded solvers, the DEBUG / PROFILE flags) and a failed allocation of its buffers run column by column: cudamat_solver_solve once per column, bit for bit what a caller's loop would do.
+// Per-column shifts (D != NULL): the batched form transposes D into one more interleaved block (many.dk, padding columns 0) and
+// every SpMM of the loop -- r0 = b - (A0 + I d_j) x0_j included -- adds dk_j .* x_j where it would add d .* x_j; the solver's own
+// shift is not read.  Column by column, the solver's shift points at column j of D for the length of that column's solve (a
+// caller's set_shift + solve, bit for bit) and is put back when the call returns, whatever it returns.
 #include <math.h>
 #include <string.h>
 
@@ -42,20 +47,25 @@ int64_t many_rows(const cudamat_solver *s)
     return rows > 0 ? rows : 1;
 }
 
-// The interleaved buffers come in two groups, each a list of (pointer, bytes for K columns, zeroed at allocation?): the plain
-// loop's -- seven vectors (r, rw, p, v, t, b, x), the partial sums, the K loop states -- and the three further blocks of the
-// preconditioned loop: ph = M^-1 p, sh = M^-1 r and the scratch of L^-1.
+// The interleaved buffers come in three groups, each a list of (pointer, bytes for K columns, zeroed at allocation?): the plain
+// loop's -- seven vectors (r, rw, p, v, t, b, x), the partial sums, the K loop states --, the three further blocks of the
+// preconditioned loop: ph = M^-1 p, sh = M^-1 r and the scratch of L^-1; and the per-column shifts' one block.
+enum Group { G_PLAIN = 0, G_PRECOND = 1, G_SHIFTS = 2 };
+
+int &group_cap(cudamat_solver *s, Group g) { return g == G_PRECOND ? s->many.pcap : g == G_SHIFTS ? s->many.dcap : s->many.cap; }
+
 struct Buf {
     void **p;
     size_t bytes;
     bool zero;
 };
 
-std::vector<Buf> many_group(cudamat_solver *s, bool precond, int K)
+std::vector<Buf> many_group(cudamat_solver *s, Group g, int K)
 {
     ManyWork &m = s->many;
     const size_t nb = sizeof(double) * (size_t)K * (size_t)many_rows(s);
-    if (precond) return {{(void **)&m.pw, nb, true}, {(void **)&m.s, nb, true}, {(void **)&m.lt, nb, true}};
+    if (g == G_SHIFTS) return {{(void **)&m.dk, nb, true}};
+    if (g == G_PRECOND) return {{(void **)&m.pw, nb, true}, {(void **)&m.s, nb, true}, {(void **)&m.lt, nb, true}};
     const size_t pv = sizeof(double) * 2 * (size_t)K * kVecGridMax, ps = sizeof(double) * 2 * (size_t)K * kSpmvGridMax;
     return {{(void **)&m.r, nb, true}, {(void **)&m.rw, nb, true}, {(void **)&m.p, nb, true}, {(void **)&m.v, nb, true},
             {(void **)&m.t, nb, true}, {(void **)&m.b, nb, true}, {(void **)&m.x, nb, true},
@@ -63,13 +73,13 @@ std::vector<Buf> many_group(cudamat_solver *s, bool precond, int K)
             {(void **)&m.parts_tt, ps, false}, {(void **)&m.st, sizeof(LoopState) * (size_t)K, false}};
 }
 
-void free_group(cudamat_solver *s, bool precond)
+void free_group(cudamat_solver *s, Group g)
 {
-    for (const Buf &b : many_group(s, precond, 0)) {
+    for (const Buf &b : many_group(s, g, 0)) {
         if (*b.p) CM_DROP(hipFree(*b.p));
         *b.p = nullptr;
     }
-    (precond ? s->many.pcap : s->many.cap) = 0;
+    group_cap(s, g) = 0;
 }
 
 }  // namespace
@@ -79,8 +89,9 @@ namespace cm {
 void many_release(cudamat_solver *s)
 {
     ManyWork &m = s->many;
-    free_group(s, false);
-    free_group(s, true);
+    free_group(s, G_PLAIN);
+    free_group(s, G_PRECOND);
+    free_group(s, G_SHIFTS);
     if (m.hist) CM_DROP(hipFree(m.hist));
     m.hist = nullptr;
     m.hist_bytes = 0;
@@ -91,37 +102,38 @@ void many_release(cudamat_solver *s)
 namespace {
 
 // One group holds K columns: allocated (and zeroed) as a whole, or -- CUDAMAT_ERR_NOMEM -- not at all.  A wider plain group
-// replaces everything (the preconditioned group and the histories go with it); a failed preconditioned group leaves the plain
+// replaces everything (the other groups and the histories go with it); a failed preconditioned or shift group leaves the plain
 // one in place.  The stream is drained before anything is freed.
-int ensure_many(cudamat_solver *s, bool precond, int K)
+int ensure_many(cudamat_solver *s, Group g, int K)
 {
-    if ((precond ? s->many.pcap : s->many.cap) >= K) return CUDAMAT_OK;
+    if (group_cap(s, g) >= K) return CUDAMAT_OK;
     hipStream_t st = s->ctx->stream;
     CM_HIP(hipStreamSynchronize(st));
-    if (precond) free_group(s, true);
+    if (g != G_PLAIN) free_group(s, g);
     else many_release(s);
     int rc = CUDAMAT_OK;
-    for (const Buf &b : many_group(s, precond, K)) {
+    for (const Buf &b : many_group(s, g, K)) {
         if ((rc = dev_alloc(b.p, b.bytes))) break;
         if (b.zero && (rc = CM_RC(hipMemsetAsync(*b.p, 0, b.bytes, st)))) break;
     }
     if (rc) {
         CM_DROP(hipStreamSynchronize(st));
-        free_group(s, precond);
+        free_group(s, g);
         return rc;
     }
-    (precond ? s->many.pcap : s->many.cap) = K;
+    group_cap(s, g) = K;
     return CUDAMAT_OK;
 }
 
-// Is there room for the batched form of a call with nrhs columns (the plain group, with `precond` the other one too, for its
-// widest block)?  Buffers that do not fit are not an error of the call -- *room = false, it runs column by column --; any other
+// Is there room for the batched form of a call with nrhs columns (the plain group, with `precond` / `shifts` their groups too,
+// for its widest block)?  Buffers that do not fit are not an error of the call -- *room = false, it runs column by column --; any other
 // failure is.
-int many_room(cudamat_solver *s, int nrhs, bool precond, bool *room)
+int many_room(cudamat_solver *s, int nrhs, bool precond, bool shifts, bool *room)
 {
     const int K = pow2_cols(nrhs < kBatchMax ? nrhs : kBatchMax);
-    int rc = ensure_many(s, false, K);
-    if (rc == CUDAMAT_OK && precond) rc = ensure_many(s, true, K);
+    int rc = ensure_many(s, G_PLAIN, K);
+    if (rc == CUDAMAT_OK && precond) rc = ensure_many(s, G_PRECOND, K);
+    if (rc == CUDAMAT_OK && shifts) rc = ensure_many(s, G_SHIFTS, K);
     *room = rc == CUDAMAT_OK;
     return rc == CUDAMAT_ERR_NOMEM ? CUDAMAT_OK : rc;
 }
@@ -141,24 +153,37 @@ std::vector<ColBlock> col_blocks(int nrhs)
     return blocks;
 }
 
-SpmmArgs spmm_args(const cudamat_solver *s, const double *x, double *y)
+// dk: the interleaved per-column shifts of this batch, which then stand in for the solver's own shift
+SpmmArgs spmm_args(const cudamat_solver *s, const double *x, double *y, const double *dk = nullptr)
 {
     SpmmArgs a{};
     a.n = s->n; a.rp = s->rp; a.ci = s->ci; a.val = s->val;
-    a.x = x; a.d = s->d; a.xd = x;
+    a.x = x; a.d = dk ? nullptr : s->d; a.dk = dk; a.xd = x;
     a.alpha = 1.0; a.beta = 0.0; a.y = y;
     a.dot = 0; a.w = nullptr; a.parts = nullptr;
     a.check = CHECK_NONE; a.half = nullptr; a.half_count = 0;
     return a;
 }
 
+// the solver's own shift, put back when the scope ends: a call with per-column shifts leaves s->d as it found it on every path
+struct ShiftGuard {
+    cudamat_solver *s;
+    const double *saved;
+    explicit ShiftGuard(cudamat_solver *sv) : s(sv), saved(sv->d) {}
+    ~ShiftGuard() { s->d = saved; }
+    ShiftGuard(const ShiftGuard &) = delete;
+    ShiftGuard &operator=(const ShiftGuard &) = delete;
+};
+
 // One batch of kc <= K columns (K a power of two, the rest padding that starts stopped).  B / X column-major with leading
 // dimensions ldb / ldx; B == NULL: many.b and many.x are already filled (the timing of the form choice), X == NULL: the iterate
 // stays in many.x.  fin receives the K final states; hist_out (kc vectors, or NULL) the columns' residual histories.
 // precond: CUDAMAT_PRECOND_NONE, or CUDAMAT_PRECOND_ILU0 with covered factors (trsm_covered), the reference loop and
-// the preconditioned group allocated (many_room).
+// the preconditioned group allocated (many_room).  shifts: column j is (A0 + I d_j) x_j = b_j with the shifts of many.dk, filled
+// here from D (column-major, ldd) unless D == NULL (filled already); the shift group allocated (many_room).
 int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, double *X, int64_t ldx, int precond, int loop,
-              int maxit, double tol, int flags, LoopState *fin, std::vector<double> *hist_out, double *t_loop)
+              int maxit, double tol, int flags, LoopState *fin, std::vector<double> *hist_out, double *t_loop,
+              bool shifts = false, const double *D = nullptr, int64_t ldd = 0)
 {
     ManyWork &m = s->many;
     const bool pc = precond != CUDAMAT_PRECOND_NONE;
@@ -185,8 +210,10 @@ int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, do
         if (flags & CUDAMAT_FLAG_X0_ONES) CM_TRY(launch_fill(st, (int64_t)K * n, 1.0, m.x));
         else CM_TRY(launch_batch_in(st, K, kc, n, n, X, ldx, 0.0, m.x));
     }
+    if (D) CM_TRY(launch_batch_in(st, K, kc, n, n, D, ldd, 0.0, m.dk));       // (padding columns: shift 0)
+    const double *dk = shifts ? m.dk : nullptr;
     // r = A x0; r = b - r, rw = r, p = r; the states                                        pbicgstab.cu:67-74 / :645-659
-    CM_TRY(launch_spmm(st, L, K, spmm_args(s, m.x, m.r)));
+    CM_TRY(launch_spmm(st, L, K, spmm_args(s, m.x, m.r, dk)));
     int np_full = 0, np_half = 0, np_spmm = 0, rpb = 0;
     spmm_partition(L, n, &np_spmm, &rpb);
     CM_TRY(launch_init_b(st, K, n, m.b, m.r, m.rw, m.p, m.parts_full, &np_full));
@@ -206,7 +233,7 @@ int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, do
             pw = m.pw;
         }
         // v = A pw, rw.v                                                                      :104-106
-        SpmmArgs a1 = spmm_args(s, pw, m.v);
+        SpmmArgs a1 = spmm_args(s, pw, m.v, dk);
         a1.dot = 1; a1.w = m.rw; a1.parts = m.parts_rv; a1.loop = la;
         CM_TRY(launch_spmm(st, L, K, a1));
         // alpha, r -= alpha v, ||r||                                                          :107-111
@@ -218,7 +245,7 @@ int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, do
             CM_TRY(precond_apply_b(s, K, m.r, m.lt, m.s));
             sv = m.s;
         }
-        SpmmArgs a2 = spmm_args(s, sv, m.t);
+        SpmmArgs a2 = spmm_args(s, sv, m.t, dk);
         a2.dot = 2; a2.w = m.r; a2.parts = m.parts_tt; a2.loop = la;
         if (!pc) { a2.check = CHECK_HALF; a2.half = m.parts_half; a2.half_count = np_half; }
         CM_TRY(launch_spmm(st, L, K, a2));
@@ -246,17 +273,19 @@ int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, do
 }
 
 // MANY_FORM / MANY_PRECOND = auto: is the batched loop with K columns faster than kc single solves?  Timed once per solver,
-// loop, preconditioner and K (FLAG_NO_EXIT iterations on scratch right-hand sides: b = 1, x0 = 0); what the timing takes is
-// added to *t_tune.
-int prefer_batched(cudamat_solver *s, int K, int kc, int precond, int loop, bool *batched, double *t_tune)
+// loop, preconditioner, with or without per-column shifts, and K (FLAG_NO_EXIT iterations on scratch right-hand sides: b = 1,
+// x0 = 0); what the timing takes is added to *t_tune.  shifts: both sides run with a shift in place (scratch values in many.dk,
+// all 0: the single solve reads its first n as the solver's shift, the batched loop the block) -- the caller fills many.dk after.
+int prefer_batched(cudamat_solver *s, int K, int kc, int precond, int loop, bool shifts, bool *batched, double *t_tune)
 {
     ManyWork &m = s->many;
     const double t0 = now_s();
     hipStream_t st = s->ctx->stream;
     const int n = s->n;
-    if (m.tune_loop != loop || m.tune_precond != precond) {
+    if (m.tune_loop != loop || m.tune_precond != precond || m.tune_shifts != (shifts ? 1 : 0)) {
         m.tune_loop = loop;
         m.tune_precond = precond;
+        m.tune_shifts = shifts ? 1 : 0;
         m.t_single = -1.0;
         for (double &t : m.t_batch) t = -1.0;
         // a few iterations: enough that launch and set-up overheads do not decide (small systems run ~10 us per iteration)
@@ -264,9 +293,12 @@ int prefer_batched(cudamat_solver *s, int K, int kc, int precond, int loop, bool
         m.tune_iters = it < 4.0 ? 4 : it > 64.0 ? 64 : (int)it;
     }
     const int N = m.tune_iters;
+    ShiftGuard own(s);
+    if (shifts && (m.t_single < 0.0 || m.t_batch[log2_cols(K)] < 0.0)) CM_TRY(launch_fill(st, (int64_t)K * n, 0.0, m.dk));
     if (m.t_single < 0.0) {
         CM_TRY(ensure_work(s));
         CM_TRY(ensure_spmv_mode(s));
+        if (shifts) s->d = m.dk;
         for (int rep = 0; rep < 2; rep++) {       // (the first run warms up: the loop forms allocate on first use)
             CM_TRY(launch_fill(st, n, 1.0, m.b));
             CM_TRY(launch_fill(st, n, 0.0, m.x));
@@ -277,6 +309,7 @@ int prefer_batched(cudamat_solver *s, int K, int kc, int precond, int loop, bool
             CM_HIP(hipStreamSynchronize(st));
             m.t_single = now_s() - t;
         }
+        s->d = own.saved;
     }
     double &tb = m.t_batch[log2_cols(K)];
     if (tb < 0.0) {
@@ -287,15 +320,15 @@ int prefer_batched(cudamat_solver *s, int K, int kc, int precond, int loop, bool
             CM_HIP(hipStreamSynchronize(st));
             const double t = now_s();
             CM_TRY(run_group(s, K, K, nullptr, 0, nullptr, 0, precond, loop, rep ? N : 2, 1e-8, CUDAMAT_FLAG_NO_EXIT, fin,
-                             nullptr, nullptr));
+                             nullptr, nullptr, shifts));
             tb = now_s() - t;
         }
     }
     // batched only when clearly faster (3 %: below that the two are within the noise of one timing)
     *batched = tb < 0.97 * (double)kc * m.t_single;
     if (s->ctx->cfg.verbose)
-        fprintf(stderr, "[cudamat] several right-hand sides%s: %d iterations, single loop %.3f ms x %d columns, batched (K = %d) "
-                        "%.3f ms -> %s\n", precond ? " with ILU(0)" : "", N, 1e3 * m.t_single, kc, K, 1e3 * tb,
+        fprintf(stderr, "[cudamat] several right-hand sides%s%s: %d iterations, single loop %.3f ms x %d columns, batched (K = %d) "
+                        "%.3f ms -> %s\n", precond ? " with ILU(0)" : "", shifts ? " with per-column shifts" : "", N, 1e3 * m.t_single, kc, K, 1e3 * tb,
                 *batched ? "batched" : "columns");
     *t_tune += now_s() - t0;
     return CUDAMAT_OK;
@@ -315,28 +348,40 @@ void fill_stats(cudamat_solver *s, const LoopState &f, int precond, cudamat_stat
 
 }  // namespace
 
-extern "C" int cudamat_solver_spmm(cudamat_solver *s, int nrhs, const double *X, int ldx, double *Y, int ldy)
+extern "C" int cudamat_solver_spmm_shifts(cudamat_solver *s, int nrhs, const double *X, int ldx, const double *D, int ldd,
+                                          double *Y, int ldy)
 {
     CM_ARG(s, "solver is NULL");
     CM_ARG(nrhs >= 0, "nrhs < 0");
     if (nrhs == 0) return CUDAMAT_OK;
     CM_ARG(X && Y, "null pointer");
     CM_ARG((int64_t)ldx >= (s->sharded ? (int64_t)s->n : s->n_cols) && ldy >= s->n, "leading dimension below the rows");
+    CM_ARG(!D || ldd >= s->n, "leading dimension below the rows");
     CM_HIP(hipSetDevice(s->ctx->device));
     bool batched = !s->sharded;
-    if (batched) CM_TRY(many_room(s, nrhs, false, &batched));
+    if (batched) CM_TRY(many_room(s, nrhs, false, D != nullptr, &batched));
     if (!batched) {                      // sharded, or no room for the interleaved buffers: one SpMV per column
-        for (int j = 0; j < nrhs; j++) CM_TRY(cudamat_solver_spmv(s, X + (size_t)j * ldx, Y + (size_t)j * ldy));
+        ShiftGuard own(s);
+        for (int j = 0; j < nrhs; j++) {
+            if (D) s->d = D + (size_t)j * ldd;
+            CM_TRY(cudamat_solver_spmv(s, X + (size_t)j * ldx, Y + (size_t)j * ldy));
+        }
         return CUDAMAT_OK;
     }
     ManyWork &m = s->many;
     hipStream_t st = s->ctx->stream;
     for (const ColBlock &c : col_blocks(nrhs)) {
         CM_TRY(launch_batch_in(st, c.K, c.kc, s->n_cols, many_rows(s), X + (size_t)c.c0 * ldx, ldx, 0.0, m.x));
-        CM_TRY(launch_spmm(st, s->plan.lanes, c.K, spmm_args(s, m.x, m.t)));
+        if (D) CM_TRY(launch_batch_in(st, c.K, c.kc, s->n, s->n, D + (size_t)c.c0 * ldd, ldd, 0.0, m.dk));
+        CM_TRY(launch_spmm(st, s->plan.lanes, c.K, spmm_args(s, m.x, m.t, D ? m.dk : nullptr)));
         CM_TRY(launch_batch_out(st, c.K, c.kc, s->n, m.t, Y + (size_t)c.c0 * ldy, ldy));
     }
     return CUDAMAT_OK;
+}
+
+extern "C" int cudamat_solver_spmm(cudamat_solver *s, int nrhs, const double *X, int ldx, double *Y, int ldy)
+{
+    return cudamat_solver_spmm_shifts(s, nrhs, X, ldx, nullptr, 0, Y, ldy);
 }
 
 extern "C" int cudamat_solver_precond_apply_many(cudamat_solver *s, int nrhs, const double *In, int ldin, double *Out, int ldout)
@@ -349,7 +394,7 @@ extern "C" int cudamat_solver_precond_apply_many(cudamat_solver *s, int nrhs, co
     CM_ARG(s->has_ilu, "call cudamat_solver_ilu0 / cudamat_solver_block_ilu0 first");
     CM_HIP(hipSetDevice(s->ctx->device));
     bool batched = trsm_covered(s);
-    if (batched) CM_TRY(many_room(s, nrhs, false, &batched));
+    if (batched) CM_TRY(many_room(s, nrhs, false, false, &batched));
     if (!batched) {                      // factors the multi-column kernels do not cover, or no room: one application per column
         CM_TRY(ensure_work(s));
         for (int j = 0; j < nrhs; j++) CM_TRY(precond_apply(s, In + (size_t)j * ldin, s->t, Out + (size_t)j * ldout));
@@ -365,15 +410,17 @@ extern "C" int cudamat_solver_precond_apply_many(cudamat_solver *s, int nrhs, co
     return CUDAMAT_OK;
 }
 
-extern "C" int cudamat_solver_solve_many(cudamat_solver *s, int nrhs, const double *B, int ldb, double *X, int ldx, int precond,
-                                         int loop, int maxit, double tol, int flags, cudamat_stats *st, int *form)
+extern "C" int cudamat_solver_solve_shifts(cudamat_solver *s, int nrhs, const double *D, int ldd, const double *B, int ldb,
+                                           double *X, int ldx, int precond, int loop, int maxit, double tol, int flags,
+                                           cudamat_stats *st, int *form)
 {
     CM_ARG(s, "solver is NULL");
     CM_ARG(nrhs >= 0, "nrhs < 0");
     if (form) *form = 0;
     if (nrhs == 0) return CUDAMAT_OK;
     CM_ARG(B && X, "null pointer");
-    CM_ARG(ldb >= s->n && ldx >= s->n, "leading dimension below the rows");
+    CM_ARG(ldb >= s->n && ldx >= s->n && (!D || ldd >= s->n), "leading dimension below the rows");
+    CM_ARG(!(D && precond), "the (A0 + I d) variant has no preconditioner (pbicgstab.h:110)");
     CM_ARG(maxit >= 0, "maxit");
     CM_ARG(loop == CUDAMAT_LOOP_PBICGSTAB || loop == CUDAMAT_LOOP_PBICGSTAB2 || loop == CUDAMAT_LOOP_PIPELINED, "loop");
     CM_HIP(hipSetDevice(s->ctx->device));
@@ -398,21 +445,22 @@ extern "C" int cudamat_solver_solve_many(cudamat_solver *s, int nrhs, const doub
     const bool batchable = plain || pc;
     bool room = false;
     if (batchable && cfg.many_form != 2) {
-        CM_TRY(many_room(s, nrhs, pc, &room));
+        CM_TRY(many_room(s, nrhs, pc, D != nullptr, &room));
         if (!room && cfg.verbose) fprintf(stderr, "[cudamat] no room for the batched loop's buffers: column by column\n");
     }
     const int pc_precond = pc ? CUDAMAT_PRECOND_ILU0 : CUDAMAT_PRECOND_NONE;
     const bool force_batched = pc ? cfg.many_precond == 2 : cfg.many_form == 1;
     const bool by_timing = pc ? cfg.many_precond == 1 : cfg.many_form == 0;
+    ShiftGuard own(s);                   // (column by column, the solver's shift is column j of D while column j is solved)
     for (const ColBlock &c : col_blocks(nrhs)) {
         const int c0 = c.c0, kc = c.kc, K = c.K;
         bool batched = room && force_batched;
-        if (room && by_timing) CM_TRY(prefer_batched(s, K, kc, pc_precond, loop, &batched, &t_tune));
+        if (room && by_timing) CM_TRY(prefer_batched(s, K, kc, pc_precond, loop, D != nullptr, &batched, &t_tune));
         if (batched) {
             LoopState fin[kBatchMax];
             double tl = 0.0;
             CM_TRY(run_group(s, K, kc, B + (size_t)c0 * ldb, ldb, X + (size_t)c0 * ldx, ldx, pc_precond, loop, maxit, tol, flags,
-                             fin, hists.data() + c0, &tl));
+                             fin, hists.data() + c0, &tl, D != nullptr, D ? D + (size_t)c0 * ldd : nullptr, ldd));
             t_solve += tl;
             for (int j = 0; j < kc; j++) fill_stats(s, fin[j], pc_precond, &out[(size_t)(c0 + j)]);
             any_batched = true;
@@ -420,6 +468,7 @@ extern "C" int cudamat_solver_solve_many(cudamat_solver *s, int nrhs, const doub
         }
         for (int j = c0; j < c0 + kc; j++) {           // column by column: today's single solve
             cudamat_stats &sj = out[(size_t)j];
+            if (D) s->d = D + (size_t)j * ldd;
             CM_TRY(cudamat_solver_solve(s, B + (size_t)j * ldb, X + (size_t)j * ldx, precond, loop, maxit, tol, flags, &sj));
             t_solve += sj.t_solve;
             int cnt = 0;
@@ -438,6 +487,12 @@ extern "C" int cudamat_solver_solve_many(cudamat_solver *s, int nrhs, const doub
     if (st) memcpy(st, out.data(), sizeof(cudamat_stats) * (size_t)nrhs);
     if (form) *form = any_batched ? 1 : 0;
     return CUDAMAT_OK;
+}
+
+extern "C" int cudamat_solver_solve_many(cudamat_solver *s, int nrhs, const double *B, int ldb, double *X, int ldx, int precond,
+                                         int loop, int maxit, double tol, int flags, cudamat_stats *st, int *form)
+{
+    return cudamat_solver_solve_shifts(s, nrhs, nullptr, 0, B, ldb, X, ldx, precond, loop, maxit, tol, flags, st, form);
 }
 
 extern "C" int cudamat_solver_history_col(cudamat_solver *s, int col, double *hist_host, int cap, int *count)

@@ -31,7 +31,7 @@ struct TriFactor {                 // one triangular factor in level-major stora
 };
 
 // several right-hand sides (loops_batch.hip): the work of the batched loop, allocated at the first batched solve or SpMM and
-// released with the solver.  Two groups of interleaved buffers, each allocated and released as a whole.
+// released with the solver.  Three groups of interleaved buffers, each allocated and released as a whole.
 struct ManyWork {
     // the plain loop: seven vectors of `cap` columns, the partial sums, `cap` loop states (device)
     int cap = 0;                // columns the group holds (0: not allocated)
@@ -41,12 +41,15 @@ struct ManyWork {
     // the preconditioned loop: M^-1 p, M^-1 r and the scratch of L^-1 (`pcap` columns; allocated at its first use)
     int pcap = 0;
     double *pw = nullptr, *s = nullptr, *lt = nullptr;
+    // per-column shifts (cudamat_solver_spmm_shifts / _solve_shifts): one block of `dcap` columns, allocated at its first use
+    int dcap = 0;
+    double *dk = nullptr;
     double *hist = nullptr;     // device: per column a history of the batch's length (hist_bytes in all)
     size_t hist_bytes = 0;
     std::vector<std::vector<double>> hist_host;   // per column: the residual history of the last cudamat_solver_solve_many
     // form choice (MANY_FORM / MANY_PRECOND = auto): seconds of tune_iters iterations, single loop (< 0: not timed) and batched by log2 K
     double t_single = -1.0, t_batch[4] = {-1.0, -1.0, -1.0, -1.0};
-    int tune_loop = -1, tune_precond = -1, tune_iters = 0;
+    int tune_loop = -1, tune_precond = -1, tune_shifts = -1, tune_iters = 0;
 };
 
 }  // namespace cm

@@ -352,7 +352,21 @@ int cudamat_solver_precond_apply_many(cudamat_solver *s, int nrhs, const double 
 /* name(s) of the HIP kernel(s) that call launches per factor for a batch of nrhs (<= 8) columns, e.g.
  * "L: k_trsm_lds<8, 8>; U: k_trsm_level<16, 8> + k_trsm_small_levels<16, 8>"; "" when the factors run column by column   */
 int cudamat_solver_trsm_kernel(cudamat_solver *s, int nrhs, char *name, int cap);
-/* residual history of column `col` of the last cudamat_solver_solve_many, laid out as cudamat_solver_history's       */
+/* One shift vector per column: column j is (A0 + diag(D_j)) with D a column-major device block (ldd >= n_local, D_j its column
+ * j), the matrix shared.  For the length of the call D REPLACES the solver's own shift (cudamat_solver_set_shift), which is
+ * what it was when the call returns, on every error path too.  D == NULL: exactly cudamat_solver_spmm / _solve_many.
+ * cudamat_solver_spmm_shifts: Y_j = (A0 + diag(D_j)) X_j; up to 8 columns share one pass over the matrix, and column j is
+ * bit-identical to cudamat_solver_spmm (so to the lanes-per-row cudamat_solver_spmv) of column j after set_shift(D_j).
+ * cudamat_solver_solve_shifts: (A0 + diag(D_j)) x_j = b_j, everything else as cudamat_solver_solve_many (statistics, histories,
+ * *form, MANY_FORM -- auto times both forms with shifts in place, once per solver, loop and batch width).  The batched form
+ * covers what it covers there; the rest (MANY_FORM = columns, LOOP_PIPELINED, sharded solvers -- D then holds the local rows --,
+ * FLAG_DEBUG / FLAG_PROFILE, no room for the buffers) runs set_shift(D_j) + cudamat_solver_solve per column, bit for bit.  The
+ * (A0 + I d) variant has no preconditioner (pbicgstab.h:110): precond != CUDAMAT_PRECOND_NONE with D is CUDAMAT_ERR_ARG.      */
+int cudamat_solver_spmm_shifts(cudamat_solver *s, int nrhs, const double *X, int ldx, const double *D, int ldd, double *Y,
+                               int ldy);
+int cudamat_solver_solve_shifts(cudamat_solver *s, int nrhs, const double *D, int ldd, const double *B, int ldb, double *X,
+                                int ldx, int precond, int loop, int maxit, double tol, int flags, cudamat_stats *st, int *form);
+/* residual history of column `col` of the last cudamat_solver_solve_many / _solve_shifts, laid out as cudamat_solver_history's */
 int cudamat_solver_history_col(cudamat_solver *s, int col, double *hist_host, int cap, int *count);
 
 /* ---- drop-in host-pointer solve ---------------------------------------------------- */
@@ -372,6 +386,13 @@ int cudamat_solve(int n, int nnz, const double *A, const int *iA, const int *jA,
 int cudamat_solve_many(int n, int nnz, const double *A, const int *iA, const int *jA, const double *d, int nrhs,
                        const double *B, int ldb, const double *x0, double *X, int ldx, int precond, int loop, int maxit,
                        double tol, cudamat_stats *st, int *form);
+
+/* cudamat_solve_many for a family of shifted systems (A0 + diag(D_j)) x_j = b_j: D (ldd >= n) column-major in HOST memory like
+ * B, one shift vector per column, uploaded beside B; no preconditioner (pbicgstab.h:110).  The plan cache compares the matrix,
+ * not the shifts: a second call with the same A0 and other shifts reuses the plan (st[j].plan_reused = 1).                 */
+int cudamat_solve_shifts(int n, int nnz, const double *A0, const int *iA0, const int *jA0, int nrhs, const double *D, int ldd,
+                         const double *B, int ldb, const double *x0, double *X, int ldx, int loop, int maxit, double tol,
+                         cudamat_stats *st, int *form);
 
 /* cudamat_solve keeps the solver of its LAST call (CSR copies, SpMV plan, ILU(0) factors: device memory on device 0 --
  * about 16 GB at 1e7 rows x 50 entries, 50 GB with ILU(0)) so that a caller who solves with the same matrix again --

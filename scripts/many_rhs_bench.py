@@ -10,6 +10,12 @@ csrc/trsm.hip) against K sequential Solver.solve calls with ILU(0), on mat10000,
 2e5 x 50 system (TRSV_HYBRID = 0 throughout: hybrid factors are not covered by the batched form), and what MANY_PRECOND = auto
 picks.  --sequential-only measures just the K sequential solves and uses nothing newer than Solver.solve, so the same file
 can be run against an older build of the library to take the sequential figure there.
+
+--shifts: one shift vector per column, (A0 + I d_j) x_j = b_j (Solver.solve_shifts, MANY_FORM = batched) against (a) K
+sequential set_shift + Solver.solve calls and (b) the shared-d batched loop (set_shift + Solver.solve_many) at the same K --
+(a) and (b) use nothing newer than solve_many --, what MANY_FORM = auto picks with shifts, and the SpMM with per-column shifts
+(bytes = 12 nnz + 4 (n + 1) + 8 K (n_cols + n) + 8 K n).  C2 is mat10000 with its diagonal split off and d_j = its diagonal
+times (1 + j/8); the generated systems keep their matrix as A0 and get d_j = (1 + j)/8.  All FLAG_NO_EXIT.
 """
 import argparse
 import json
@@ -98,6 +104,89 @@ def run(name, iters):
     return out
 
 
+def make_split(ctx, name):
+    """make(), but mat10000 loses its diagonal: (solver of A0, n, nnz, kept arrays, the diagonal or None)"""
+    if name != "C2_mat10000":
+        return make(ctx, name) + (None,)
+    err, m, n, nnz, val, row, col = cm.loadMMSparseMatrix(os.path.join(ROOT, "tests", "golden", "mat10000.mtx"))
+    base = int(row[0])
+    row_of = np.repeat(np.arange(n), np.diff(row))
+    on_diag = (col - base) == row_of
+    dg = np.zeros(n)
+    dg[row_of[on_diag]] = val[on_diag]
+    rp0 = np.zeros(n + 1, np.int32)
+    np.cumsum(np.bincount(row_of[~on_diag], minlength=n), out=rp0[1:])
+    rp, ci, v = ctx.array(rp0, np.int32), ctx.array((col[~on_diag] - base).astype(np.int32), np.int32), ctx.array(val[~on_diag])
+    nnz0 = int(rp0[n])
+    return cm.Solver(ctx, n, n, nnz0, rp, ci, v, 0), n, nnz0, (rp, ci, v), dg
+
+
+def run_shifts(name, iters):
+    ctx = cm.Context(0)
+    s, n, nnz, keep, dg = make_split(ctx, name)
+    B, X, Y = ctx.empty(8 * n), ctx.empty(8 * n), ctx.empty(8 * n)
+    for j in range(8):
+        ctx.gen_xstar(0, n, 100 + j, X.ptr + 8 * j * n)
+    scale = [(1.0 + j / 8.0) if dg is not None else (1.0 + j) / 8.0 for j in range(8)]
+    Dh = np.concatenate([(dg if dg is not None else np.ones(n)) * scale[j] for j in range(8)])
+    D = ctx.array(Dh)
+    del Dh
+    s.spmm_shifts(8, X, n, D, n, B, n)
+    tm = ctx.timer()
+    kw = dict(loop=cm.LOOP_PBICGSTAB, tol=1e-8, flags=cm.FLAG_NO_EXIT)
+    for K in (1, 2, 4, 8):
+        s.spmm_shifts(K, X, n, D, n, Y, n)
+        reps = 10
+        tm.start()
+        for _ in range(reps):
+            s.spmm_shifts(K, X, n, D, n, Y, n)
+        tm.stop()
+        ms = tm.elapsed_ms() / reps
+        nbytes = 12 * nnz + 4 * (n + 1) + 8 * K * (n + n) + 8 * K * n
+        x = ctx.empty(K * n)
+        # per-column shifts, batched
+        ctx.set_option("MANY_FORM", "batched")
+        x.zero()
+        s.solve_shifts(K, D, n, B, n, x, n, maxit=2, **kw)                                       # warm-up
+        x.zero()
+        sts, form_k = s.solve_shifts(K, D, n, B, n, x, n, maxit=iters, **kw)
+        t_k = sts[0].t_solve
+        # (b) the shared-d batched loop: every column with d_0
+        s.set_shift(D)
+        x.zero()
+        s.solve_many(K, B, n, x, n, maxit=2, **kw)                                               # warm-up
+        x.zero()
+        sts, form_b = s.solve_many(K, B, n, x, n, maxit=iters, **kw)
+        t_b = sts[0].t_solve
+        # (a) K sequential set_shift + solve
+        t_s = 0.0
+        for j in range(K):
+            x.zero()
+            ctx.sync()
+            s.set_shift(D.ptr + 8 * j * n)
+            st = s.solve(B.ptr + 8 * j * n, x.ptr + 8 * j * n, maxit=iters, **kw)
+            t_s += st.t_solve
+        s.set_shift(None)
+        # what auto picks with shifts (the first such call of this solver per K times both forms)
+        ctx.set_option("MANY_FORM", "auto")
+        x.zero()
+        sts_a, form_a = s.solve_shifts(K, D, n, B, n, x, n, maxit=iters, **kw)
+        x.free()
+        t_best = min(t_k, t_s)
+        line = {"config": name, "shifts": "per column", "n": n, "nnz": nnz, "K": K, "iters": iters, "shifts_form": form_k,
+                "shifts_col_it_s": K * iters / t_k, "shared_d_batched_col_it_s": K * iters / t_b,
+                "sequential_col_it_s": K * iters / t_s, "gain_vs_sequential": t_s / t_k, "vs_shared_d_batched": t_b / t_k,
+                "spmm_ms": ms, "spmm_bytes": nbytes, "spmm_roofline": nbytes / (ms * 1e-3) / HBM_PEAK,
+                "auto_form": "batched" if form_a else "columns", "auto_t_tune_s": sts_a[0].t_tune,
+                "auto_col_it_s": K * iters / sts_a[0].t_solve,
+                "auto_picked_faster": (form_a == 1) == (t_k <= t_s), "faster_margin": abs(t_k - t_s) / t_best}
+        print(json.dumps(line), flush=True)
+    for a in (B, X, Y, D):
+        a.free()
+    s.close()
+    ctx.close()
+
+
 def run_precond(name, iters, sequential_only, build):
     ctx = cm.Context(0)
     ctx.set_option("TRSV_HYBRID", "0")
@@ -148,6 +237,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--c4", action="store_true")
     ap.add_argument("--precond", choices=["none", "ilu0"], default="none")
+    ap.add_argument("--shifts", action="store_true", help="one shift vector per column: solve_shifts against its two yardsticks")
     ap.add_argument("--sequential-only", action="store_true")
     ap.add_argument("--build", default="this", help="label of the library build in the output lines")
     ap.add_argument("--only", default="", help="run the configs whose name contains this")
@@ -161,4 +251,5 @@ if __name__ == "__main__":
     if a.c4:
         configs.append(("C4_rand1e7x50", 10))
     for name, it in configs:
-        run(name, it)
+        if a.only in name:
+            (run_shifts if a.shifts else run)(name, it)
