@@ -61,7 +61,8 @@ int launch_batch_out(hipStream_t s, int K, int kc, int64_t rows, const double *s
 int launch_init_b(hipStream_t s, int K, int64_t n, const double *b, double *r, double *rw, double *p, double *parts,
                   int *nparts);
 // columns >= kc are dead: their state starts at 2 (stopped) and nothing touches them
-int launch_init_finish_b(hipStream_t s, int K, int kc, LoopState *st, const double *parts, int count, double tol);
+int launch_init_finish_b(hipStream_t s, int K, int kc, LoopState *st, const double *parts, int count, double tol, int no_exit,
+                         const double *r, int64_t n);
 int launch_update_p_b(hipStream_t s, int K, BatchArgs la, const double *full, int full_count, int64_t n, const double *r,
                       double *p, const double *v);
 int launch_half_b(hipStream_t s, int K, BatchArgs la, const double *rv, int rv_count, int64_t n, double *r, const double *v,

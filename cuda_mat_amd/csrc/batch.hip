@@ -338,17 +338,28 @@ int launch_init_b(hipStream_t s, int K, int64_t n, const double *b, double *r, d
     CM_BATCH_DISPATCH(k_init_b, g, n, b, r, rw, p, parts)
 }
 
+// r (interleaved, n rows): looked at only for a column whose sum of squares is exactly 0 (device.h: init_refusal)
 template <int K>
-__global__ __launch_bounds__(kBlock) void k_init_finish_b(int kc, LoopState *st, const double *parts, int count, double tol)
+__global__ __launch_bounds__(kBlock) void k_init_finish_b(int kc, LoopState *st, const double *parts, int count, double tol,
+                                                          int no_exit, const double *r, int64_t n)
 {
     __shared__ double lds[8 * K];
     double sc[2 * K];
-    load_parts<2 * K>(parts, count, sc, lds);
+    load_parts<2 * K>(parts, count, sc, lds);      // (every thread holds the sums)
+    unsigned nonzero = 0;
+    for (int j = 0; j < kc; j++) {
+        if (sc[2 * j + 1] != 0.0) continue;        // workgroup-uniform, and rare: is the column's r0 zero, or did every square underflow?
+        int any = 0;
+        for (int64_t i = threadIdx.x; i < n; i += kBlock) any |= r[(size_t)i * K + j] != 0.0;
+        if (__syncthreads_or(any)) nonzero |= 1u << j;
+    }
     if (threadIdx.x == 0) {
         for (int j = 0; j < K; j++) {
             const double nrm0 = j < kc ? sqrt(sc[2 * j + 1]) : 0.0;     // pbicgstab.cu:74 / :655
             LoopState *q = st + j;
-            q->state = nrm0 == 0.0 ? 2 : 0;      // x0 solves the system (or a padding column): frozen from the start
+            int state = nrm0 == 0.0 ? 2 : 0;     // x0 solves the system (or a padding column): frozen from the start
+            if (j < kc && !no_exit && tol > 0.0 && init_refusal(nrm0, tol * nrm0, (nonzero >> j) & 1u)) state = 3;
+            q->state = state;
             q->it = 0;
             q->rho[0] = 1.0;
             q->rho[1] = 1.0;
@@ -361,9 +372,10 @@ __global__ __launch_bounds__(kBlock) void k_init_finish_b(int kc, LoopState *st,
     }
 }
 
-int launch_init_finish_b(hipStream_t s, int K, int kc, LoopState *st, const double *parts, int count, double tol)
+int launch_init_finish_b(hipStream_t s, int K, int kc, LoopState *st, const double *parts, int count, double tol, int no_exit,
+                         const double *r, int64_t n)
 {
-    CM_BATCH_DISPATCH(k_init_finish_b, 1, kc, st, parts, count, tol)
+    CM_BATCH_DISPATCH(k_init_finish_b, 1, kc, st, parts, count, tol, no_exit, r, n)
 }
 
 // full-step test of the previous iteration; p = r + beta (p - omega v)                 pbicgstab.cu:80-89

@@ -349,7 +349,7 @@ extern "C" int cudamat_nrm2(cudamat_ctx *ctx, int64_t n, const double *x, double
     CM_ARG(ctx && out_dev && n >= 0 && (n == 0 || x), "bad argument");
     int np = 0;
     CM_TRY(launch_dot_parts(ctx->stream, n, x, x, ctx->parts, &np));
-    return launch_reduce_parts(ctx->stream, ScalarSrc{ctx->parts, np, 1}, 1, out_dev, 1);
+    return launch_nrm2_finish(ctx->stream, ScalarSrc{ctx->parts, np, 1}, n, x, out_dev);
 }
 
 extern "C" int cudamat_axpy(cudamat_ctx *ctx, int64_t n, double alpha, const double *x, double *y)

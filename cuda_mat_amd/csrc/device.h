@@ -137,6 +137,27 @@ __device__ __forceinline__ void publish_progress(const LoopArgs &la, int state)
 }
 
 // ------------------------------------------------------------- stopping tests
+// The range in which `nrm < tolabs` on plain sums of squares means what it says.  The loops neither rescale nor carry
+// scaled norms: a solve whose stopping tests cannot be trusted is REFUSED when its state is initialised (state 3, no
+// iteration, x0 untouched) instead of reporting a convergence it has not computed:
+//   - ||r0|| is not finite (the sum of squares overflowed, or holds a NaN): tolabs would be inf or NaN;
+//   - ||r0|| == 0 although r0 has a non-zero entry: every square underflowed (r0 == 0 itself is the 'x0 solves the
+//     system' case and stays converged).  r_nonzero comes from a look at r0 that only this case pays for.  A sharded run
+//     does not take it yet: each rank holds a slice of r0 and the ranks must agree, so the answer would have to travel
+//     with the all-reduce of the initial sums (its first slot only repeats the second); until then total underflow there
+//     still reads as r0 == 0;
+//   - 0 < tolabs < kTolabsMin = sqrt(DBL_MIN / DBL_EPSILON) = 2^-485: a residual at the tolerance has squares below
+//     DBL_MIN / DBL_EPSILON = 2^-970, where the spacing of doubles (2^-1074, subnormal) exceeds DBL_EPSILON times the
+//     square: the terms of the sum are no longer held to full precision and vanish altogether below 2^-537, so the sum
+//     can pass the test for a residual that does not.
+// Only called where a stopping test applies (no FLAG_NO_EXIT, a tolerance > 0).
+constexpr double kTolabsMin = 0x1p-485;
+
+__device__ __forceinline__ bool init_refusal(double nrm0, double tolabs, bool r_nonzero)
+{
+    return !isfinite(nrm0) || (nrm0 == 0.0 && r_nonzero) || (tolabs > 0.0 && tolabs < kTolabsMin);
+}
+
 // half-step test, pbicgstab.cu:111-118.  Returns true when the caller must return.
 __device__ __forceinline__ bool check_half(const LoopArgs &la, const ScalarSrc &half, double *lds)
 {

@@ -131,7 +131,8 @@ int launch_init(hipStream_t s, int64_t n, const double *b, double *r, double *rw
 // one workgroup: set up LoopState from the initial reduction
 // abs_tol > 0: the loop stops at this absolute residual norm (tol is ignored) and starts out 'converged' when the
 // initial residual is within twice of it
-int launch_init_finish(hipStream_t s, LoopState *st, ScalarSrc init, double tol, double abs_tol = 0.0);
+int launch_init_finish(hipStream_t s, LoopState *st, ScalarSrc init, double tol, double abs_tol, int no_exit, const double *r,
+                       int64_t n);
 // p = r + beta (p - omega v), preceded by the full-step test of the previous iteration
 int launch_update_p(hipStream_t s, LoopArgs la, ScalarSrc full, int64_t n, const double *r,
                     double *p, const double *v);
@@ -162,6 +163,7 @@ int launch_pipe_dots(hipStream_t s, const LoopArgs &la, int64_t n, const double 
 int launch_check(hipStream_t s, LoopArgs la, ScalarSrc src, int which);
 // out[k] = sum of partials, k < K (one workgroup)
 int launch_reduce_parts(hipStream_t s, ScalarSrc in, int K, double *out, int sqrt_it);
+int launch_nrm2_finish(hipStream_t s, ScalarSrc sq, int64_t n, const double *x, double *out);
 // generic streaming kernels
 int launch_dot_parts(hipStream_t s, int64_t n, const double *x, const double *y, double *parts,
                      int *nparts);

@@ -55,6 +55,51 @@ int launch_reduce_parts(hipStream_t s, ScalarSrc in, int K, double *out, int sqr
     return CUDAMAT_OK;
 }
 
+// ||x|| over the whole range of doubles, like the scaled cublasDnrm2 it stands for.  `sq` holds the partials of the plain
+// sum of squares: wherever that sum is trustworthy the result is its square root, with the bits it always had.  Where it
+// is inf, 0, or below DBL_MIN / DBL_EPSILON (squares that overflowed, underflowed, or lost bits as subnormals) this one
+// workgroup sums again with x scaled by the power of two that brings max|x| into [0.5, 1): a rare path, not a fast one.
+// A NaN in x makes the plain sum NaN, which is returned; an inf makes the norm inf.
+__global__ __launch_bounds__(kBlock) void k_nrm2_finish(ScalarSrc sq, int64_t n, const double *x, double *out)
+{
+    __shared__ double lds[8];
+    double sc[1];
+    load_scalars<1>(sq, sc, lds);                  // (every thread holds the sum)
+    const double plain = sc[0];
+    if (!(plain == 0.0 || plain == INFINITY || plain < 0x1p-970)) {      // in range, or NaN
+        if (threadIdx.x == 0) out[0] = sqrt(plain);
+        return;
+    }
+    double big = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += kBlock) big = fmax(big, fabs(x[i]));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) big = fmax(big, __shfl_xor(big, o, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = big;
+    __syncthreads();
+    big = fmax(fmax(lds[0], lds[1]), fmax(lds[2], lds[3]));
+    if (big == 0.0 || big == INFINITY) {
+        if (threadIdx.x == 0) out[0] = big;
+        return;
+    }
+    int e = 0;
+    (void)frexp(big, &e);                          // big = f * 2^e, f in [0.5, 1)
+    double acc[1] = {0.0};
+    for (int64_t i = threadIdx.x; i < n; i += kBlock) {
+        const double v = ldexp(x[i], -e);          // exact, but for entries below 2^-1022 max|x|: they do not count
+        acc[0] += v * v;
+    }
+    block_sum<1>(acc, lds);                        // in [0.25, n)
+    if (threadIdx.x == 0) out[0] = ldexp(sqrt(acc[0]), e);
+}
+
+int launch_nrm2_finish(hipStream_t s, ScalarSrc sq, int64_t n, const double *x, double *out)
+{
+    hipLaunchKernelGGL(k_nrm2_finish, dim3(1), dim3(kBlock), 0, s, sq, n, x, out);
+    CM_HIP(hipGetLastError());
+    return CUDAMAT_OK;
+}
+
 // ------------------------------------------------------- streaming vector kernels
 // 16 bytes per lane (double2) whenever every operand is 16-byte aligned; a fixed
 // grid (<= kVecGridMax workgroups) walks the vector grid-stride so that the number
@@ -106,32 +151,44 @@ int launch_init(hipStream_t s, int64_t n, const double *b, double *r, double *rw
     return CUDAMAT_OK;
 }
 
-__global__ __launch_bounds__(kBlock) void k_init_finish(LoopState *st, ScalarSrc init, double tol, double abs_tol)
+// r / n: this rank's r0, looked at only when the sum of squares is exactly 0 (NULL in a sharded run: see init_refusal)
+__global__ __launch_bounds__(kBlock) void k_init_finish(LoopState *st, ScalarSrc init, double tol, double abs_tol, int no_exit,
+                                                        const double *r, int64_t n)
 {
     __shared__ double lds[8];
     double sc[2];
-    load_scalars<2>(init, sc, lds);
+    load_scalars<2>(init, sc, lds);                // (every thread holds the sums)
+    int any = 0;
+    if (sc[1] == 0.0 && r) {                       // workgroup-uniform, and rare: is r0 zero, or did every square underflow?
+        for (int64_t i = threadIdx.x; i < n; i += kBlock) any |= r[i] != 0.0;
+        any = __syncthreads_or(any);
+    }
     if (threadIdx.x == 0) {
         const double nrm0 = sqrt(sc[1]);           // pbicgstab.cu:74 / :655
+        const double tolabs = abs_tol > 0.0 ? abs_tol : tol * nrm0;
         // x0 already solves the system exactly (r0 = 0): the reference's loop would divide 0 by 0 and hand back NaNs;
         // here the loop starts frozen in the 'converged' state and x0 is returned untouched
         // abs_tol > 0 (a restart that verifies an iterate): stop at that ABSOLUTE residual, and if the residual of the
         // initial guess is already within twice of it (a recursive residual drifts by about that much) there is nothing to do
-        st->state = (nrm0 == 0.0 || (abs_tol > 0.0 && nrm0 <= 2.0 * abs_tol)) ? 2 : 0;
+        int state = (nrm0 == 0.0 || (abs_tol > 0.0 && nrm0 <= 2.0 * abs_tol)) ? 2 : 0;
+        // (a restart with abs_tol, itself >= kTolabsMin, whose true residual underflows to 0 IS below its target: not refused)
+        if (!no_exit && (tol > 0.0 || abs_tol > 0.0) && init_refusal(nrm0, tolabs, any != 0 && !(abs_tol > 0.0))) state = 3;
+        st->state = state;
         st->it = 0;
         st->rho[0] = 1.0;                          // pbicgstab.cu:617 (rho = 1)
         st->rho[1] = 1.0;
         st->alpha = 1.0;                           // :615
         st->omega = 1.0;                           // :614
         st->nrm0 = nrm0;
-        st->tolabs = abs_tol > 0.0 ? abs_tol : tol * nrm0;
+        st->tolabs = tolabs;
         st->nrm = nrm0;
     }
 }
 
-int launch_init_finish(hipStream_t s, LoopState *st, ScalarSrc init, double tol, double abs_tol)
+int launch_init_finish(hipStream_t s, LoopState *st, ScalarSrc init, double tol, double abs_tol, int no_exit, const double *r,
+                       int64_t n)
 {
-    hipLaunchKernelGGL(k_init_finish, dim3(1), dim3(kBlock), 0, s, st, init, tol, abs_tol);
+    hipLaunchKernelGGL(k_init_finish, dim3(1), dim3(kBlock), 0, s, st, init, tol, abs_tol, no_exit, r, n);
     CM_HIP(hipGetLastError());
     return CUDAMAT_OK;
 }

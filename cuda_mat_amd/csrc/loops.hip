@@ -222,7 +222,8 @@ int Solve::setup()
         CM_TRY(allreduce(s, s->red + 4, 2));
         full_src = ScalarSrc{s->red + 4, 0, 1};
     }
-    CM_TRY(launch_init_finish(st, s->st, full_src, tol, abs_tol));
+    // (sharded: the ranks must take the same decision, and r0's entries are spread over them -- init_refusal)
+    CM_TRY(launch_init_finish(st, s->st, full_src, tol, abs_tol, la.no_exit, sharded ? nullptr : s->r, n));
     return CUDAMAT_OK;
 }
 
