@@ -48,8 +48,7 @@ struct SpmmArgs {
     const double *half;    // k_half_b partials (stride K)
     int half_count;
 };
-// the partition of the lanes-per-row plan for L lanes (plan_spmv's); parts = workgroups
-void spmm_partition(int L, int n, int *grid, int *rows_per_block);
+// (the row partition is spmv_partition(L, n, ...), kernels.h; parts = its workgroups)
 int launch_spmm(hipStream_t s, int L, int K, const SpmmArgs &a);
 
 // column-major (leading dimension ld) <-> interleaved.  In: columns >= kc and rows in [rows, rows_out) become `fill`.

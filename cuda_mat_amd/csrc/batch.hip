@@ -93,7 +93,7 @@ __global__ __launch_bounds__(kBlock) void k_spmm_csr(SpmmArgs a, int rows_per_bl
     const int lane = threadIdx.x & (L - 1);
     const int group = threadIdx.x / L;
     const int nb = gridDim.x, b = blockIdx.x;
-    const int cid = ((nb & 7) == 0) ? (b & 7) * (nb >> 3) + (b >> 3) : b;
+    const int cid = xcd_chunk(b, nb);
     const long long r0 = (long long)cid * rows_per_block;
     const int row_begin = (int)(r0 < a.n ? r0 : a.n);
     const int row_end = (int)(r0 + rows_per_block < a.n ? r0 + rows_per_block : a.n);
@@ -123,27 +123,7 @@ __global__ __launch_bounds__(kBlock) void k_spmm_csr(SpmmArgs a, int rows_per_bl
         }
 #pragma unroll
         for (int j = 0; j < K; j++) sum[j] = group_sum<L>(sum[j]);
-        if (lane == 0) {
-            double out[K], yo[K], xd[K], w[K], dk[K];
-            if (a.beta != 0.0) load_row<K>(a.y, row, yo);
-            if (S || a.d) load_row<K>(a.xd, row, xd);
-            if (S) load_row<K>(a.dk, row, dk);
-            if (a.dot) load_row<K>(a.w, row, w);
-#pragma unroll
-            for (int j = 0; j < K; j++) {
-                double sj = sum[j];
-                if (S) sj += dk[j] * xd[j];
-                else if (a.d) sj += a.d[row] * xd[j];
-                double o = a.alpha * sj;
-                if (a.beta != 0.0) o += a.beta * yo[j];
-                out[j] = o;
-                if (a.dot) {
-                    acc[2 * j] += o * w[j];
-                    acc[2 * j + 1] += o * o;
-                }
-            }
-            store_row<K>(a.y, row, out, kAll);
-        }
+        if (lane == 0) spmm_finish_row<K, S>(a, row, sum, acc);
     }
     __syncthreads();
     for (int done = 0, nl; (nl = long_rows_round(lr, a.rp, row_begin, row_end, done)) > 0; done += nl) {
@@ -161,27 +141,7 @@ __global__ __launch_bounds__(kBlock) void k_spmm_csr(SpmmArgs a, int rows_per_bl
                 for (int j = 0; j < K; j++) part[j] += v * xv[j];
             }
             block_sum<K>(part, lds);
-            if (threadIdx.x == 0) {
-                double out[K], yo[K], xd[K], w[K], dk[K];
-                if (a.beta != 0.0) load_row<K>(a.y, row, yo);
-                if (S || a.d) load_row<K>(a.xd, row, xd);
-                if (S) load_row<K>(a.dk, row, dk);
-                if (a.dot) load_row<K>(a.w, row, w);
-#pragma unroll
-                for (int j = 0; j < K; j++) {
-                    double sj = part[j];
-                    if (S) sj += dk[j] * xd[j];
-                    else if (a.d) sj += a.d[row] * xd[j];
-                    double o = a.alpha * sj;
-                    if (a.beta != 0.0) o += a.beta * yo[j];
-                    out[j] = o;
-                    if (a.dot) {
-                        acc[2 * j] += o * w[j];
-                        acc[2 * j + 1] += o * o;
-                    }
-                }
-                store_row<K>(a.y, row, out, kAll);
-            }
+            if (threadIdx.x == 0) spmm_finish_row<K, S>(a, row, part, acc);
         }
     }
     if (a.dot) {
@@ -191,20 +151,6 @@ __global__ __launch_bounds__(kBlock) void k_spmm_csr(SpmmArgs a, int rows_per_bl
             for (int q = 0; q < 2 * K; q++) a.parts[(size_t)b * 2 * K + q] = acc[q];
         }
     }
-}
-
-void spmm_partition(int L, int n, int *grid, int *rows_per_block)
-{
-    const int rpb = kBlock / L;          // plan_spmv's partition (spmv_csr.hip)
-    long long groups = ((long long)n + rpb - 1) / rpb;
-    int g = (int)(groups < kSpmvGridMax ? groups : kSpmvGridMax);
-    if (g < 1) g = 1;
-    long long per = ((long long)n + g - 1) / g;
-    per = (per + rpb - 1) / rpb * rpb;
-    if (per < rpb) per = rpb;
-    *rows_per_block = (int)per;
-    *grid = (int)(((long long)n + per - 1) / per);
-    if (*grid < 1) *grid = 1;
 }
 
 template <int L, bool S>
@@ -243,7 +189,7 @@ int launch_spmm(hipStream_t s, int L, int K, const SpmmArgs &a)
         return CUDAMAT_ERR_ARG;
     }
     int grid = 1, rpb = 1;
-    spmm_partition(L, a.n, &grid, &rpb);
+    spmv_partition(L, a.n, &grid, &rpb);
     return a.dk ? launch_spmm_s<true>(s, L, K, a, grid, rpb) : launch_spmm_s<false>(s, L, K, a, grid, rpb);
 }
 

@@ -1,9 +1,11 @@
 // device.h -- device-side helpers shared by the kernels of libcudamat_hip.so: fixed-order workgroup reductions, the
 // scalars that live in HBM (per-workgroup partial sums summed by every consumer), the loop state as a workgroup reads
-// it, and the half-step stopping test that SpMV kernels evaluate in their prologue.  256-thread workgroups (kBlock).
+// it, the half-step stopping test that SpMV kernels evaluate in their prologue, and the pieces every SpMV-shaped kernel
+// shares: prologue, XCD-aware dealing, row epilogue (two rounding flavours), dot partials.  256-thread workgroups (kBlock).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "batch.h"
 #include "kernels.h"
 
 namespace cm {
@@ -282,9 +284,60 @@ __device__ __forceinline__ int block_scan_int(int v, int *lds_waves, int *total)
     return before + inc - v;
 }
 
-// y = alpha*(sum + d.*xd) + beta*y for one row, and the row's share of the fused dots (w.y, y.y)
-__device__ __forceinline__ void spmv_finish_row(const SpmvArgs &a, int row, double sum, double (&acc)[2])
+// ------------------------------------------------------------------ the parts every SpMV-shaped kernel shares
+// Prologue of a kernel that may evaluate the half-step test: true when the launch must return (the loop is frozen, or the
+// test it evaluated here stopped it).  Kernels that never evaluate the test look at state alone and do not call this.
+__device__ __forceinline__ bool spmv_enter(const SpmvArgs &a, double *lds)
 {
+    if (!a.loop.st) return false;
+    if (a.check == CHECK_HALF) return check_half(a.loop, a.half, lds);
+    return a.loop.st->state != 0;
+}
+
+// Work is dealt to workgroups XCD by XCD (workgroup b runs on XCD b & 7 when the grid is a multiple of 8): each XCD gets a
+// contiguous eighth, so rows that share x entries (banded matrices) meet in one 4 MiB L2.
+// Chunks -- one contiguous run of rows or tiles per workgroup: the chunk of workgroup b.
+__device__ __forceinline__ int xcd_chunk(int b, int nb)
+{
+    return ((nb & 7) == 0) ? (b & 7) * (nb >> 3) + (b >> 3) : b;
+}
+
+// Tiles -- tiles_per_block of them per workgroup, dealt CYCLICALLY inside the XCD's contiguous share: the t-th tile of
+// workgroup b.  At any moment the workgroups of one XCD sit on neighbouring tiles, so the three uses of an x entry by a
+// stencil row (rows i - nx, i, i + nx) fall into the same few microseconds and hit the XCD's L2 instead of being re-fetched
+// after 20 MB of streamed entries.
+__device__ __forceinline__ long long xcd_tile(int b, int nb, int tiles_per_block, int t)
+{
+    const bool xcd_split = (nb & 7) == 0;
+    const int wg_per_set = xcd_split ? nb >> 3 : nb;
+    const int set = xcd_split ? (b & 7) : 0;
+    const int w = xcd_split ? (b >> 3) : b;
+    const long long set_tile0 = (long long)set * wg_per_set * tiles_per_block;
+    return set_tile0 + (long long)t * wg_per_set + w;
+}
+
+// Row epilogue: y = alpha*(sum + d.*xd) + beta*y for one row, and the row's share of the fused dots (w.y, y.y).
+// Two flavours, and a kernel's bits depend on which one it calls.  Both bodies sit under
+// contract(off) -- the pragma is lexical, an inlined helper keeps the setting of the place it is written in, not its
+// caller's -- so each says exactly what it computes:
+//   fused: fma(d, xd, sum); fma(beta, y, alpha*sum); fma(out, w, acc0); fma(out, out, acc1)  -- spmv_csr.hip, k_spmm_csr
+//   exact: one rounding per product and per sum (the CPU loop's)                           -- pattern and SELL forms
+__device__ __forceinline__ void spmv_finish_row_fused(const SpmvArgs &a, int row, double sum, double (&acc)[2])
+{
+#pragma clang fp contract(off)
+    if (a.d) sum = fma(a.d[row], a.xd[row], sum);
+    double out = a.alpha * sum;
+    if (a.beta != 0.0) out = fma(a.beta, a.y[row], out);
+    a.y[row] = out;
+    if (a.dot) {
+        acc[0] = fma(out, a.w[row], acc[0]);
+        acc[1] = fma(out, out, acc[1]);
+    }
+}
+
+__device__ __forceinline__ void spmv_finish_row_exact(const SpmvArgs &a, int row, double sum, double (&acc)[2])
+{
+#pragma clang fp contract(off)
     if (a.d) sum += a.d[row] * a.xd[row];
     double out = a.alpha * sum;
     if (a.beta != 0.0) out += a.beta * a.y[row];
@@ -293,6 +346,56 @@ __device__ __forceinline__ void spmv_finish_row(const SpmvArgs &a, int row, doub
         acc[0] += out * a.w[row];
         acc[1] += out * out;
     }
+}
+
+// The K-column form of the fused flavour (k_spmm_csr): column j does what spmv_finish_row_fused does, in the same order.
+// S: per-column shifts a.dk in place of the shared a.d.
+template <int K, bool S>
+__device__ __forceinline__ void spmm_finish_row(const SpmmArgs &a, int row, const double (&sum)[K], double (&acc)[2 * K])
+{
+#pragma clang fp contract(off)
+    double out[K], yo[K], xd[K], w[K], dk[K];
+    if (a.beta != 0.0) load_row<K>(a.y, row, yo);
+    if (S || a.d) load_row<K>(a.xd, row, xd);
+    if (S) load_row<K>(a.dk, row, dk);
+    if (a.dot) load_row<K>(a.w, row, w);
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        double sj = sum[j];
+        if (S) sj = fma(dk[j], xd[j], sj);
+        else if (a.d) sj = fma(a.d[row], xd[j], sj);
+        double o = a.alpha * sj;
+        if (a.beta != 0.0) o = fma(a.beta, yo[j], o);
+        out[j] = o;
+        if (a.dot) {
+            acc[2 * j] = fma(o, w[j], acc[2 * j]);
+            acc[2 * j + 1] = fma(o, o, acc[2 * j + 1]);
+        }
+    }
+    store_row<K>(a.y, row, out, kAll);
+}
+
+// the workgroup's two dot partials -> parts[2 * slot], parts[2 * slot + 1] (slot: the workgroup's place among the launch's)
+__device__ __forceinline__ void spmv_store_dots(const SpmvArgs &a, int slot, double (&acc)[2], double *lds)
+{
+    if (!a.dot) return;
+    block_sum<2>(acc, lds);
+    if (threadIdx.x == 0) {
+        a.parts[2 * slot] = acc[0];
+        a.parts[2 * slot + 1] = acc[1];
+    }
+}
+
+// Tail of a stream tile (rows r0 .. r0 + nr, products in prod, row i's at [srp[i] - base, srp[i + 1] - base)): thread i < nr
+// adds its row's products in column order (the rounding sequence of the CPU loop) and finishes the row.
+__device__ __forceinline__ void stream_finish_rows(const SpmvArgs &a, int r0, int nr, const int *srp, int base,
+                                                   const double *prod, double (&acc)[2])
+{
+    const int tid = threadIdx.x;
+    if (tid >= nr) return;
+    double sum = 0.0;
+    for (int j = srp[tid] - base; j < srp[tid + 1] - base; j++) sum += prod[j];
+    spmv_finish_row_fused(a, r0 + tid, sum, acc);
 }
 
 // ---- streaming vector kernels: 16 bytes per lane (double2) whenever every operand is 16-byte aligned

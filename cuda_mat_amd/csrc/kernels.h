@@ -49,6 +49,22 @@ struct SpmvPlan {
     unsigned char *d_val8 = nullptr;
 };
 SpmvPlan plan_spmv(const Config &cfg, int n_rows, int64_t nnz);
+// The row partition of the lanes-per-row kernels (k_spmv<L>, k_spmm_csr<L, K>): every workgroup owns rows_per_block
+// contiguous rows, a multiple of its kBlock / L groups, on at most kSpmvGridMax workgroups.  It depends on n_rows and L
+// only, and both kernels take it from here: a row is reduced the same way with one column or K.
+inline void spmv_partition(int L, int n_rows, int *grid, int *rows_per_block)
+{
+    const int rpb = kBlock / L;
+    long long groups = ((long long)n_rows + rpb - 1) / rpb;
+    int g = (int)(groups < kSpmvGridMax ? groups : kSpmvGridMax);
+    if (g < 1) g = 1;
+    long long per = ((long long)n_rows + g - 1) / g;
+    per = (per + rpb - 1) / rpb * rpb;
+    if (per < rpb) per = rpb;
+    *rows_per_block = (int)per;
+    *grid = (int)(((long long)n_rows + per - 1) / per);
+    if (*grid < 1) *grid = 1;
+}
 void plan_spmv_free(SpmvPlan *plan);
 // per-workgroup dot partials one launch leaves behind
 inline int plan_spmv_parts(const SpmvPlan &p) { return p.grid + (p.tiles ? p.tile_fix_grid : 0); }

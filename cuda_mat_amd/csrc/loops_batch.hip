@@ -215,7 +215,7 @@ int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, do
     // r = A x0; r = b - r, rw = r, p = r; the states                                        pbicgstab.cu:67-74 / :645-659
     CM_TRY(launch_spmm(st, L, K, spmm_args(s, m.x, m.r, dk)));
     int np_full = 0, np_half = 0, np_spmm = 0, rpb = 0;
-    spmm_partition(L, n, &np_spmm, &rpb);
+    spmv_partition(L, n, &np_spmm, &rpb);
     CM_TRY(launch_init_b(st, K, n, m.b, m.r, m.rw, m.p, m.parts_full, &np_full));
     CM_TRY(launch_init_finish_b(st, K, kc, m.st, m.parts_full, np_full, tol, la.no_exit, m.r, n));
     for (int k = 0; k < maxit; k++) {

@@ -20,18 +20,12 @@ template <int L>
 __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a, int rows_per_block)
 {
     __shared__ double lds[8];
-    if (a.loop.st) {
-        if (a.check == CHECK_HALF) {
-            if (check_half(a.loop, a.half, lds)) return;
-        } else if (a.loop.st->state != 0) {
-            return;
-        }
-    }
+    if (spmv_enter(a, lds)) return;
     constexpr int RPB = kBlock / L;
     const int lane = threadIdx.x & (L - 1);
     const int group = threadIdx.x / L;
     const int nb = gridDim.x, b = blockIdx.x;
-    const int cid = ((nb & 7) == 0) ? (b & 7) * (nb >> 3) + (b >> 3) : b;
+    const int cid = xcd_chunk(b, nb);
     const long long r0 = (long long)cid * rows_per_block;
     const int row_begin = (int)(r0 < a.n ? r0 : a.n);
     const int row_end = (int)(r0 + rows_per_block < a.n ? r0 + rows_per_block : a.n);
@@ -56,16 +50,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a, int rows_per_block)
         for (int k = s + lane; k < e; k += L)
             sum += __builtin_nontemporal_load(a.val + k) * a.x[__builtin_nontemporal_load(a.ci + k)];
         sum = group_sum<L>(sum);
-        if (lane == 0) {
-            if (a.d) sum += a.d[row] * a.xd[row];
-            double out = a.alpha * sum;
-            if (a.beta != 0.0) out += a.beta * a.y[row];
-            a.y[row] = out;
-            if (a.dot) {
-                acc[0] += out * a.w[row];
-                acc[1] += out * out;
-            }
-        }
+        if (lane == 0) spmv_finish_row_fused(a, row, sum, acc);
     }
     __syncthreads();
     for (int done = 0, nl; (nl = long_rows_round(lr, a.rp, row_begin, row_end, done)) > 0; done += nl) {
@@ -76,26 +61,10 @@ __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a, int rows_per_block)
             for (int k = s + (int)threadIdx.x; k < e; k += kBlock)
                 part[0] += __builtin_nontemporal_load(a.val + k) * a.x[__builtin_nontemporal_load(a.ci + k)];
             block_sum<1>(part, lds);
-            if (threadIdx.x == 0) {
-                double sum = part[0];
-                if (a.d) sum += a.d[row] * a.xd[row];
-                double out = a.alpha * sum;
-                if (a.beta != 0.0) out += a.beta * a.y[row];
-                a.y[row] = out;
-                if (a.dot) {
-                    acc[0] += out * a.w[row];
-                    acc[1] += out * out;
-                }
-            }
+            if (threadIdx.x == 0) spmv_finish_row_fused(a, row, part[0], acc);
         }
     }
-    if (a.dot) {
-        block_sum<2>(acc, lds);
-        if (threadIdx.x == 0) {
-            a.parts[2 * b] = acc[0];
-            a.parts[2 * b + 1] = acc[1];
-        }
-    }
+    spmv_store_dots(a, b, acc, lds);
 }
 
 SpmvPlan plan_spmv(const Config &cfg, int n_rows, int64_t nnz)
@@ -111,16 +80,7 @@ SpmvPlan plan_spmv(const Config &cfg, int n_rows, int64_t nnz)
     else if (mean <= 96.0) L = 32;
     if (cfg.spmv_lanes) L = cfg.spmv_lanes;
     p.lanes = L;
-    const int rpb = kBlock / L;
-    long long groups = ((long long)n_rows + rpb - 1) / rpb;
-    int grid = (int)(groups < kSpmvGridMax ? groups : kSpmvGridMax);
-    if (grid < 1) grid = 1;
-    long long per = ((long long)n_rows + grid - 1) / grid;
-    per = (per + rpb - 1) / rpb * rpb;
-    if (per < rpb) per = rpb;
-    p.rows_per_block = (int)per;
-    p.grid = (int)(((long long)n_rows + per - 1) / per);
-    if (p.grid < 1) p.grid = 1;
+    spmv_partition(L, n_rows, &p.grid, &p.rows_per_block);
     return p;
 }
 
@@ -137,26 +97,12 @@ __global__ __launch_bounds__(kBlock) void k_spmv_stream(SpmvArgs a, int tiles_pe
     __shared__ double prod[kStreamNnz];
     __shared__ int srp[R + 1];
     __shared__ double lds[8];
-    if (a.loop.st) {
-        if (a.check == CHECK_HALF) {
-            if (check_half(a.loop, a.half, lds)) return;
-        } else if (a.loop.st->state != 0) {
-            return;
-        }
-    }
+    if (spmv_enter(a, lds)) return;
     const int tid = threadIdx.x;
     const int nb = gridDim.x, b = blockIdx.x;
-    // Tiles are dealt CYCLICALLY inside an XCD's contiguous share: at any moment the workgroups of one XCD sit on
-    // neighbouring tiles, so the three uses of an x entry by a stencil row (rows i - nx, i, i + nx) fall into the
-    // same few microseconds and hit the XCD's L2 instead of being re-fetched after 20 MB of streamed entries.
-    const bool xcd_split = (nb & 7) == 0;
-    const int wg_per_set = xcd_split ? nb >> 3 : nb;
-    const int set = xcd_split ? (b & 7) : 0;
-    const int w = xcd_split ? (b >> 3) : b;
-    const long long set_tile0 = (long long)set * wg_per_set * tiles_per_block;
     double acc[2] = {0.0, 0.0};
     for (int t = 0; t < tiles_per_block; t++) {
-        const long long r0l = (set_tile0 + (long long)t * wg_per_set + w) * R;
+        const long long r0l = xcd_tile(b, nb, tiles_per_block, t) * R;
         if (r0l >= a.n) continue;
         const int r0 = (int)r0l;
         const int nr = a.n - r0 < R ? a.n - r0 : R;
@@ -167,29 +113,10 @@ __global__ __launch_bounds__(kBlock) void k_spmv_stream(SpmvArgs a, int tiles_pe
         for (int k = tid; k < cnt; k += kBlock)
             prod[k] = __builtin_nontemporal_load(a.val + base + k) * a.x[__builtin_nontemporal_load(a.ci + base + k)];
         __syncthreads();
-        if (tid < nr) {
-            const int row = r0 + tid;
-            const int s = srp[tid] - base, e = srp[tid + 1] - base;
-            double sum = 0.0;
-            for (int j = s; j < e; j++) sum += prod[j];
-            if (a.d) sum += a.d[row] * a.xd[row];
-            double out = a.alpha * sum;
-            if (a.beta != 0.0) out += a.beta * a.y[row];
-            a.y[row] = out;
-            if (a.dot) {
-                acc[0] += out * a.w[row];
-                acc[1] += out * out;
-            }
-        }
+        stream_finish_rows(a, r0, nr, srp, base, prod, acc);
         __syncthreads();
     }
-    if (a.dot) {
-        block_sum<2>(acc, lds);
-        if (tid == 0) {
-            a.parts[2 * b] = acc[0];
-            a.parts[2 * b + 1] = acc[1];
-        }
-    }
+    spmv_store_dots(a, b, acc, lds);
 }
 
 // ---- the same with compressed indices (banded matrices): per entry a 16-bit column offset from the tile's first
@@ -206,23 +133,12 @@ __global__ __launch_bounds__(kBlock) void k_spmv_stream_c(SpmvArgs a, int tiles_
     __shared__ int srp[R + 1];
     __shared__ int scan_w[kBlock / 64];
     __shared__ double lds[8];
-    if (a.loop.st) {
-        if (a.check == CHECK_HALF) {
-            if (check_half(a.loop, a.half, lds)) return;
-        } else if (a.loop.st->state != 0) {
-            return;
-        }
-    }
+    if (spmv_enter(a, lds)) return;
     const int tid = threadIdx.x;
     const int nb = gridDim.x, b = blockIdx.x;
-    const bool xcd_split = (nb & 7) == 0;
-    const int wg_per_set = xcd_split ? nb >> 3 : nb;
-    const int set = xcd_split ? (b & 7) : 0;
-    const int w = xcd_split ? (b >> 3) : b;
-    const long long set_tile0 = (long long)set * wg_per_set * tiles_per_block;
     double acc[2] = {0.0, 0.0};
     for (int t = 0; t < tiles_per_block; t++) {
-        const long long tile = set_tile0 + (long long)t * wg_per_set + w;
+        const long long tile = xcd_tile(b, nb, tiles_per_block, t);
         const long long r0l = tile * R;
         if (r0l >= a.n) continue;
         const int r0 = (int)r0l;
@@ -236,29 +152,10 @@ __global__ __launch_bounds__(kBlock) void k_spmv_stream_c(SpmvArgs a, int tiles_
         for (int k = tid; k < cnt; k += kBlock)
             prod[k] = __builtin_nontemporal_load(vals + base + k) * a.x[r0 + (int)__builtin_nontemporal_load(off16 + base + k)];
         __syncthreads();
-        if (tid < nr) {
-            const int row = r0 + tid;
-            const int s = srp[tid], e = srp[tid + 1];
-            double sum = 0.0;
-            for (int j = s; j < e; j++) sum += prod[j];
-            if (a.d) sum += a.d[row] * a.xd[row];
-            double out = a.alpha * sum;
-            if (a.beta != 0.0) out += a.beta * a.y[row];
-            a.y[row] = out;
-            if (a.dot) {
-                acc[0] += out * a.w[row];
-                acc[1] += out * out;
-            }
-        }
+        stream_finish_rows(a, r0, nr, srp, 0, prod, acc);
         __syncthreads();
     }
-    if (a.dot) {
-        block_sum<2>(acc, lds);
-        if (tid == 0) {
-            a.parts[2 * b] = acc[0];
-            a.parts[2 * b + 1] = acc[1];
-        }
-    }
+    spmv_store_dots(a, b, acc, lds);
 }
 
 // The same kernel for a matrix with a VALUE DICTIONARY (valdict.h; at most 256 distinct fp64 bit patterns): the plan
@@ -277,23 +174,12 @@ __global__ __launch_bounds__(kBlock) void k_spmv_stream_d(SpmvArgs a, int tiles_
     __shared__ double lds[8];
     __shared__ double dv[kBlock];                     // the dictionary, one entry per thread (kBlock == 256)
     dv[threadIdx.x] = dict[threadIdx.x];              // (visible after the first __syncthreads below)
-    if (a.loop.st) {
-        if (a.check == CHECK_HALF) {
-            if (check_half(a.loop, a.half, lds)) return;
-        } else if (a.loop.st->state != 0) {
-            return;
-        }
-    }
+    if (spmv_enter(a, lds)) return;
     const int tid = threadIdx.x;
     const int nb = gridDim.x, b = blockIdx.x;
-    const bool xcd_split = (nb & 7) == 0;
-    const int wg_per_set = xcd_split ? nb >> 3 : nb;
-    const int set = xcd_split ? (b & 7) : 0;
-    const int w = xcd_split ? (b >> 3) : b;
-    const long long set_tile0 = (long long)set * wg_per_set * tiles_per_block;
     double acc[2] = {0.0, 0.0};
     for (int t = 0; t < tiles_per_block; t++) {
-        const long long tile = set_tile0 + (long long)t * wg_per_set + w;
+        const long long tile = xcd_tile(b, nb, tiles_per_block, t);
         const long long r0l = tile * R;
         if (r0l >= a.n) continue;
         const int r0 = (int)r0l;
@@ -320,29 +206,10 @@ __global__ __launch_bounds__(kBlock) void k_spmv_stream_d(SpmvArgs a, int tiles_
             for (int q = 0; q < 8; q++) prod[8 * tid + q] = dv[(iw[q >> 2] >> (8 * (q & 3))) & 0xffu] * xv[q];
         }
         __syncthreads();
-        if (tid < nr) {
-            const int row = r0 + tid;
-            const int s = srp[tid], e = srp[tid + 1];
-            double sum = 0.0;
-            for (int j = s; j < e; j++) sum += prod[j];
-            if (a.d) sum += a.d[row] * a.xd[row];
-            double out = a.alpha * sum;
-            if (a.beta != 0.0) out += a.beta * a.y[row];
-            a.y[row] = out;
-            if (a.dot) {
-                acc[0] += out * a.w[row];
-                acc[1] += out * out;
-            }
-        }
+        stream_finish_rows(a, r0, nr, srp, 0, prod, acc);
         __syncthreads();
     }
-    if (a.dot) {
-        block_sum<2>(acc, lds);
-        if (tid == 0) {
-            a.parts[2 * b] = acc[0];
-            a.parts[2 * b + 1] = acc[1];
-        }
-    }
+    spmv_store_dots(a, b, acc, lds);
 }
 
 // one 8-lane team per row: 8-bit length, 16-bit offsets from the first row of the row's tile; flags[0] = does not fit
@@ -581,16 +448,10 @@ __global__ __launch_bounds__(kBlock) void k_spmv_tiles(SpmvArgs a, const int *S,
     __shared__ int scan_w[kBlock / 64];
     __shared__ int n_items;
     __shared__ double lds[8];
-    if (a.loop.st) {
-        if (a.check == CHECK_HALF) {
-            if (check_half(a.loop, a.half, lds)) return;
-        } else if (a.loop.st->state != 0) {
-            return;
-        }
-    }
+    if (spmv_enter(a, lds)) return;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int nb = gridDim.x, b = blockIdx.x;
-    const int cid = ((nb & 7) == 0) ? (b & 7) * (nb >> 3) + (b >> 3) : b;
+    const int cid = xcd_chunk(b, nb);
     const int kbase = a.rp[0], kend = a.rp[a.n];
     double acc[2] = {0.0, 0.0};
     for (int tt = 0; tt < tiles_per_block; tt++) {
@@ -631,7 +492,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv_tiles(SpmvArgs a, const int *S,
             if (isrow && !coop) {
                 double sum = 0.0;
                 for (int j = rb - k0; j < rend - k0; j++) sum += prod[j];
-                spmv_finish_row(a, r, sum, acc);
+                spmv_finish_row_fused(a, r, sum, acc);
             }
             int total;
             const int pos = block_scan_flag(coop ? 1 : 0, scan_w, &total);
@@ -654,20 +515,14 @@ __global__ __launch_bounds__(kBlock) void k_spmv_tiles(SpmvArgs a, const int *S,
             for (int j = it.j0 + lane; j < it.j1; j += 64) sum += prod[j];
             sum = wave_sum(sum);
             if (lane == 0) {
-                if (it.kind == 0) spmv_finish_row(a, it.row, sum, acc);
+                if (it.kind == 0) spmv_finish_row_fused(a, it.row, sum, acc);
                 else if (it.kind == 1) heads[t] = sum;
                 else tails[t] = sum;
             }
         }
         __syncthreads();       // prod and items are reused by the next tile
     }
-    if (a.dot) {
-        block_sum<2>(acc, lds);
-        if (tid == 0) {
-            a.parts[2 * b] = acc[0];
-            a.parts[2 * b + 1] = acc[1];
-        }
-    }
+    spmv_store_dots(a, b, acc, lds);
 }
 
 // rows spanning several tiles: one wavefront per row adds tails[t] + heads[t+1 .. last] (fixed tree)
@@ -686,15 +541,9 @@ __global__ __launch_bounds__(kBlock) void k_spmv_tiles_fix(SpmvArgs a, const int
         double sum = 0.0;
         for (int q = t + 1 + lane; q <= last; q += 64) sum += heads[q];
         sum = wave_sum(sum);
-        if (lane == 0) spmv_finish_row(a, row, tails[t] + sum, acc);
+        if (lane == 0) spmv_finish_row_fused(a, row, tails[t] + sum, acc);
     }
-    if (a.dot) {
-        block_sum<2>(acc, lds);
-        if (threadIdx.x == 0) {
-            a.parts[2 * (parts_off + blockIdx.x)] = acc[0];
-            a.parts[2 * (parts_off + blockIdx.x) + 1] = acc[1];
-        }
-    }
+    spmv_store_dots(a, parts_off + blockIdx.x, acc, lds);
 }
 
 // S[t] = first row r with rp[r] >= first entry of tile t (rows are rp[0..n]); flag[t] = the last row that

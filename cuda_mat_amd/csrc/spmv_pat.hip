@@ -271,7 +271,7 @@ int pat_build(hipStream_t st, int n, int64_t nnz, const int *rp, const int *ci, 
         return rc;
     }
     // a workgroup takes tiles of 4 chunks (256 rows); tiles_per_block so that the grid stays within kSpmvGridMax and is a
-    // multiple of 8 (the XCD-aware dealing below)
+    // multiple of 8 (the XCD-aware dealing: device.h, xcd_tile)
     const long long tiles = ((long long)p.nchunks + 3) / 4;
     long long tpb = (tiles + kSpmvGridMax - 1) / kSpmvGridMax;
     if (tpb < 1) tpb = 1;
@@ -292,27 +292,14 @@ __global__ __launch_bounds__(kBlock) void k_spmv_pat(SpmvArgs a, int nchunks, in
 #pragma clang fp contract(off)      // one rounding per product and per sum, in column order (bicstab.cpp:72-77)
     __shared__ int stab[kPatMax * kPatRow];
     __shared__ double lds[8];
-    if (a.loop.st) {
-        if (a.check == CHECK_HALF) {
-            if (check_half(a.loop, a.half, lds)) return;
-        } else if (a.loop.st->state != 0) {
-            return;
-        }
-    }
+    if (spmv_enter(a, lds)) return;
     for (int i = threadIdx.x; i < npat_rows * kPatRow; i += kBlock) stab[i] = tab[i];
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int nb = gridDim.x, b = blockIdx.x;
-    // tiles dealt CYCLICALLY inside an XCD's contiguous share (see k_spmv_stream): the workgroups of one XCD sit on
-    // neighbouring tiles at any moment, so the uses of an x entry by rows i - nx, i, i + nx meet in that XCD's L2
-    const bool xcd_split = (nb & 7) == 0;
-    const int wg_per_set = xcd_split ? nb >> 3 : nb;
-    const int set = xcd_split ? (b & 7) : 0;
-    const int w = xcd_split ? (b >> 3) : b;
-    const long long set_tile0 = (long long)set * wg_per_set * tiles_per_block;
     double acc[2] = {0.0, 0.0};
     for (int t = 0; t < tiles_per_block; t++) {
-        const long long tile = set_tile0 + (long long)t * wg_per_set + w;
+        const long long tile = xcd_tile(b, nb, tiles_per_block, t);
         const long long c = tile * 4 + wave;
         if (c >= nchunks) continue;
         const long long rowl = c * kPatChunk + lane;
@@ -333,31 +320,9 @@ __global__ __launch_bounds__(kBlock) void k_spmv_pat(SpmvArgs a, int nchunks, in
                 const double prod = v[j] * xv[j];
                 sum = sum + prod;
             }
-        if (rowl < a.n) {
-            const int row = (int)rowl;
-            if (a.d) {
-                const double dx = a.d[row] * a.xd[row];
-                sum = sum + dx;
-            }
-            double out = a.alpha * sum;
-            if (a.beta != 0.0) {
-                const double by = a.beta * a.y[row];
-                out = out + by;
-            }
-            a.y[row] = out;
-            if (a.dot) {
-                acc[0] += out * a.w[row];
-                acc[1] += out * out;
-            }
-        }
+        if (rowl < a.n) spmv_finish_row_exact(a, (int)rowl, sum, acc);
     }
-    if (a.dot) {
-        block_sum<2>(acc, lds);
-        if (threadIdx.x == 0) {
-            a.parts[2 * b] = acc[0];
-            a.parts[2 * b + 1] = acc[1];
-        }
-    }
+    spmv_store_dots(a, b, acc, lds);
 }
 
 // The same with a VALUE DICTIONARY: a row's values are 8-bit indices packed into one 8- or 16-byte word (one coalesced
@@ -372,26 +337,15 @@ __global__ __launch_bounds__(kBlock) void k_spmv_pat_d(SpmvArgs a, int nchunks, 
     __shared__ int stab[kPatMax * kPatRow];
     __shared__ double dv[kDictMax];
     __shared__ double lds[8];
-    if (a.loop.st) {
-        if (a.check == CHECK_HALF) {
-            if (check_half(a.loop, a.half, lds)) return;
-        } else if (a.loop.st->state != 0) {
-            return;
-        }
-    }
+    if (spmv_enter(a, lds)) return;
     for (int i = threadIdx.x; i < npat_rows * kPatRow; i += kBlock) stab[i] = tab[i];
     dv[threadIdx.x] = dict[threadIdx.x];                 // (kBlock == kDictMax == 256)
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int nb = gridDim.x, b = blockIdx.x;
-    const bool xcd_split = (nb & 7) == 0;
-    const int wg_per_set = xcd_split ? nb >> 3 : nb;
-    const int set = xcd_split ? (b & 7) : 0;
-    const int w = xcd_split ? (b >> 3) : b;
-    const long long set_tile0 = (long long)set * wg_per_set * tiles_per_block;
     double acc[2] = {0.0, 0.0};
     for (int t = 0; t < tiles_per_block; t++) {
-        const long long tile = set_tile0 + (long long)t * wg_per_set + w;
+        const long long tile = xcd_tile(b, nb, tiles_per_block, t);
         const long long c = tile * 4 + wave;
         if (c >= nchunks) continue;
         const long long rowl = c * kPatChunk + lane;
@@ -411,31 +365,9 @@ __global__ __launch_bounds__(kBlock) void k_spmv_pat_d(SpmvArgs a, int nchunks, 
                 const double prod = dv[(word[j >> 3] >> (8 * (j & 7))) & 0xffull] * xv[j];
                 sum = sum + prod;
             }
-        if (rowl < a.n) {
-            const int row = (int)rowl;
-            if (a.d) {
-                const double dx = a.d[row] * a.xd[row];
-                sum = sum + dx;
-            }
-            double out = a.alpha * sum;
-            if (a.beta != 0.0) {
-                const double by = a.beta * a.y[row];
-                out = out + by;
-            }
-            a.y[row] = out;
-            if (a.dot) {
-                acc[0] += out * a.w[row];
-                acc[1] += out * out;
-            }
-        }
+        if (rowl < a.n) spmv_finish_row_exact(a, (int)rowl, sum, acc);
     }
-    if (a.dot) {
-        block_sum<2>(acc, lds);
-        if (threadIdx.x == 0) {
-            a.parts[2 * b] = acc[0];
-            a.parts[2 * b + 1] = acc[1];
-        }
-    }
+    spmv_store_dots(a, b, acc, lds);
 }
 
 int launch_spmv_pat(hipStream_t st, const PatPlan &p, const SpmvArgs &a)

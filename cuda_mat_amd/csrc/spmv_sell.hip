@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "device.h"
 #include "spmv_sell.h"
 
 namespace cm {
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv_sell(SpmvArgs a, int nchunks, i
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int c0 = blockIdx.x * chunks_per_block;
     const int c1 = c0 + chunks_per_block < nchunks ? c0 + chunks_per_block : nchunks;
-    double acc0 = 0.0, acc1 = 0.0;
+    double acc[2] = {0.0, 0.0};
     for (int c = c0 + wave; c < c1; c += kBlock / kChunk) {
         const int row = perm[(size_t)c * kChunk + lane], l = len[(size_t)c * kChunk + lane];
         const long long base = chunk_off[c] * kChunk + lane;
@@ -188,32 +189,17 @@ __global__ __launch_bounds__(kBlock) void k_spmv_sell(SpmvArgs a, int nchunks, i
                 const double prod = sval[base + (long long)j * kChunk] * a.x[scol[base + (long long)j * kChunk]];
                 sum = sum + prod;
             }
-        if (row >= 0) {
-            if (a.d) {
-                const double dx = a.d[row] * a.xd[row];
-                sum = sum + dx;
-            }
-            double out = a.alpha * sum;
-            if (a.beta != 0.0) {
-                const double by = a.beta * a.y[row];
-                out = out + by;
-            }
-            a.y[row] = out;
-            if (a.dot) {
-                acc0 += out * a.w[row];
-                acc1 += out * out;
-            }
-        }
+        if (row >= 0) spmv_finish_row_exact(a, row, sum, acc);
     }
     if (a.dot) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
-            acc0 += __shfl_xor(acc0, o, 64);
-            acc1 += __shfl_xor(acc1, o, 64);
+            acc[0] += __shfl_xor(acc[0], o, 64);
+            acc[1] += __shfl_xor(acc[1], o, 64);
         }
         if (lane == 0) {
-            red[2 * wave] = acc0;
-            red[2 * wave + 1] = acc1;
+            red[2 * wave] = acc[0];
+            red[2 * wave + 1] = acc[1];
         }
         __syncthreads();
         if (threadIdx.x == 0) {

@@ -150,6 +150,85 @@ def test_spmv_bit_exact_on_integer_data(ctx, oracle, golden_dir, name, lanes, sw
     np.testing.assert_array_equal(dy.download(), oracle.csrmv(A, 1.0, x, 1.0, x * d))
 
 
+# ---- which rounding the row epilogue of every SpMV form uses (csrc/device.h; mirrors and inputs: test_spmv_rounding.py)
+@pytest.mark.parametrize("form", ["lanes2", "lanes16", "lanes64", "stream", "tiles"])
+def test_epilogue_rounding_standalone_spmv(ctx, sw, form):
+    """y = alpha (A x + d .* x) + beta y0 with real alpha, beta, d, y0 on integer A and x (exact row sums): every kernel of
+    spmv_csr.hip gives fma(beta, y0, fl(alpha * fma(d, x, s))) bit for bit -- and that is not what separate roundings give."""
+    import test_spmv_rounding as R
+    c = R.case("poisson" if form == "stream" else "rand")
+    R.assert_not_vacuous(c)
+    if form.startswith("lanes"):
+        sw("SPMV_LANES", form[5:])           # k_spmv<L>
+    elif form == "tiles":
+        sw("SPMV_FORM", "tiles")             # k_spmv_tiles (+ k_spmv_tiles_fix); "stream": rows of 5 take k_spmv_stream
+    A = c["A"]
+    rp, ci, v = _dev_csr(ctx, A)
+    dx, dd, dy = ctx.array(c["x"]), ctx.array(c["d"]), ctx.array(c["y0"])
+    ctx.spmv(A.n, rp, ci, v, A.base, dx, dy, alpha=R.ALPHA, beta=R.BETA, d=dd)
+    y = dy.download()
+    for a in (rp, ci, v, dx, dd, dy):
+        a.free()
+    print(form, "differs from fused in", R.differing(y, c["fused"]), "rows, from exact in", R.differing(y, c["exact"]))
+    np.testing.assert_array_equal(y, c["fused"])
+
+
+@pytest.mark.parametrize("form,which,mode,vdict,kernel,mirror", [
+    ("stream_c", "poisson", "csr", "0", "k_spmv_stream_c<", "fused"),
+    ("stream_d", "poisson_dict", "csr", None, "k_spmv_stream_d<", "fused"),
+    ("pat", "poisson", "pat", "0", "k_spmv_pat<", "exact"),
+    ("pat_d", "poisson_dict", "pat", None, "k_spmv_pat_d<", "exact"),
+    ("sell", "rand", "sell", None, "k_spmv_sell", "exact"),
+    ("blocked", "rand", "pb", None, "k_pb_phase1", "exact"),
+])
+def test_epilogue_rounding_of_a_shifted_solver_spmv(cm, ctx, sw, form, which, mode, vdict, kernel, mirror):
+    """y = (A0 + I d) x through a solver (set_shift): the forms in spmv_csr.hip give fma(d, x, s); the pattern, SELL and
+    blocked forms round d x and the sum separately (the oracle's csrmv).  The bits of a shifted product follow the form."""
+    import test_spmv_rounding as R
+    c = R.case(which)
+    R.assert_not_vacuous(c)
+    sw("SPMV_MODE", mode)
+    if vdict is not None:
+        sw("VALUE_DICT", vdict)
+    A = c["A"]
+    s = cm.Solver.from_host_csr(ctx, A.rowptr, A.colidx, A.val)
+    assert s.spmv_kernel().startswith(kernel), s.spmv_kernel()
+    s.set_shift(ctx.array(c["d"]))
+    dx, dy = ctx.array(c["x"]), ctx.empty(A.n)
+    s.spmv(dx, dy)
+    y = dy.download()
+    s.close()
+    fused, exact = c["fused_shift"][:, 0], c["exact_shift"]
+    print(form, "differs from fused in", R.differing(y, fused), "rows, from exact in", R.differing(y, exact))
+    np.testing.assert_array_equal(y, fused if mirror == "fused" else exact)
+
+
+@pytest.mark.parametrize("K", [1, 2, 8])
+def test_epilogue_rounding_spmm(cm, ctx, sw, K):
+    """k_spmm_csr, with the solver's one shift and with a shift per column: column j is fma(d_j, x_j, s_j), the fused
+    epilogue of k_spmv<L>"""
+    import test_spmv_rounding as R
+    c = R.case("rand")
+    R.assert_not_vacuous(c, columns=range(K))
+    sw("SPMV_MODE", "csr")
+    A, n = c["A"], c["n"]
+    s = cm.Solver.from_host_csr(ctx, A.rowptr, A.colidx, A.val)
+    assert s.spmv_kernel().startswith("k_spmv<"), s.spmv_kernel()
+    s.set_shift(ctx.array(c["d"]))
+    dX = ctx.array(np.asfortranarray(c["X"][:, :K]).ravel(order="F"))
+    dD = ctx.array(np.asfortranarray(c["D"][:, :K]).ravel(order="F"))
+    dY = ctx.empty(n * K)
+    s.spmm(K, dX, n, dY, n)
+    y_shift = dY.download().reshape((n, K), order="F")
+    s.spmm_shifts(K, dX, n, dD, n, dY, n)
+    y_shifts = dY.download().reshape((n, K), order="F")
+    s.close()
+    print("K", K, "one shift: differs from fused in", R.differing(y_shift, c["fused_shift"][:, :K]), "entries; per-column shifts:",
+          R.differing(y_shifts, c["fused_shifts"][:, :K]))
+    np.testing.assert_array_equal(y_shift, c["fused_shift"][:, :K])
+    np.testing.assert_array_equal(y_shifts, c["fused_shifts"][:, :K])
+
+
 def test_spmv_real_data_tolerance(ctx, oracle, golden_dir):
     """real-valued data: |y - y_ref| <= 4 nnz_row eps sum|a_ij x_j|"""
     A = oracle.rand_rows(20000, 50, 3)
