@@ -15,8 +15,8 @@
 //                       residency is throttled when the work per level is small (pollers slow the hand-offs);
 //   * hybrid split      big factors with scattered columns: entries whose column lies in an EARLIER group go
 //                       through one blocked two-phase SpMV per group (streams), only the rest is gathered;
-//   * k_trsv_lds        n <= 16384 with narrow levels: one workgroup, solution vector in LDS, barrier per level;
-//   * k_trsv_level / k_trsv_small_levels   one launch per level / one single-workgroup launch per run of small
+//   * k_trsm_lds<L, 1>  n <= 16384 with narrow levels: one workgroup, solution vector in LDS, barrier per level;
+//   * k_trsm_level<L, 1> / k_trsm_small_levels<L, 1>   one launch per level / one single-workgroup launch per run of small
 //                       levels -- the reference form the others are bit-identical to, and the fallback when a
 //                       dependency-driven solve times out (another spinning kernel on the same GPU).
 // Block-Jacobi (row-sharded runs): the same machinery on the rank's diagonal block (select_precond_matrix).

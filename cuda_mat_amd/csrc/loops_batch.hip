@@ -14,7 +14,7 @@
 // (Solve::iterate_reference per column, pbicgstab.cu:92-98, :116, :121-127):
 //   k_update_p_b | ph = U^-1 L^-1 p | SpMM v = A ph (+ rw.v) | k_half_b | half-step tests | sh = U^-1 L^-1 r |
 //   SpMM t = A sh (+ t.r, t.t) | k_full_b(x, sv = sh, r, t, rw, pw = ph)
-// with the multi-column triangular solves of trsm.hip: one gathered index yields K doubles, one level hop serves K columns, the
+// with the multi-column triangular solves of trsv.hip: one gathered index yields K doubles, one level hop serves K columns, the
 // factors are read once.  The half-step tests get a launch of their own (they must be decided before sh is computed).  The
 // triangular solves write ph, sh and a scratch block only, for every column of the block: a stopped column's x, r, p and history
 // keep their bits, and its ph -- which a half-step exit still owes to x -- is recomputed from its frozen p to the same bits.

@@ -23,7 +23,7 @@ struct TriFactor {                 // one triangular factor in level-major stora
     int *row_of = nullptr;         // device: original row id of permuted row
     double *dinv = nullptr;        // device: 1/diag in permuted order (upper only)
     int64_t nnz = 0;
-    // index spaces of a solve (trsv.hip trsv_rows): permuted row pr reads rhs[rhs_of[pr]], writes out[out_of[pr]]
+    // index spaces of a solve (trsv.hip tri_rows): permuted row pr reads rhs[rhs_of[pr]], writes out[out_of[pr]]
     // (nullptr = pr itself); `ci` holds indices into out.  Original space: both = row_of.  Level-major space (lm,
     // hybrid factors): out_of = nullptr; rhs_of = nullptr for L, the U-position -> L-position map (owned) for U.
     int *rhs_of = nullptr, *out_of = nullptr;

@@ -1,7 +1,8 @@
-// trsm.h -- the ILU(0) factors applied to K interleaved columns at once (internal API, trsm.hip).
+// trsm.h -- the ILU(0) factors applied to K interleaved columns at once (internal API, trsv.hip).
 //
-// Vectors are laid out as in batch.h: n rows x K columns row-major, K in {1, 2, 4, 8}.  Column j of every solve here is
-// bit-identical to trsv_apply (trsv.hip) on column j alone, whatever K is and whatever the other columns hold.
+// Vectors are laid out as in batch.h: n rows x K columns row-major, K in {1, 2, 4, 8}.  The kernels are the ones trsv_apply
+// launches at K = 1 (one implementation, trsv.hip), so column j of every solve here is bit-identical to trsv_apply on
+// column j alone, whatever K is and whatever the other columns hold.
 #pragma once
 #include "solver.h"
 

@@ -1,65 +1,108 @@
 // trsv.hip -- application of the ILU(0) factors: t = L^-1 y (unit diagonal), U^-1 t (cusparseDcsrsv_solve x4 per
-// iteration, pbicgstab.cu:92-98,:121-127).  The forms and when each is taken are described at the top of ilu.hip.
+// iteration, pbicgstab.cu:92-98,:121-127), for one vector (trsv_apply) and for K interleaved columns (trsm.h: the batched
+// loop of loops_batch.hip, cudamat_solver_precond_apply_many).  The forms and when each is taken are described at the top
+// of ilu.hip.
+//
+// The level-scheduled forms are ONE kernel family templated on the lanes per row and on the columns K in {1, 2, 4, 8}:
+//   * k_trsm_level<LANES, K>         one launch per wide level
+//   * k_trsm_small_levels<LANES, K>  a run of narrow levels in one workgroup (workgroup-scope fence + barrier per level)
+//   * k_trsm_lds<LANES, K>           the whole solve in one workgroup with the n x K block in LDS, when n K 8 bytes fit the
+//                                    128 KiB the single-column form asks for and the factor's levels are narrow (TriHost::lds)
+// A single vector is the K = 1 instantiation, so column j of a K-column solve is bit-identical to the single-column solve
+// of column j by construction: lane k of a row's team takes entries k, k + LANES, ..., every column keeps its own partial
+// sum, the same xor tree per column, one rounding per operation, no atomics -- and the grid and the row partition depend on
+// the factor only, never on K: a column's bits do not depend on the batch it sits in.  With the columns interleaved
+// (V[i*K + j], batch.h) one gathered column index yields K contiguous doubles (dwordx4 loads for K >= 2), one level hop
+// serves K columns, and the factor's indices and values (12 B per entry) are read once instead of K times.
+// Every column of the block is computed (padding columns of a short batch too: plain arithmetic on whatever they hold, NaN
+// or Inf included); the callers never copy a padding column back.
+//
+// Single-column only: the dependency-driven k_trsv_syncfree.  Its protocol publishes one 8-byte value per row; a K-wide row
+// would be K publications read by 16-byte loads, which needs an argument about tearing that has not been made.  Also not
+// covered by the multi-column path (trsm_covered; the callers then run column by column): hybrid factors in level-major
+// spaces (TriFactor::lm -- their far parts are blocked SpMVs without a multi-column form), block-Jacobi ILU(0), sharded
+// solvers.
+#include <stdio.h>
+
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
+#include "batch.h"
+#include "device.h"
 #include "ilu.h"
+#include "trsm.h"
 
 using namespace cm;
 
 namespace cm {
 
 // ---------------------------------------------------------------- triangular solves
-// out[o(pr)] = (rhs[i(pr)] - sum_k val[k] out[col[k]]) * dinv   for the permuted rows [r0, r1).
+// out[o(pr)][j] = (rhs[i(pr)][j] - sum_k val[k] out[col[k]][j]) * dinv   for the permuted rows [r0, r1), K columns.
 // Index spaces: a permuted row pr reads rhs at rhs_of[pr] and writes out at out_of[pr] (a nullptr map = pr itself);
 // the stored columns are indices into `out`.  Factors in ORIGINAL index space have rhs_of = out_of = row_of; factors
 // in LEVEL-MAJOR space (hybrid, TriFactor::lm) have out_of = nullptr -- the solve writes a contiguous stream -- and
 // rhs_of = nullptr (L: the right-hand side is in L's space) or the U-position -> L-position map (U).
-// LANES lanes per row, exactly the SpMV inner loop; rows of one level are independent.
-template <int LANES>
-__device__ __forceinline__ void trsv_rows(int r0, int r1, int first, int stride, const int *frp, const int *fci,
-                                          const double *fval, const int *rhs_of, const int *out_of, const double *dinv,
-                                          const double *far, const double *rhs, double *out)
+// LANES lanes per row, exactly the SpMV inner loop; rows of one level are independent.  far (K = 1 only: hybrid factors
+// have no multi-column form) holds the entries whose column lies in an earlier group.
+template <int LANES, int K>
+__device__ __forceinline__ void tri_rows(int r0, int r1, int first, int stride, const int *frp, const int *fci,
+                                         const double *fval, const int *rhs_of, const int *out_of, const double *dinv,
+                                         const double *far, const double *rhs, double *out)
 {
     const int lane = threadIdx.x & (LANES - 1);
     for (int pr = r0 + first; pr < r1; pr += stride) {
         const int s = frp[pr], e = frp[pr + 1];
-        double sum = 0.0;
-        for (int k = s + lane; k < e; k += LANES) sum += fval[k] * out[fci[k]];
+        double sum[K];
 #pragma unroll
-        for (int o = LANES / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+        for (int j = 0; j < K; j++) sum[j] = 0.0;
+        for (int k = s + lane; k < e; k += LANES) {
+            const double a = fval[k];
+            double xv[K];
+            load_row<K>(out, fci[k], xv);
+#pragma unroll
+            for (int j = 0; j < K; j++) sum[j] += a * xv[j];
+        }
+#pragma unroll
+        for (int j = 0; j < K; j++) sum[j] = group_sum<LANES>(sum[j]);
         if (lane == 0) {
-            double v = rhs[rhs_of ? rhs_of[pr] : pr] - sum;
-            if (far) v -= far[pr];              // entries whose column lies in an earlier group
-            if (dinv) v *= dinv[pr];
-            out[out_of ? out_of[pr] : pr] = v;
+            double v[K];
+            load_row<K>(rhs, rhs_of ? rhs_of[pr] : pr, v);
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                v[j] = v[j] - sum[j];
+                if constexpr (K == 1) {
+                    if (far) v[j] -= far[pr];
+                }
+                if (dinv) v[j] *= dinv[pr];
+            }
+            store_row<K>(out, out_of ? out_of[pr] : pr, v, kAll);
         }
     }
 }
 
-template <int LANES>
-__global__ __launch_bounds__(kBlock) void k_trsv_level(int r0, int r1, const int *frp, const int *fci,
-                                                       const double *fval, const int *rhs_of, const int *out_of,
-                                                       const double *dinv, const double *far, const double *rhs,
-                                                       double *out)
+template <int LANES, int K>
+__global__ __launch_bounds__(kBlock) void k_trsm_level(int r0, int r1, const int *frp, const int *fci, const double *fval,
+                                                       const int *rhs_of, const int *out_of, const double *dinv,
+                                                       const double *far, const double *rhs, double *out)
 {
     constexpr int RPB = kBlock / LANES;
-    trsv_rows<LANES>(r0, r1, blockIdx.x * RPB + threadIdx.x / LANES, gridDim.x * RPB, frp, fci, fval, rhs_of, out_of,
-                     dinv, far, rhs, out);
+    tri_rows<LANES, K>(r0, r1, blockIdx.x * RPB + threadIdx.x / LANES, gridDim.x * RPB, frp, fci, fval, rhs_of, out_of,
+                       dinv, far, rhs, out);
 }
 
 // several consecutive small levels in ONE workgroup: a workgroup-scope fence + barrier publishes a
 // level's results (same CU, same L1) to the threads that consume them in the next level.
-template <int LANES>
-__global__ __launch_bounds__(kBlock) void k_trsv_small_levels(int l0, int l1, const int *level_ptr,
-                                                              const int *frp, const int *fci, const double *fval,
-                                                              const int *rhs_of, const int *out_of, const double *dinv,
-                                                              const double *far, const double *rhs, double *out)
+template <int LANES, int K>
+__global__ __launch_bounds__(kBlock) void k_trsm_small_levels(int l0, int l1, const int *level_ptr, const int *frp,
+                                                              const int *fci, const double *fval, const int *rhs_of,
+                                                              const int *out_of, const double *dinv, const double *far,
+                                                              const double *rhs, double *out)
 {
     constexpr int RPB = kBlock / LANES;
     for (int l = l0; l < l1; l++) {
-        trsv_rows<LANES>(level_ptr[l], level_ptr[l + 1], threadIdx.x / LANES, RPB, frp, fci, fval, rhs_of, out_of, dinv,
-                         far, rhs, out);
+        tri_rows<LANES, K>(level_ptr[l], level_ptr[l + 1], threadIdx.x / LANES, RPB, frp, fci, fval, rhs_of, out_of, dinv,
+                           far, rhs, out);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __syncthreads();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -188,23 +231,25 @@ __global__ __launch_bounds__(BLOCK) void k_trsv_syncfree(int r0, int r1, const i
   }    // tickets
 }
 
-// ---- small systems (n <= 16384): the whole solve in ONE workgroup with the solution vector in LDS
+// ---- small systems (n K <= 16384): the whole solve in ONE workgroup with the n x K block in LDS
 // The level-by-level chain is then LDS read -> multiply-add -> shuffle -> LDS write -> barrier (~0.15 us per level):
-// each team's row of the NEXT level (row pointers, first entries, right-hand side, 1/diagonal) is fetched from
+// each team's row of the NEXT level (row pointers, first entries, right-hand sides, 1/diagonal) is fetched from
 // global memory before the barrier, so nothing but LDS sits between two levels (mat10000: 199 levels per factor).
-// Same per-row summation as k_trsv_level (lane k takes entries k, k + LANES, ...; xor tree) => bit-identical.
-
-template <int LANES>
-__global__ __launch_bounds__(kBlock) void k_trsv_lds(int n, int nlev, const int *level_ptr, const int *frp, const int *fci,
+// Same per-row summation as tri_rows (lane k takes entries k, k + LANES, ...; xor tree per column) => bit-identical.
+// Factors in the original index space only (row_of): a hybrid factor never takes this form.
+template <int LANES, int K>
+__global__ __launch_bounds__(kBlock) void k_trsm_lds(int n, int nlev, const int *level_ptr, const int *frp, const int *fci,
                                                      const double *fval, const int *row_of, const double *dinv,
                                                      const double *rhs, double *out)
 {
-    extern __shared__ __attribute__((aligned(16))) double xs[];       // n doubles, original row numbering
+    extern __shared__ __attribute__((aligned(16))) double xs[];       // n x K doubles, original row numbering
     constexpr int RPB = kBlock / LANES;
     const int lane = threadIdx.x & (LANES - 1), team = threadIdx.x / LANES;
-    // prefetched state of this team's first row of the coming level
     int pr = 0, s = 0, e = 0, r = 0, c = 0;
-    double a = 0.0, b = 0.0, di = 1.0;
+    double a = 0.0, di = 1.0;
+    double b[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) b[j] = 0.0;
     bool mine = false;
     auto fetch = [&](int l) {
         mine = false;
@@ -220,7 +265,7 @@ __global__ __launch_bounds__(kBlock) void k_trsv_lds(int n, int nlev, const int 
         }
         if (lane == 0) {
             r = row_of[pr];
-            b = rhs[r];
+            load_row<K>(rhs, r, b);
             if (dinv) di = dinv[pr];
         }
     };
@@ -229,33 +274,66 @@ __global__ __launch_bounds__(kBlock) void k_trsv_lds(int n, int nlev, const int 
         const int lend = level_ptr[l + 1];
         const bool have = mine;
         const int pr0 = pr, s0 = s, e0 = e, r0 = r;
-        const double b0 = b, di0 = di;
-        double sum = 0.0;
+        const double di0 = di;
+        double b0[K], sum[K];
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            b0[j] = b[j];
+            sum[j] = 0.0;
+        }
         if (have) {
-            if (s0 + lane < e0) sum = a * xs[c];
-            for (int k = s0 + lane + LANES; k < e0; k += LANES) sum += fval[k] * xs[fci[k]];
+            if (s0 + lane < e0) {
+                double xv[K];
+                load_row<K>(xs, c, xv);
+#pragma unroll
+                for (int j = 0; j < K; j++) sum[j] = a * xv[j];
+            }
+            for (int k = s0 + lane + LANES; k < e0; k += LANES) {
+                const double av = fval[k];
+                double xv[K];
+                load_row<K>(xs, fci[k], xv);
+#pragma unroll
+                for (int j = 0; j < K; j++) sum[j] += av * xv[j];
+            }
         }
 #pragma unroll
-        for (int o = LANES / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+        for (int j = 0; j < K; j++) sum[j] = group_sum<LANES>(sum[j]);
         if (have && lane == 0) {
-            double v = b0 - sum;
-            if (dinv) v *= di0;
-            xs[r0] = v;
-            out[r0] = v;
+            double v[K];
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                v[j] = b0[j] - sum[j];
+                if (dinv) v[j] *= di0;
+            }
+            store_row<K>(xs, r0, v, kAll);
+            store_row<K>(out, r0, v, kAll);
         }
         // further rows of a level wider than the workgroup's teams
         for (int q = pr0 + RPB; have && q < lend; q += RPB) {
             const int qs = frp[q], qe = frp[q + 1];
-            double t = 0.0;
-            for (int k = qs + lane; k < qe; k += LANES) t += fval[k] * xs[fci[k]];
+            double t[K];
 #pragma unroll
-            for (int o = LANES / 2; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+            for (int j = 0; j < K; j++) t[j] = 0.0;
+            for (int k = qs + lane; k < qe; k += LANES) {
+                const double av = fval[k];
+                double xv[K];
+                load_row<K>(xs, fci[k], xv);
+#pragma unroll
+                for (int j = 0; j < K; j++) t[j] += av * xv[j];
+            }
+#pragma unroll
+            for (int j = 0; j < K; j++) t[j] = group_sum<LANES>(t[j]);
             if (lane == 0) {
                 const int rr = row_of[q];
-                double v = rhs[rr] - t;
-                if (dinv) v *= dinv[q];
-                xs[rr] = v;
-                out[rr] = v;
+                double v[K];
+                load_row<K>(rhs, rr, v);
+#pragma unroll
+                for (int j = 0; j < K; j++) {
+                    v[j] = v[j] - t[j];
+                    if (dinv) v[j] *= dinv[q];
+                }
+                store_row<K>(xs, rr, v, kAll);
+                store_row<K>(out, rr, v, kAll);
             }
         }
         fetch(l + 1);                      // global loads of the next level overlap the barrier
@@ -281,8 +359,40 @@ static int launch_far(hipStream_t st, const TriFactor &F, const TriHost &H, int 
     return launch_spmv_pb(st, H.far[(size_t)grp], a);
 }
 
-template <int LANES>
-static int launch_trsv_segments(hipStream_t st, const TriFactor &F, const TriHost &H, const double *rhs, double *out)
+// f(std::integral_constant<int, LANES>()) for the lanes per row of a factor's plan: the one place where TriHost::lanes
+// becomes a template argument
+template <class Fn>
+static int with_lanes(int lanes, Fn &&f)
+{
+    switch (lanes) {
+    case 2:  return f(std::integral_constant<int, 2>());
+    case 4:  return f(std::integral_constant<int, 4>());
+    case 8:  return f(std::integral_constant<int, 8>());
+    case 16: return f(std::integral_constant<int, 16>());
+    case 32: return f(std::integral_constant<int, 32>());
+    default: return f(std::integral_constant<int, 64>());
+    }
+}
+
+// the same for the columns of a batch
+template <class Fn>
+static int with_cols(int K, Fn &&f)
+{
+    switch (K) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 4: return f(std::integral_constant<int, 4>());
+    case 8: return f(std::integral_constant<int, 8>());
+    }
+    set_error("triangular solve: %d columns per batch", K);
+    return CUDAMAT_ERR_ARG;
+}
+
+// the level-by-level launch plan (TriHost::seg_begin / seg_end): a wide level is its own launch, a run of narrow levels
+// one single-workgroup launch.  The grids depend on the factor only.  A hybrid factor (K = 1 only, trsm_covered) gets one
+// blocked SpMV per group for its far entries.
+template <int LANES, int K>
+static int launch_level_segments(hipStream_t st, const TriFactor &F, const TriHost &H, const double *rhs, double *out)
 {
     constexpr int RPB = kBlock / LANES;
     int cur_group = -1;
@@ -290,20 +400,30 @@ static int launch_trsv_segments(hipStream_t st, const TriFactor &F, const TriHos
         const int grp = H.seg_group.empty() ? 0 : H.seg_group[g];
         const double *far = nullptr;
         if (H.hybrid && grp > 0 && H.far[(size_t)grp].nnz > 0) {
-            if (grp != cur_group) CM_TRY(launch_far(st, F, H, grp, out));   // one blocked SpMV per group
+            if (grp != cur_group) CM_TRY(launch_far(st, F, H, grp, out));
             far = H.far_buf;
         }
         cur_group = grp;
         const int l0 = H.seg_begin[g], l1 = H.seg_end[g];
         const int r0 = F.level_ptr[(size_t)l0], r1 = F.level_ptr[(size_t)l1];
         if (segment_is_wide(F, H, g)) {
-            hipLaunchKernelGGL(k_trsv_level<LANES>, dim3(row_grid(r1 - r0, RPB)), dim3(kBlock), 0, st, r0, r1, F.rp, F.ci, F.val,
-                               F.rhs_of, F.out_of, F.dinv, far, rhs, out);
+            hipLaunchKernelGGL((k_trsm_level<LANES, K>), dim3(row_grid(r1 - r0, RPB)), dim3(kBlock), 0, st, r0, r1, F.rp, F.ci,
+                               F.val, F.rhs_of, F.out_of, F.dinv, far, rhs, out);
         } else {
-            hipLaunchKernelGGL(k_trsv_small_levels<LANES>, dim3(1), dim3(kBlock), 0, st, l0, l1, H.level_ptr_dev,
-                               F.rp, F.ci, F.val, F.rhs_of, F.out_of, F.dinv, far, rhs, out);
+            hipLaunchKernelGGL((k_trsm_small_levels<LANES, K>), dim3(1), dim3(kBlock), 0, st, l0, l1, H.level_ptr_dev, F.rp,
+                               F.ci, F.val, F.rhs_of, F.out_of, F.dinv, far, rhs, out);
         }
     }
+    return CUDAMAT_OK;
+}
+
+template <int LANES, int K>
+static int launch_lds(cudamat_solver *s, const TriFactor &F, const TriHost &H, const double *rhs, double *out)
+{
+    const size_t bytes = sizeof(double) * (size_t)s->n * (size_t)K;
+    CM_TRY(set_max_lds((const void *)k_trsm_lds<LANES, K>));
+    hipLaunchKernelGGL((k_trsm_lds<LANES, K>), dim3(1), dim3(kBlock), bytes, s->ctx->stream, s->n, F.nlevels, H.level_ptr_dev,
+                       F.rp, F.ci, F.val, F.row_of, F.dinv, rhs, out);
     return CUDAMAT_OK;
 }
 
@@ -403,51 +523,13 @@ int trsv_apply(cudamat_solver *s, const TriFactor &F, bool upper, const double *
     IluPlans *pl = plans_of(s, false);
     if (!pl || !s->has_ilu) { set_error("ILU(0) factors missing"); return CUDAMAT_ERR_ARG; }
     const TriHost &H = upper ? pl->U : pl->L;
-    hipStream_t st = s->ctx->stream;
-    int rc;
-    if (H.lds && !H.syncfree) {
-        const size_t bytes = sizeof(double) * (size_t)s->n;
-#define CM_TRSV_LDS(LV)                                                                                             \
-    do {                                                                                                            \
-        CM_TRY(set_max_lds((const void *)k_trsv_lds<LV>));                                                          \
-        hipLaunchKernelGGL(k_trsv_lds<LV>, dim3(1), dim3(kBlock), bytes, st, s->n, F.nlevels, H.level_ptr_dev, F.rp, \
-                           F.ci, F.val, F.row_of, F.dinv, rhs, out);                                                \
-    } while (0)
-        switch (H.lanes) {
-        case 2:  CM_TRSV_LDS(2); break;
-        case 4:  CM_TRSV_LDS(4); break;
-        case 8:  CM_TRSV_LDS(8); break;
-        case 16: CM_TRSV_LDS(16); break;
-        case 32: CM_TRSV_LDS(32); break;
-        default: CM_TRSV_LDS(64); break;
-        }
-#undef CM_TRSV_LDS
-        CM_HIP(hipGetLastError());
-        return CUDAMAT_OK;
-    }
-    if (H.syncfree) {
-        if (rhs == out) { set_error("triangular solve: rhs and out must not alias"); return CUDAMAT_ERR_ARG; }
-        switch (H.lanes) {
-        case 2:  rc = launch_trsv_syncfree<2>(st, F, H, s->n, rhs, out, pl->err_dev); break;
-        case 4:  rc = launch_trsv_syncfree<4>(st, F, H, s->n, rhs, out, pl->err_dev); break;
-        case 8:  rc = launch_trsv_syncfree<8>(st, F, H, s->n, rhs, out, pl->err_dev); break;
-        case 16: rc = launch_trsv_syncfree<16>(st, F, H, s->n, rhs, out, pl->err_dev); break;
-        case 32: rc = launch_trsv_syncfree<32>(st, F, H, s->n, rhs, out, pl->err_dev); break;
-        default: rc = launch_trsv_syncfree<64>(st, F, H, s->n, rhs, out, pl->err_dev); break;
-        }
-        CM_TRY(rc);
-        CM_HIP(hipGetLastError());
-        return CUDAMAT_OK;
-    }
-    switch (H.lanes) {
-    case 2:  rc = launch_trsv_segments<2>(st, F, H, rhs, out); break;
-    case 4:  rc = launch_trsv_segments<4>(st, F, H, rhs, out); break;
-    case 8:  rc = launch_trsv_segments<8>(st, F, H, rhs, out); break;
-    case 16: rc = launch_trsv_segments<16>(st, F, H, rhs, out); break;
-    case 32: rc = launch_trsv_segments<32>(st, F, H, rhs, out); break;
-    default: rc = launch_trsv_segments<64>(st, F, H, rhs, out); break;
-    }
-    CM_TRY(rc);
+    if (H.syncfree && rhs == out) { set_error("triangular solve: rhs and out must not alias"); return CUDAMAT_ERR_ARG; }
+    CM_TRY(with_lanes(H.lanes, [&](auto lanes) {
+        constexpr int LANES = decltype(lanes)::value;
+        if (H.lds && !H.syncfree) return launch_lds<LANES, 1>(s, F, H, rhs, out);
+        if (H.syncfree) return launch_trsv_syncfree<LANES>(s->ctx->stream, F, H, s->n, rhs, out, pl->err_dev);
+        return launch_level_segments<LANES, 1>(s->ctx->stream, F, H, rhs, out);
+    }));
     CM_HIP(hipGetLastError());
     return CUDAMAT_OK;
 }
@@ -491,4 +573,83 @@ int precond_apply_original(cudamat_solver *s, const double *in, double *tmp, dou
     return perm_from_space(s, true, pl->perm_b, out);
 }
 
+// ---- K interleaved columns (trsm.h)
+// the single-workgroup form: the factor's levels are narrow (TriHost::lds, decided at set-up for the single-column form) and
+// the K-column block fits the LDS that form asks for
+static bool takes_lds(const cudamat_solver *s, const TriHost &H, int K)
+{
+    return H.lds && (size_t)s->n * (size_t)K <= (size_t)kLdsTrsvRows;
+}
+
+bool trsm_covered(cudamat_solver *s)
+{
+    IluPlans *pl = plans_of(s, false);
+    return pl && s->has_ilu && !s->ilu_block && !s->sharded && !s->L.lm && !s->U.lm && !pl->L.hybrid && !pl->U.hybrid &&
+           s->n_cols == s->n && s->n > 0;
+}
+
+int trsm_form_code(cudamat_solver *s, bool upper, int K)
+{
+    IluPlans *pl = plans_of(s, false);
+    if (!pl || !s->has_ilu) return 0;
+    return takes_lds(s, upper ? pl->U : pl->L, K) ? 2 : 0;
+}
+
+int trsm_apply(cudamat_solver *s, const TriFactor &F, bool upper, int K, const double *rhs, double *out)
+{
+    IluPlans *pl = plans_of(s, false);
+    if (!pl || !trsm_covered(s)) { set_error("ILU(0) factors missing or not covered by the multi-column solves"); return CUDAMAT_ERR_ARG; }
+    if (rhs == out) { set_error("triangular solve: rhs and out must not alias"); return CUDAMAT_ERR_ARG; }
+    const TriHost &H = upper ? pl->U : pl->L;
+    CM_TRY(with_lanes(H.lanes, [&](auto lanes) {
+        return with_cols(K, [&](auto cols) {
+            constexpr int LANES = decltype(lanes)::value, KC = decltype(cols)::value;
+            if (takes_lds(s, H, KC)) return launch_lds<LANES, KC>(s, F, H, rhs, out);
+            return launch_level_segments<LANES, KC>(s->ctx->stream, F, H, rhs, out);
+        });
+    }));
+    CM_HIP(hipGetLastError());
+    return CUDAMAT_OK;
+}
+
+int precond_apply_b(cudamat_solver *s, int K, const double *in, double *tmp, double *out)
+{
+    CM_TRY(trsm_apply(s, s->L, false, K, in, tmp));     // pbicgstab.cu:92-94 / :121-123
+    CM_TRY(trsm_apply(s, s->U, true, K, tmp, out));     // pbicgstab.cu:96-98 / :125-127
+    return CUDAMAT_OK;
+}
+
 }  // namespace cm
+
+// the kernels a multi-column application of the factors launches, as a kernel trace shows them
+extern "C" int cudamat_solver_trsm_kernel(cudamat_solver *s, int nrhs, char *name, int cap)
+{
+    CM_ARG(s && name && cap > 0, "null pointer");
+    CM_ARG(nrhs >= 1, "nrhs < 1");
+    CM_ARG(s->has_ilu, "call cudamat_solver_ilu0 first");
+    name[0] = 0;
+    if (!trsm_covered(s)) return CUDAMAT_OK;          // "": the factors run column by column (trsv_apply)
+    IluPlans *pl = plans_of(s, false);
+    const int K = pow2_cols(nrhs);
+    int used = 0;
+    for (int u = 0; u < 2 && used < cap; u++) {
+        const TriHost &H = u ? pl->U : pl->L;
+        const TriFactor &F = u ? s->U : s->L;
+        used += snprintf(name + used, (size_t)(cap - used), "%s", u ? "; U: " : "L: ");
+        if (used >= cap) break;
+        if (takes_lds(s, H, K)) {
+            used += snprintf(name + used, (size_t)(cap - used), "k_trsm_lds<%d, %d>", H.lanes, K);
+            continue;
+        }
+        bool big = false, small = false;
+        for (size_t g = 0; g < H.seg_begin.size(); g++) {
+            const bool b = segment_is_wide(F, H, g);
+            big = big || b;
+            small = small || !b;
+        }
+        if (big) used += snprintf(name + used, (size_t)(cap - used), "k_trsm_level<%d, %d>", H.lanes, K);
+        if (big && small && used < cap) used += snprintf(name + used, (size_t)(cap - used), " + ");
+        if (small && used < cap) used += snprintf(name + used, (size_t)(cap - used), "k_trsm_small_levels<%d, %d>", H.lanes, K);
+    }
+    return CUDAMAT_OK;
+}

@@ -6,7 +6,7 @@ roofline (bytes = 12 nnz + 4 (n + 1) + 8 K (n_cols + n)), and the form MANY_FORM
     python scripts/many_rhs_bench.py [--c4]        (--c4 adds the 1e7 x 50 random system, ~35 GB of device memory)
 
 --precond ilu0: the same comparison for the preconditioned loop -- MANY_PRECOND = batched (multi-column triangular solves,
-csrc/trsm.hip) against K sequential Solver.solve calls with ILU(0), on mat10000, the 4000 x 2500 stencil and a random
+csrc/trsv.hip) against K sequential Solver.solve calls with ILU(0), on mat10000, the 4000 x 2500 stencil and a random
 2e5 x 50 system (TRSV_HYBRID = 0 throughout: hybrid factors are not covered by the batched form), and what MANY_PRECOND = auto
 picks.  --sequential-only measures just the K sequential solves and uses nothing newer than Solver.solve, so the same file
 can be run against an older build of the library to take the sequential figure there.

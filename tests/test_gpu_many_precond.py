@@ -1,4 +1,4 @@
-"""Several right-hand sides with ILU(0): the multi-column triangular solves (cudamat_solver_precond_apply_many, csrc/trsm.hip)
+"""Several right-hand sides with ILU(0): the multi-column triangular solves (cudamat_solver_precond_apply_many, csrc/trsv.hip)
 bit for bit against the single-column ones and against the oracle's substitutions, the preconditioned batched loop
 (MANY_PRECOND = batched) against the oracle column by column, the independence of a column from the batch it is solved in,
 freeze on exit per column, the column-by-column fall-backs, the form choice and the host-pointer entry point.

@@ -864,13 +864,24 @@ def _chain_matrix(oracle, n, width, seed):
     return oracle.Csr(n, S.indptr.astype(np.int32), S.indices.astype(np.int32), S.data.copy(), n)
 
 
-@pytest.mark.parametrize("name", ["chain3000", "poisson160x90", "rand20000x50", "rand20000x50_hybrid", "longrows",
-                                  "mat10000"])
-def test_dependency_driven_trsv_equals_level_solve(cm, ctx, oracle, golden_dir, name, sw):
+@pytest.mark.parametrize("name, lanes", [
+    pytest.param(name, None, id=name)
+    for name in ("chain3000", "poisson160x90", "rand20000x50", "rand20000x50_hybrid", "longrows", "mat10000")
+] + [
+    pytest.param("poisson160x90", 2, id="poisson160x90-lanes2"),
+    pytest.param("longrows", 64, id="longrows-lanes64"),
+    pytest.param("wide", None, id="wide"),
+])
+def test_dependency_driven_trsv_equals_level_solve(cm, ctx, oracle, golden_dir, name, lanes, sw):
     """k_trsv_syncfree (one launch per group, rows wait for their dependencies' values) against the
-    level-by-level kernels on the same factors: every row is summed by the same lanes in the same order,
+    level-by-level kernels (the K = 1 instantiations of k_trsm_level / k_trsm_small_levels / k_trsm_lds) on the same
+    factors: every row is summed by the same lanes in the same order,
     so L^-1 U^-1 must be BIT-identical -- deep chains inside one wavefront (chain3000: every row waits for
-    the previous one), wavefront-shaped levels (Poisson), scattered rows, the hybrid far/near split."""
+    the previous one), wavefront-shaped levels (Poisson), scattered rows, the hybrid far/near split, the lane
+    counts at both ends pinned with TRSV_LANES (2 on Poisson, 64 on the 60 % dense rows, whatever the row-length rule
+    picks), and levels of 3000 rows ("wide": k_trsm_level<L, 1> on several workgroups, then a run of narrow levels)."""
+    if lanes:
+        sw("TRSV_LANES", str(lanes))
     if name == "chain3000":
         A = _chain_matrix(oracle, 3000, 2, 3)
     elif name == "poisson160x90":
@@ -879,6 +890,9 @@ def test_dependency_driven_trsv_equals_level_solve(cm, ctx, oracle, golden_dir, 
         A = oracle.rand_rows(20000, 50, 0x5EED)
     elif name == "longrows":
         A = _real_sparse(oracle, 400, 0.6, 5)
+    elif name == "wide":
+        from tests.test_gpu_many_precond import _wide_levels
+        A = _wide_levels(oracle)
     else:
         A = _load(oracle, golden_dir, name)
     sw("TRSV_HYBRID", "1" if name.endswith("hybrid") else "0")
@@ -1134,8 +1148,8 @@ def test_ilu0_prefetching_kernel_equals_simple_kernel(cm, ctx, oracle, golden_di
 
 @pytest.mark.parametrize("name", ["mat900", "mat10000", "chain3000", "longrows", "rand9000x30"])
 def test_lds_resident_trsv_equals_level_kernels(cm, ctx, oracle, golden_dir, name, sw):
-    """k_trsv_lds (n <= 16384: one workgroup, solution vector in LDS, next level's operands prefetched across the
-    barrier) against the level kernels with the vector in global memory: bit-identical L^-1 U^-1, and both within
+    """k_trsm_lds<L, 1> (n <= 16384: one workgroup, solution vector in LDS, next level's operands prefetched across the
+    barrier) against the level kernels (k_trsm_level / k_trsm_small_levels at K = 1) with the vector in global memory: bit-identical L^-1 U^-1, and both within
     1e-10 of the oracle's substitutions"""
     if name == "chain3000":
         A = _chain_matrix(oracle, 3000, 2, 3)
