@@ -56,7 +56,7 @@ int launch_batch_in(hipStream_t s, int K, int kc, int64_t rows, int64_t rows_out
                     double *dst);
 int launch_batch_out(hipStream_t s, int K, int kc, int64_t rows, const double *src, double *dst, int64_t ld);
 
-// the loop's vector kernels, column by column what kernels.h's single-vector forms do (same operations, same order)
+// the loop's vector kernels, column by column what kernels.h's single-vector forms do (the same steps of steps.h, in the same order)
 int launch_init_b(hipStream_t s, int K, int64_t n, const double *b, double *r, double *rw, double *p, double *parts,
                   int *nparts);
 // columns >= kc are dead: their state starts at 2 (stopped) and nothing touches them

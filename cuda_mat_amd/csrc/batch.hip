@@ -3,8 +3,9 @@
 //
 // The SpMM reads the matrix (12 B per entry) once for K columns; each entry then gathers K contiguous doubles of X (one
 // 8K-byte piece, dwordx4 loads for K >= 2) instead of one double per column and SpMV.  Every column keeps the arithmetic of
-// the single-vector kernels: the same operations in the same order (k_spmv<L>, k_init, k_update_p, k_half, k_full), so that
-// column j of k_spmm_csr<L, K> is bit-identical to k_spmv<L> on column j alone.  A thread owns whole rows (all K columns), the
+// the single-vector kernels: the vector kernels call the steps k_init, k_update_p, k_half and k_full call (steps.h), the SpMM
+// sums a row as k_spmv<L> does and finishes it with the fused epilogue (device.h), so that column j of k_spmm_csr<L, K> is
+// bit-identical to k_spmv<L> on column j alone.  A thread owns whole rows (all K columns), the
 // grid and the row partition depend on n and L only: the reduction order of a column does not depend on K.  Within a column
 // the reduction order of a ROW depends on the row's own length and L only: rows of at most 4096 entries are summed by their
 // L lanes, every longer one by the whole workgroup -- however many long rows share a partition (device.h: LongRows).
@@ -12,6 +13,8 @@
 // column; the mask is uniform over the workgroup, so the branches do not diverge).
 #include "batch.h"
 #include "device.h"
+
+#pragma clang fp contract(off)      // no product-sum here is left to the compiler: fma() is written where one rounding is meant
 
 namespace cm {
 
@@ -119,7 +122,7 @@ __global__ __launch_bounds__(kBlock) void k_spmm_csr(SpmmArgs a, int rows_per_bl
             double xv[K];
             load_row<K>(a.x, __builtin_nontemporal_load(a.ci + k), xv);
 #pragma unroll
-            for (int j = 0; j < K; j++) sum[j] += v * xv[j];
+            for (int j = 0; j < K; j++) sum[j] = fma(v, xv[j], sum[j]);
         }
 #pragma unroll
         for (int j = 0; j < K; j++) sum[j] = group_sum<L>(sum[j]);
@@ -138,7 +141,7 @@ __global__ __launch_bounds__(kBlock) void k_spmm_csr(SpmmArgs a, int rows_per_bl
                 double xv[K];
                 load_row<K>(a.x, __builtin_nontemporal_load(a.ci + k), xv);
 #pragma unroll
-                for (int j = 0; j < K; j++) part[j] += v * xv[j];
+                for (int j = 0; j < K; j++) part[j] = fma(v, xv[j], part[j]);
             }
             block_sum<K>(part, lds);
             if (threadIdx.x == 0) spmm_finish_row<K, S>(a, row, part, acc);
@@ -260,8 +263,8 @@ __global__ __launch_bounds__(kBlock) void k_init_b(int64_t n, const double *b, d
         load_row<K>(r, i, rr);
 #pragma unroll
         for (int j = 0; j < K; j++) {
-            rr[j] = bb[j] - rr[j];
-            acc[j] += rr[j] * rr[j];
+            rr[j] = step_r0(bb[j], rr[j]);
+            dot_step(acc[j], rr[j], rr[j]);
         }
         store_row<K>(r, i, rr, kAll);
         store_row<K>(rw, i, rr, kAll);
@@ -334,12 +337,12 @@ __global__ __launch_bounds__(kBlock) void k_update_p_b(BatchArgs la, const doubl
     if (!live) return;
     double sc[2 * K];
     load_parts<2 * K>(full, full_count, sc, lds);
-    double beta[K], nomega[K];
+    double beta[K], omega[K];
     unsigned upd = 0;
 #pragma unroll
     for (int j = 0; j < K; j++) {
         beta[j] = 0.0;
-        nomega[j] = 0.0;
+        omega[j] = 0.0;
         if (!(live & (1u << j))) continue;
         LoopState *st = la.st + j;
         const int it = st->it;
@@ -347,11 +350,10 @@ __global__ __launch_bounds__(kBlock) void k_update_p_b(BatchArgs la, const doubl
         if (check_full(col_args(la, j), two)) continue;
         const double rho = two[0];                             // :81
         const double rhop = st->rho[(it + 1) & 1];             // :80
-        const double alpha = st->alpha, omega = st->omega;
         if (leader()) st->rho[it & 1] = rho;
         if (it == 0) continue;                                 // :83  p = r already (:73)
-        beta[j] = (rho / rhop) * (alpha / omega);              // :84
-        nomega[j] = -omega;
+        omega[j] = st->omega;
+        beta[j] = step_beta(rho, rhop, st->alpha, omega[j]);
         upd |= 1u << j;
     }
     if (!upd) return;
@@ -362,11 +364,7 @@ __global__ __launch_bounds__(kBlock) void k_update_p_b(BatchArgs la, const doubl
         load_row<K>(v, i, vv);
         load_row<K>(p, i, pp);
 #pragma unroll
-        for (int j = 0; j < K; j++) {
-            double q = fma(nomega[j], vv[j], pp[j]);          // :86
-            q = beta[j] * q;                                   // :87
-            pp[j] = rr[j] + q;                                 // :88
-        }
+        for (int j = 0; j < K; j++) pp[j] = step_p(rr[j], pp[j], vv[j], beta[j], omega[j]);
         store_row<K>(p, i, pp, upd);
     }
 }
@@ -388,15 +386,14 @@ __global__ __launch_bounds__(kBlock) void k_half_b(BatchArgs la, const double *r
     if (!live) return;
     double sc[2 * K];
     load_parts<2 * K>(rv, rv_count, sc, lds);
-    double nalpha[K];
+    double alpha[K];
 #pragma unroll
     for (int j = 0; j < K; j++) {
-        nalpha[j] = 0.0;
+        alpha[j] = 0.0;
         if (!(live & (1u << j))) continue;
         LoopState *st = la.st + j;
-        const double alpha = st->rho[st->it & 1] / sc[2 * j];  // :107
-        nalpha[j] = -alpha;
-        if (leader()) st->alpha = alpha;
+        alpha[j] = step_alpha(st->rho[st->it & 1], sc[2 * j]);
+        if (leader()) st->alpha = alpha[j];
     }
     double acc[K];
 #pragma unroll
@@ -408,8 +405,8 @@ __global__ __launch_bounds__(kBlock) void k_half_b(BatchArgs la, const double *r
         load_row<K>(v, i, vv);
 #pragma unroll
         for (int j = 0; j < K; j++) {
-            rr[j] = fma(nalpha[j], vv[j], rr[j]);              // :109
-            acc[j] += rr[j] * rr[j];                           // :111
+            rr[j] = step_r_half(rr[j], vv[j], alpha[j]);
+            dot_step(acc[j], rr[j], rr[j]);                    // :111
         }
         store_row<K>(r, i, rr, live);
     }
@@ -446,7 +443,7 @@ __global__ __launch_bounds__(kBlock) void k_full_b(BatchArgs la, const double *t
     double omega[K], alpha[K];
 #pragma unroll
     for (int j = 0; j < K; j++) {
-        omega[j] = sc[2 * j] / sc[2 * j + 1];                  // :137
+        omega[j] = step_omega(sc[2 * j], sc[2 * j + 1]);
         alpha[j] = (live & (1u << j)) ? la.st[j].alpha : 0.0;
     }
     double acc[2 * K];
@@ -463,11 +460,11 @@ __global__ __launch_bounds__(kBlock) void k_full_b(BatchArgs la, const double *t
         load_row<K>(x, i, xx);
 #pragma unroll
         for (int j = 0; j < K; j++) {
-            xx[j] = fma(alpha[j], pp[j], xx[j]);               // :110
-            xx[j] = fma(omega[j], ss[j], xx[j]);               // :139
-            rr[j] = fma(-omega[j], tv[j], rr[j]);              // :140
-            acc[2 * j] += ww[j] * rr[j];                       // :81 of i+1
-            acc[2 * j + 1] += rr[j] * rr[j];                   // :142
+            xx[j] = step_x_half(xx[j], pp[j], alpha[j]);
+            xx[j] = step_x_full(xx[j], ss[j], omega[j]);
+            rr[j] = step_r_full(rr[j], tv[j], omega[j]);
+            dot_step(acc[2 * j], ww[j], rr[j]);                // :81 of i+1
+            dot_step(acc[2 * j + 1], rr[j], rr[j]);            // :142
         }
         store_row<K>(x, i, xx, live);
         store_row<K>(r, i, rr, live);
@@ -544,7 +541,7 @@ __global__ __launch_bounds__(kBlock) void k_half_exit_b(const LoopState *st, int
         load_row<K>(pw, i, pp);
         load_row<K>(x, i, xx);
 #pragma unroll
-        for (int j = 0; j < K; j++) xx[j] = fma(alpha[j], pp[j], xx[j]);
+        for (int j = 0; j < K; j++) xx[j] = step_x_half(xx[j], pp[j], alpha[j]);
         store_row<K>(x, i, xx, half);
     }
 }

@@ -7,6 +7,7 @@
 
 #include "batch.h"
 #include "kernels.h"
+#include "steps.h"
 
 namespace cm {
 
@@ -399,15 +400,32 @@ __device__ __forceinline__ void stream_finish_rows(const SpmvArgs &a, int r0, in
 }
 
 // ---- streaming vector kernels: 16 bytes per lane (double2) whenever every operand is 16-byte aligned
-static inline bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
+template <int W> struct Width { static constexpr int value = W; };
 
-#define COMMA ,
-#define CM_VEC_LOOP(N, BODY2, BODY1)                                                   \
-    {                                                                                  \
-        const int64_t n2__ = VEC ? (N) / 2 : 0;                                        \
-        const int64_t stride__ = (int64_t)gridDim.x * kBlock;                          \
-        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n2__; i += stride__) { BODY2 } \
-        for (int64_t i = 2 * n2__ + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < (N); i += stride__) { BODY1 } \
-    }
+// body(i, Width<W>): VEC = 1 runs it at W = 2 over the n / 2 pairs (i: the pair, load_row<2> / store_row<2> with kAll) and at
+// W = 1 over the odd tail; VEC = 0 at W = 1 over every element.  Grid-stride, and the tail after the pairs: a thread's
+// partial sums take the pairs in that order, .x before .y, then its tail element.
+template <int VEC, class Body>
+__device__ __forceinline__ void vec_loop(int64_t n, Body body)
+{
+    const int64_t n2 = VEC ? n / 2 : 0;
+    const int64_t first = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = first; i < n2; i += stride) body(i, Width<2>{});
+    for (int64_t i = 2 * n2 + first; i < n; i += stride) body(i, Width<1>{});
+}
+
+// a null pointer counts as aligned (an operand the launch does not use)
+template <class... P>
+static inline bool all_aligned16(const P *...p) { return (((((uintptr_t)p) & 15) == 0) && ...); }
+
+// Launches KERNEL -- an expression in VEC, such as k_dot<VEC> -- on grid G of stream s with VEC = 1 when ALIGNED, else 0, and
+// returns from the launcher.
+#define CM_VEC_LAUNCH(ALIGNED, G, KERNEL, ...)                                                              \
+    do {                                                                                                    \
+        if (ALIGNED) { constexpr int VEC = 1; hipLaunchKernelGGL(KERNEL, dim3(G), dim3(kBlock), 0, s, __VA_ARGS__); } \
+        else { constexpr int VEC = 0; hipLaunchKernelGGL(KERNEL, dim3(G), dim3(kBlock), 0, s, __VA_ARGS__); }         \
+        CM_HIP(hipGetLastError());                                                                          \
+        return CUDAMAT_OK;                                                                                  \
+    } while (0)
 
 }  // namespace cm

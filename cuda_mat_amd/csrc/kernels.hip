@@ -2,7 +2,8 @@
 //
 // Everything on this path is HBM-bandwidth-bound fp64 streaming / gather work (<= 0.17 flop/byte): no MFMA.
 // What matters is (a) coalesced 16-byte-per-lane loads on the streamed vectors, (b) one pass per fused update instead of
-// the reference's copy/scal/axpy triplets (pbicgstab.cu:86-88,109-110,139-140,668-672,...), (c) dot products produced by
+// the reference's copy/scal/axpy triplets (pbicgstab.cu:86-88,109-110,139-140,668-672,...; the arithmetic of each update is
+// stated once, in steps.h, and each kernel body once: vec_loop runs it pair-wide and on the tail), (c) dot products produced by
 // the kernel that already streams the operands, reduced wave64-shuffle -> LDS -> per-workgroup partial -> fixed-order
 // sum in the consumer's prologue (bitwise reproducible, no atomics, no host sync).
 // Scalars (rho, alpha, omega, norms) never leave the device: see LoopState.
@@ -14,6 +15,8 @@
 
 #include "kernels.h"
 #include "device.h"
+
+#pragma clang fp contract(off)      // no product-sum here is left to the compiler: fma() is written where one rounding is meant
 
 namespace cm {
 
@@ -87,7 +90,7 @@ __global__ __launch_bounds__(kBlock) void k_nrm2_finish(ScalarSrc sq, int64_t n,
     double acc[1] = {0.0};
     for (int64_t i = threadIdx.x; i < n; i += kBlock) {
         const double v = ldexp(x[i], -e);          // exact, but for entries below 2^-1022 max|x|: they do not count
-        acc[0] += v * v;
+        dot_step(acc[0], v, v);
     }
     block_sum<1>(acc, lds);                        // in [0.25, n)
     if (threadIdx.x == 0) out[0] = ldexp(sqrt(acc[0]), e);
@@ -118,19 +121,17 @@ __global__ __launch_bounds__(kBlock) void k_init(int64_t n, const double *b, dou
 {
     __shared__ double lds[8];
     double acc[1] = {0.0};
-    CM_VEC_LOOP(n,
-        {
-            const double2 bb = ((const double2 *)b)[i];
-            double2 rr = ((double2 *)r)[i];
-            rr.x = bb.x - rr.x; rr.y = bb.y - rr.y;        // r = f - A x (pbicgstab.cu:67-70)
-            ((double2 *)r)[i] = rr; ((double2 *)rw)[i] = rr; ((double2 *)p)[i] = rr;  // :72-73
-            acc[0] += rr.x * rr.x; acc[0] += rr.y * rr.y;
-        },
-        {
-            const double rr = b[i] - r[i];
-            r[i] = rr; rw[i] = rr; p[i] = rr;
-            acc[0] += rr * rr;
-        })
+    vec_loop<VEC>(n, [&](int64_t i, auto w) {
+        constexpr int W = decltype(w)::value;
+        double bb[W], rr[W];
+        load_row<W>(b, i, bb); load_row<W>(r, i, rr);
+#pragma unroll
+        for (int j = 0; j < W; j++) {
+            rr[j] = step_r0(bb[j], rr[j]);
+            dot_step(acc[0], rr[j], rr[j]);
+        }
+        store_row<W>(r, i, rr, kAll); store_row<W>(rw, i, rr, kAll); store_row<W>(p, i, rr, kAll);      // :72-73
+    });
     block_sum<1>(acc, lds);
     if (threadIdx.x == 0) {
         parts[2 * blockIdx.x] = acc[0];       // rho0 = rw.r = r.r
@@ -143,12 +144,7 @@ int launch_init(hipStream_t s, int64_t n, const double *b, double *r, double *rw
 {
     const int g = vec_grid(n);
     *nparts = g;
-    if (aligned16(b) && aligned16(r) && aligned16(rw) && aligned16(p))
-        hipLaunchKernelGGL(k_init<1>, dim3(g), dim3(kBlock), 0, s, n, b, r, rw, p, parts);
-    else
-        hipLaunchKernelGGL(k_init<0>, dim3(g), dim3(kBlock), 0, s, n, b, r, rw, p, parts);
-    CM_HIP(hipGetLastError());
-    return CUDAMAT_OK;
+    CM_VEC_LAUNCH(all_aligned16(b, r, rw, p), g, k_init<VEC>, n, b, r, rw, p, parts);
 }
 
 // r / n: this rank's r0, looked at only when the sum of squares is exactly 0 (NULL in a sharded run: see init_refusal)
@@ -193,7 +189,7 @@ int launch_init_finish(hipStream_t s, LoopState *st, ScalarSrc init, double tol,
     return CUDAMAT_OK;
 }
 
-// p = r + beta (p - omega v)          pbicgstab.cu:83-89 (axpy, scal, axpy) fused
+// p = r + beta (p - omega v)          pbicgstab.cu:83-89 (axpy, scal, axpy) fused: step_p
 template <int VEC>
 __global__ __launch_bounds__(kBlock) void k_update_p(LoopArgs la, ScalarSrc full, int64_t n,
                                                      const double *r, double *p, const double *v)
@@ -210,35 +206,21 @@ __global__ __launch_bounds__(kBlock) void k_update_p(LoopArgs la, ScalarSrc full
     const double alpha = st->alpha, omega = st->omega;
     if (leader()) st->rho[it & 1] = rho;
     if (it == 0) return;                                   // :83  p = r already (:73)
-    const double beta = (rho / rhop) * (alpha / omega);    // :84
-    const double nomega = -omega;
-    CM_VEC_LOOP(n,
-        {
-            const double2 rr = ((const double2 *)r)[i];
-            const double2 vv = ((const double2 *)v)[i];
-            double2 pp = ((double2 *)p)[i];
-            pp.x = fma(nomega, vv.x, pp.x); pp.y = fma(nomega, vv.y, pp.y);   // :86
-            pp.x = beta * pp.x;             pp.y = beta * pp.y;               // :87
-            pp.x = rr.x + pp.x;             pp.y = rr.y + pp.y;               // :88
-            ((double2 *)p)[i] = pp;
-        },
-        {
-            double pp = fma(nomega, v[i], p[i]);
-            pp = beta * pp;
-            p[i] = r[i] + pp;
-        })
+    const double beta = step_beta(rho, rhop, alpha, omega);
+    vec_loop<VEC>(n, [&](int64_t i, auto w) {
+        constexpr int W = decltype(w)::value;
+        double rr[W], vv[W], pp[W];
+        load_row<W>(r, i, rr); load_row<W>(v, i, vv); load_row<W>(p, i, pp);
+#pragma unroll
+        for (int j = 0; j < W; j++) pp[j] = step_p(rr[j], pp[j], vv[j], beta, omega);
+        store_row<W>(p, i, pp, kAll);
+    });
 }
 
 int launch_update_p(hipStream_t s, LoopArgs la, ScalarSrc full, int64_t n, const double *r,
                     double *p, const double *v)
 {
-    const int g = vec_grid(n);
-    if (aligned16(r) && aligned16(p) && aligned16(v))
-        hipLaunchKernelGGL(k_update_p<1>, dim3(g), dim3(kBlock), 0, s, la, full, n, r, p, v);
-    else
-        hipLaunchKernelGGL(k_update_p<0>, dim3(g), dim3(kBlock), 0, s, la, full, n, r, p, v);
-    CM_HIP(hipGetLastError());
-    return CUDAMAT_OK;
+    CM_VEC_LAUNCH(all_aligned16(r, p, v), vec_grid(n), k_update_p<VEC>, la, full, n, r, p, v);
 }
 
 // alpha = rho/(rw.v); r -= alpha v; ||r||^2     pbicgstab.cu:106-111
@@ -255,23 +237,20 @@ __global__ __launch_bounds__(kBlock) void k_half(LoopArgs la, ScalarSrc rv, int6
     const int it = st->it;
     double sc[1];
     load_scalars<1>(rv, sc, lds);
-    const double alpha = st->rho[it & 1] / sc[0];          // :107
-    const double nalpha = -alpha;
+    const double alpha = step_alpha(st->rho[it & 1], sc[0]);
     if (leader()) st->alpha = alpha;
     double acc[1] = {0.0};
-    CM_VEC_LOOP(n,
-        {
-            const double2 vv = ((const double2 *)v)[i];
-            double2 rr = ((double2 *)r)[i];
-            rr.x = fma(nalpha, vv.x, rr.x); rr.y = fma(nalpha, vv.y, rr.y);   // :109
-            ((double2 *)r)[i] = rr;
-            acc[0] += rr.x * rr.x; acc[0] += rr.y * rr.y;                     // :111
-        },
-        {
-            const double rr = fma(nalpha, v[i], r[i]);
-            r[i] = rr;
-            acc[0] += rr * rr;
-        })
+    vec_loop<VEC>(n, [&](int64_t i, auto w) {
+        constexpr int W = decltype(w)::value;
+        double vv[W], rr[W];
+        load_row<W>(v, i, vv); load_row<W>(r, i, rr);
+#pragma unroll
+        for (int j = 0; j < W; j++) {
+            rr[j] = step_r_half(rr[j], vv[j], alpha);
+            dot_step(acc[0], rr[j], rr[j]);                // :111
+        }
+        store_row<W>(r, i, rr, kAll);
+    });
     block_sum<1>(acc, lds);
     if (threadIdx.x == 0) parts[blockIdx.x] = acc[0];
 }
@@ -280,12 +259,7 @@ int launch_half(hipStream_t s, LoopArgs la, ScalarSrc rv, int64_t n, double *r, 
 {
     const int g = vec_grid(n);
     *nparts = g;
-    if (aligned16(r) && aligned16(v))
-        hipLaunchKernelGGL(k_half<1>, dim3(g), dim3(kBlock), 0, s, la, rv, n, r, v, parts);
-    else
-        hipLaunchKernelGGL(k_half<0>, dim3(g), dim3(kBlock), 0, s, la, rv, n, r, v, parts);
-    CM_HIP(hipGetLastError());
-    return CUDAMAT_OK;
+    CM_VEC_LAUNCH(all_aligned16(r, v), g, k_half<VEC>, la, rv, n, r, v, parts);
 }
 
 // omega = (t.r)/(t.t); x += omega s; r -= omega t; (rw.r, r.r); it++   pbicgstab.cu:135-151
@@ -310,58 +284,32 @@ __global__ __launch_bounds__(kBlock) void k_full(LoopArgs la, ScalarSrc tt, int6
     }
     double sc[2];
     load_scalars<2>(tt, sc, lds);
-    const double omega = sc[0] / sc[1];                    // :137
-    const double nomega = -omega;
+    const double omega = step_omega(sc[0], sc[1]);
     double acc[2] = {0.0, 0.0};
-    if (!pw) {
-        CM_VEC_LOOP(n,
-            {
-                const double2 ss = ((const double2 *)sv)[i];
-                const double2 ttv = ((const double2 *)t)[i];
-                const double2 ww = ((const double2 *)rw)[i];
-                double2 rr = ((double2 *)r)[i];
-                double2 xx = ((double2 *)x)[i];
-                xx.x = fma(omega, ss.x, xx.x);   xx.y = fma(omega, ss.y, xx.y);   // :139
-                rr.x = fma(nomega, ttv.x, rr.x); rr.y = fma(nomega, ttv.y, rr.y); // :140
-                ((double2 *)x)[i] = xx; ((double2 *)r)[i] = rr;
-                acc[0] += ww.x * rr.x; acc[0] += ww.y * rr.y;                     // :81 of i+1
-                acc[1] += rr.x * rr.x; acc[1] += rr.y * rr.y;                     // :142
-            },
-            {
-                const double ss = sv[i];
-                x[i] = fma(omega, ss, x[i]);
-                const double rr = fma(nomega, t[i], r[i]);
-                r[i] = rr;
-                acc[0] += rw[i] * rr;
-                acc[1] += rr * rr;
-            })
-    } else {
-        // the half step's x += alpha pw (:110), left out by k_half, first -- then :139: two roundings in the reference's order
-        const double alpha = st->alpha;
-        CM_VEC_LOOP(n,
-            {
-                const double2 ss = ((const double2 *)sv)[i];
-                const double2 ttv = ((const double2 *)t)[i];
-                const double2 ww = ((const double2 *)rw)[i];
-                const double2 pp = ((const double2 *)pw)[i];
-                double2 rr = ((double2 *)r)[i];
-                double2 xx = ((double2 *)x)[i];
-                xx.x = fma(alpha, pp.x, xx.x);   xx.y = fma(alpha, pp.y, xx.y);   // :110
-                xx.x = fma(omega, ss.x, xx.x);   xx.y = fma(omega, ss.y, xx.y);   // :139
-                rr.x = fma(nomega, ttv.x, rr.x); rr.y = fma(nomega, ttv.y, rr.y); // :140
-                ((double2 *)x)[i] = xx; ((double2 *)r)[i] = rr;
-                acc[0] += ww.x * rr.x; acc[0] += ww.y * rr.y;                     // :81 of i+1
-                acc[1] += rr.x * rr.x; acc[1] += rr.y * rr.y;                     // :142
-            },
-            {
-                const double ss = sv[i];
-                x[i] = fma(omega, ss, fma(alpha, pw[i], x[i]));
-                const double rr = fma(nomega, t[i], r[i]);
-                r[i] = rr;
-                acc[0] += rw[i] * rr;
-                acc[1] += rr * rr;
-            })
-    }
+    // PW: the half step's x += alpha pw (:110), left out by k_half, first -- then :139: two roundings in the reference's order
+    auto sweep = [&](auto with_pw) {
+        constexpr bool PW = decltype(with_pw)::value != 0;
+        const double alpha = PW ? st->alpha : 0.0;
+        vec_loop<VEC>(n, [&](int64_t i, auto w) {
+            constexpr int W = decltype(w)::value;
+            [[maybe_unused]] double pp[W];
+            double ss[W], tv[W], ww[W], rr[W], xx[W];
+            load_row<W>(sv, i, ss); load_row<W>(t, i, tv); load_row<W>(rw, i, ww);
+            if constexpr (PW) load_row<W>(pw, i, pp);
+            load_row<W>(r, i, rr); load_row<W>(x, i, xx);
+#pragma unroll
+            for (int j = 0; j < W; j++) {
+                if constexpr (PW) xx[j] = step_x_half(xx[j], pp[j], alpha);
+                xx[j] = step_x_full(xx[j], ss[j], omega);
+                rr[j] = step_r_full(rr[j], tv[j], omega);
+                dot_step(acc[0], ww[j], rr[j]);            // :81 of i+1
+                dot_step(acc[1], rr[j], rr[j]);            // :142
+            }
+            store_row<W>(x, i, xx, kAll); store_row<W>(r, i, rr, kAll);
+        });
+    };
+    if (pw) sweep(Width<1>{});
+    else sweep(Width<0>{});
     block_sum<2>(acc, lds);
     if (threadIdx.x == 0) {
         parts[2 * blockIdx.x] = acc[0];
@@ -379,12 +327,7 @@ int launch_full(hipStream_t s, LoopArgs la, ScalarSrc tt, int64_t n, double *x, 
 {
     const int g = vec_grid(n);
     *nparts = g;
-    if (aligned16(x) && aligned16(sv) && aligned16(r) && aligned16(t) && aligned16(rw) && (!pw || aligned16(pw)))
-        hipLaunchKernelGGL(k_full<1>, dim3(g), dim3(kBlock), 0, s, la, tt, n, x, sv, r, t, rw, parts, half, pw);
-    else
-        hipLaunchKernelGGL(k_full<0>, dim3(g), dim3(kBlock), 0, s, la, tt, n, x, sv, r, t, rw, parts, half, pw);
-    CM_HIP(hipGetLastError());
-    return CUDAMAT_OK;
+    CM_VEC_LAUNCH(all_aligned16(x, sv, r, t, rw, pw), g, k_full<VEC>, la, tt, n, x, sv, r, t, rw, parts, half, pw);
 }
 
 // ---------------------------------------------------------------- BLAS-1 pieces
@@ -394,13 +337,13 @@ __global__ __launch_bounds__(kBlock) void k_dot(int64_t n, const double *x, cons
 {
     __shared__ double lds[8];
     double acc[1] = {0.0};
-    CM_VEC_LOOP(n,
-        {
-            const double2 a = ((const double2 *)x)[i];
-            const double2 b = ((const double2 *)y)[i];
-            acc[0] += a.x * b.x; acc[0] += a.y * b.y;
-        },
-        { acc[0] += x[i] * y[i]; })
+    vec_loop<VEC>(n, [&](int64_t i, auto w) {
+        constexpr int W = decltype(w)::value;
+        double a[W], b[W];
+        load_row<W>(x, i, a); load_row<W>(y, i, b);
+#pragma unroll
+        for (int j = 0; j < W; j++) dot_step(acc[0], a[j], b[j]);
+    });
     block_sum<1>(acc, lds);
     if (threadIdx.x == 0) parts[blockIdx.x] = acc[0];
 }
@@ -410,66 +353,51 @@ int launch_dot_parts(hipStream_t s, int64_t n, const double *x, const double *y,
 {
     const int g = vec_grid(n);
     *nparts = g;
-    if (aligned16(x) && aligned16(y))
-        hipLaunchKernelGGL(k_dot<1>, dim3(g), dim3(kBlock), 0, s, n, x, y, parts);
-    else
-        hipLaunchKernelGGL(k_dot<0>, dim3(g), dim3(kBlock), 0, s, n, x, y, parts);
-    CM_HIP(hipGetLastError());
-    return CUDAMAT_OK;
+    CM_VEC_LAUNCH(all_aligned16(x, y), g, k_dot<VEC>, n, x, y, parts);
 }
 
 template <int VEC>
 __global__ __launch_bounds__(kBlock) void k_axpy(int64_t n, double alpha, const double *x, double *y)
 {
-    CM_VEC_LOOP(n,
-        {
-            const double2 a = ((const double2 *)x)[i];
-            double2 b = ((double2 *)y)[i];
-            b.x = fma(alpha, a.x, b.x); b.y = fma(alpha, a.y, b.y);
-            ((double2 *)y)[i] = b;
-        },
-        { y[i] = fma(alpha, x[i], y[i]); })
+    vec_loop<VEC>(n, [&](int64_t i, auto w) {
+        constexpr int W = decltype(w)::value;
+        double a[W], b[W];
+        load_row<W>(x, i, a); load_row<W>(y, i, b);
+#pragma unroll
+        for (int j = 0; j < W; j++) b[j] = fma(alpha, a[j], b[j]);
+        store_row<W>(y, i, b, kAll);
+    });
 }
 
 int launch_axpy(hipStream_t s, int64_t n, double alpha, const double *x, double *y)
 {
-    const int g = vec_grid(n);
-    if (aligned16(x) && aligned16(y))
-        hipLaunchKernelGGL(k_axpy<1>, dim3(g), dim3(kBlock), 0, s, n, alpha, x, y);
-    else
-        hipLaunchKernelGGL(k_axpy<0>, dim3(g), dim3(kBlock), 0, s, n, alpha, x, y);
-    CM_HIP(hipGetLastError());
-    return CUDAMAT_OK;
+    CM_VEC_LAUNCH(all_aligned16(x, y), vec_grid(n), k_axpy<VEC>, n, alpha, x, y);
 }
 
 template <int VEC>
 __global__ __launch_bounds__(kBlock) void k_scal(int64_t n, double alpha, double *x, int fill)
 {
-    CM_VEC_LOOP(n,
-        {
-            double2 a = ((double2 *)x)[i];
-            a.x = fill ? alpha : alpha * a.x; a.y = fill ? alpha : alpha * a.y;
-            ((double2 *)x)[i] = a;
-        },
-        { x[i] = fill ? alpha : alpha * x[i]; })
+    vec_loop<VEC>(n, [&](int64_t i, auto w) {
+        constexpr int W = decltype(w)::value;
+        double a[W];
+        load_row<W>(x, i, a);
+#pragma unroll
+        for (int j = 0; j < W; j++) {
+            const double scaled = alpha * a[j];
+            a[j] = fill ? alpha : scaled;
+        }
+        store_row<W>(x, i, a, kAll);
+    });
 }
 
 int launch_scal(hipStream_t s, int64_t n, double alpha, double *x)
 {
-    const int g = vec_grid(n);
-    if (aligned16(x)) hipLaunchKernelGGL(k_scal<1>, dim3(g), dim3(kBlock), 0, s, n, alpha, x, 0);
-    else hipLaunchKernelGGL(k_scal<0>, dim3(g), dim3(kBlock), 0, s, n, alpha, x, 0);
-    CM_HIP(hipGetLastError());
-    return CUDAMAT_OK;
+    CM_VEC_LAUNCH(all_aligned16(x), vec_grid(n), k_scal<VEC>, n, alpha, x, 0);
 }
 
 int launch_fill(hipStream_t s, int64_t n, double value, double *x)
 {
-    const int g = vec_grid(n);
-    if (aligned16(x)) hipLaunchKernelGGL(k_scal<1>, dim3(g), dim3(kBlock), 0, s, n, value, x, 1);
-    else hipLaunchKernelGGL(k_scal<0>, dim3(g), dim3(kBlock), 0, s, n, value, x, 1);
-    CM_HIP(hipGetLastError());
-    return CUDAMAT_OK;
+    CM_VEC_LAUNCH(all_aligned16(x), vec_grid(n), k_scal<VEC>, n, value, x, 1);
 }
 
 __global__ __launch_bounds__(kBlock) void k_rebase(int64_t n, const int *in, int shift, int *out)

@@ -93,39 +93,28 @@ __global__ __launch_bounds__(kBlock) void k_pipe_a(LoopArgs la, ScalarSrc B, int
         acc[1] += yy * yy;
         acc[2] += qq * qq;
     };
-    CM_VEC_LOOP(n,
-        {
-            const double2 rr = ((const double2 *)r)[i];
-            const double2 ww = ((const double2 *)w)[i];
-            const double2 tt = ((const double2 *)t)[i];
-            double2 vv = {0.0 COMMA 0.0};
-            if (!first) vv = ((const double2 *)v)[i];
-            const double2 xx = ((const double2 *)x)[i];
-            double2 pp = ((double2 *)p)[i];
-            double2 ss = ((double2 *)s)[i];
-            double2 zz = ((double2 *)z)[i];
-            double2 rrh = {0.0 COMMA 0.0}; double2 wwh = {0.0 COMMA 0.0}; double2 zzh = {0.0 COMMA 0.0};
-            double2 ssh = {0.0 COMMA 0.0}; double2 qqh = {0.0 COMMA 0.0};
-            if (PC) {
-                rrh = ((const double2 *)hat.rh)[i]; wwh = ((const double2 *)hat.wh)[i];
-                if (!first) { zzh = ((const double2 *)hat.zh)[i]; ssh = ((double2 *)hat.sh)[i]; }
+    vec_loop<VEC>(n, [&](int64_t i, auto width) {
+        constexpr int W = decltype(width)::value;
+        double rr[W], ww[W], tt[W], vv[W] = {}, xx[W], pp[W], ss[W], zz[W], qq[W], yy[W], xo[W];
+        double rrh[W] = {}, wwh[W] = {}, zzh[W] = {}, ssh[W] = {}, qqh[W] = {};
+        load_row<W>(r, i, rr); load_row<W>(w, i, ww); load_row<W>(t, i, tt);
+        if (!first) load_row<W>(v, i, vv);
+        load_row<W>(x, i, xx); load_row<W>(p, i, pp); load_row<W>(s, i, ss); load_row<W>(z, i, zz);
+        if (PC) {
+            load_row<W>(hat.rh, i, rrh); load_row<W>(hat.wh, i, wwh);
+            if (!first) {
+                load_row<W>(hat.zh, i, zzh); load_row<W>(hat.sh, i, ssh);
             }
-            double2 qq; double2 yy; double2 xo;
-            elem(rr.x, ww.x, tt.x, vv.x, pp.x, ss.x, zz.x, xx.x, qq.x, yy.x, xo.x, rrh.x, wwh.x, zzh.x, ssh.x, qqh.x);
-            elem(rr.y, ww.y, tt.y, vv.y, pp.y, ss.y, zz.y, xx.y, qq.y, yy.y, xo.y, rrh.y, wwh.y, zzh.y, ssh.y, qqh.y);
-            ((double2 *)p)[i] = pp; ((double2 *)s)[i] = ss; ((double2 *)z)[i] = zz;
-            ((double2 *)q)[i] = qq; ((double2 *)y)[i] = yy; ((double2 *)xh)[i] = xo;
-            if (PC) { ((double2 *)hat.sh)[i] = ssh; ((double2 *)hat.qh)[i] = qqh; }
-        },
-        {
-            double pp = p[i]; double ss = s[i]; double zz = z[i]; double qq; double yy; double xo;
-            double ssh = 0.0; double qqh = 0.0;
-            if (PC && !first) ssh = hat.sh[i];
-            elem(r[i], w[i], t[i], first ? 0.0 : v[i], pp, ss, zz, x[i], qq, yy, xo, PC ? hat.rh[i] : 0.0, PC ? hat.wh[i] : 0.0,
-                 (PC && !first) ? hat.zh[i] : 0.0, ssh, qqh);
-            p[i] = pp; s[i] = ss; z[i] = zz; q[i] = qq; y[i] = yy; xh[i] = xo;
-            if (PC) { hat.sh[i] = ssh; hat.qh[i] = qqh; }
-        })
+        }
+#pragma unroll
+        for (int j = 0; j < W; j++)
+            elem(rr[j], ww[j], tt[j], vv[j], pp[j], ss[j], zz[j], xx[j], qq[j], yy[j], xo[j], rrh[j], wwh[j], zzh[j], ssh[j], qqh[j]);
+        store_row<W>(p, i, pp, kAll); store_row<W>(s, i, ss, kAll); store_row<W>(z, i, zz, kAll);
+        store_row<W>(q, i, qq, kAll); store_row<W>(y, i, yy, kAll); store_row<W>(xh, i, xo, kAll);
+        if (PC) {
+            store_row<W>(hat.sh, i, ssh, kAll); store_row<W>(hat.qh, i, qqh, kAll);
+        }
+    });
     block_sum<kPipeA>(acc, lds);
     if (threadIdx.x == 0)
         for (int j = 0; j < kPipeA; j++) parts[kPipeA * blockIdx.x + j] = acc[j];
@@ -180,31 +169,21 @@ __global__ __launch_bounds__(kBlock) void k_pipe_b(LoopArgs la, ScalarSrc A, int
         acc[3] += ww_ * zz;
         acc[4] += rr * rr;
     };
-    CM_VEC_LOOP(n,
-        {
-            const double2 qq = ((const double2 *)q)[i];
-            const double2 yy = ((const double2 *)y)[i];
-            const double2 tt = ((const double2 *)t)[i];
-            const double2 vv = ((const double2 *)v)[i];
-            const double2 ww_ = ((const double2 *)rw)[i];
-            const double2 ss = ((const double2 *)s)[i];
-            const double2 zz = ((const double2 *)z)[i];
-            const double2 xo = ((const double2 *)xh)[i];
-            double2 qqh = {0.0 COMMA 0.0}; double2 wwh = {0.0 COMMA 0.0}; double2 zzh = {0.0 COMMA 0.0}; double2 rrh = {0.0 COMMA 0.0};
-            if (PC) { qqh = ((const double2 *)hat.qh)[i]; wwh = ((const double2 *)hat.wh)[i]; zzh = ((const double2 *)hat.zh)[i]; }
-            double2 xx; double2 rr; double2 wn;
-            elem(qq.x, yy.x, tt.x, vv.x, ww_.x, ss.x, zz.x, xo.x, xx.x, rr.x, wn.x, qqh.x, wwh.x, zzh.x, rrh.x);
-            elem(qq.y, yy.y, tt.y, vv.y, ww_.y, ss.y, zz.y, xo.y, xx.y, rr.y, wn.y, qqh.y, wwh.y, zzh.y, rrh.y);
-            ((double2 *)x)[i] = xx; ((double2 *)r)[i] = rr; ((double2 *)w)[i] = wn;
-            if (PC) ((double2 *)hat.rh)[i] = rrh;
-        },
-        {
-            double xx; double rr; double wn; double rrh = 0.0;
-            elem(q[i], y[i], t[i], v[i], rw[i], s[i], z[i], xh[i], xx, rr, wn, PC ? hat.qh[i] : 0.0, PC ? hat.wh[i] : 0.0,
-                 PC ? hat.zh[i] : 0.0, rrh);
-            x[i] = xx; r[i] = rr; w[i] = wn;
-            if (PC) hat.rh[i] = rrh;
-        })
+    vec_loop<VEC>(n, [&](int64_t i, auto width) {
+        constexpr int W = decltype(width)::value;
+        double qq[W], yy[W], tt[W], vv[W], ww_[W], ss[W], zz[W], xo[W], xx[W], rr[W], wn[W];
+        double qqh[W] = {}, wwh[W] = {}, zzh[W] = {}, rrh[W] = {};
+        load_row<W>(q, i, qq); load_row<W>(y, i, yy); load_row<W>(t, i, tt); load_row<W>(v, i, vv);
+        load_row<W>(rw, i, ww_); load_row<W>(s, i, ss); load_row<W>(z, i, zz); load_row<W>(xh, i, xo);
+        if (PC) {
+            load_row<W>(hat.qh, i, qqh); load_row<W>(hat.wh, i, wwh); load_row<W>(hat.zh, i, zzh);
+        }
+#pragma unroll
+        for (int j = 0; j < W; j++)
+            elem(qq[j], yy[j], tt[j], vv[j], ww_[j], ss[j], zz[j], xo[j], xx[j], rr[j], wn[j], qqh[j], wwh[j], zzh[j], rrh[j]);
+        store_row<W>(x, i, xx, kAll); store_row<W>(r, i, rr, kAll); store_row<W>(w, i, wn, kAll);
+        if (PC) store_row<W>(hat.rh, i, rrh, kAll);
+    });
     block_sum<kPipeB>(acc, lds);
     if (threadIdx.x == 0)
         for (int j = 0; j < kPipeB; j++) parts[kPipeB * blockIdx.x + j] = acc[j];
@@ -241,18 +220,9 @@ int launch_pipe_a(hipStream_t s, LoopArgs la, ScalarSrc B, int64_t n, const doub
 {
     const int g = vec_grid(n);
     *nparts = g;
-    const bool pc = hat.rh != nullptr;
-    const bool al = aligned16(r) && aligned16(w) && aligned16(t) && aligned16(v) && aligned16(p) && aligned16(sv) && aligned16(z) &&
-                    aligned16(q) && aligned16(y) && aligned16(x) && aligned16(xh) &&
-                    (!pc || (aligned16(hat.rh) && aligned16(hat.wh) && aligned16(hat.zh) && aligned16(hat.sh) && aligned16(hat.qh)));
-#define CM_PIPE_A(V, P) hipLaunchKernelGGL((k_pipe_a<V, P>), dim3(g), dim3(kBlock), 0, s, la, B, n, r, w, t, v, p, sv, z, q, y, x, xh, parts, hat)
-    if (al && pc) CM_PIPE_A(1, 1);
-    else if (al) CM_PIPE_A(1, 0);
-    else if (pc) CM_PIPE_A(0, 1);
-    else CM_PIPE_A(0, 0);
-#undef CM_PIPE_A
-    CM_HIP(hipGetLastError());
-    return CUDAMAT_OK;
+    const bool al = all_aligned16(r, w, t, v, p, sv, z, q, y, x, xh, hat.rh, hat.wh, hat.zh, hat.sh, hat.qh);
+    if (hat.rh) CM_VEC_LAUNCH(al, g, (k_pipe_a<VEC, 1>), la, B, n, r, w, t, v, p, sv, z, q, y, x, xh, parts, hat);
+    CM_VEC_LAUNCH(al, g, (k_pipe_a<VEC, 0>), la, B, n, r, w, t, v, p, sv, z, q, y, x, xh, parts, hat);
 }
 
 int launch_pipe_b(hipStream_t s, LoopArgs la, ScalarSrc A, int64_t n, const double *q, const double *y, const double *t,
@@ -261,18 +231,9 @@ int launch_pipe_b(hipStream_t s, LoopArgs la, ScalarSrc A, int64_t n, const doub
 {
     const int g = vec_grid(n);
     *nparts = g;
-    const bool pc = hat.rh != nullptr;
-    const bool al = aligned16(q) && aligned16(y) && aligned16(t) && aligned16(v) && aligned16(rw) && aligned16(sv) && aligned16(z) &&
-                    aligned16(xh) && aligned16(x) && aligned16(r) && aligned16(w) &&
-                    (!pc || (aligned16(hat.qh) && aligned16(hat.wh) && aligned16(hat.zh) && aligned16(hat.rh)));
-#define CM_PIPE_B(V, P) hipLaunchKernelGGL((k_pipe_b<V, P>), dim3(g), dim3(kBlock), 0, s, la, A, n, q, y, t, v, rw, sv, z, xh, x, r, w, parts, hat)
-    if (al && pc) CM_PIPE_B(1, 1);
-    else if (al) CM_PIPE_B(1, 0);
-    else if (pc) CM_PIPE_B(0, 1);
-    else CM_PIPE_B(0, 0);
-#undef CM_PIPE_B
-    CM_HIP(hipGetLastError());
-    return CUDAMAT_OK;
+    const bool al = all_aligned16(q, y, t, v, rw, sv, z, xh, x, r, w, hat.qh, hat.wh, hat.zh, hat.rh);
+    if (hat.rh) CM_VEC_LAUNCH(al, g, (k_pipe_b<VEC, 1>), la, A, n, q, y, t, v, rw, sv, z, xh, x, r, w, parts, hat);
+    CM_VEC_LAUNCH(al, g, (k_pipe_b<VEC, 0>), la, A, n, q, y, t, v, rw, sv, z, xh, x, r, w, parts, hat);
 }
 
 // ---- residual replacement of the pipelined loop (solver.hip): r = f - ax, and the five dots k_pipe_b would have left
@@ -281,23 +242,19 @@ template <int VEC>
 __global__ __launch_bounds__(kBlock) void k_residual(const LoopState *st, int64_t n, const double *f, const double *ax, double *r)
 {
     if (st && st->state != 0) return;                  // frozen loop: ax is stale, r must stay the iterate's residual
-    CM_VEC_LOOP(n,
-        {
-            const double2 ff = ((const double2 *)f)[i];
-            const double2 aa = ((const double2 *)ax)[i];
-            double2 rr; rr.x = ff.x - aa.x; rr.y = ff.y - aa.y;
-            ((double2 *)r)[i] = rr;
-        },
-        { r[i] = f[i] - ax[i]; })
+    vec_loop<VEC>(n, [&](int64_t i, auto width) {
+        constexpr int W = decltype(width)::value;
+        double ff[W], aa[W];
+        load_row<W>(f, i, ff); load_row<W>(ax, i, aa);
+#pragma unroll
+        for (int j = 0; j < W; j++) ff[j] = ff[j] - aa[j];
+        store_row<W>(r, i, ff, kAll);
+    });
 }
 
 int launch_residual(hipStream_t s, const LoopArgs &la, int64_t n, const double *f, const double *ax, double *r)
 {
-    const int g = vec_grid(n);
-    if (aligned16(f) && aligned16(ax) && aligned16(r)) hipLaunchKernelGGL(k_residual<1>, dim3(g), dim3(kBlock), 0, s, la.st, n, f, ax, r);
-    else hipLaunchKernelGGL(k_residual<0>, dim3(g), dim3(kBlock), 0, s, la.st, n, f, ax, r);
-    CM_HIP(hipGetLastError());
-    return CUDAMAT_OK;
+    CM_VEC_LAUNCH(all_aligned16(f, ax, r), vec_grid(n), k_residual<VEC>, la.st, n, f, ax, r);
 }
 
 template <int VEC>
@@ -315,17 +272,13 @@ __global__ __launch_bounds__(kBlock) void k_pipe_dots(const LoopState *st, int64
         acc[3] += ww_ * zz;
         acc[4] += rr * rr;
     };
-    CM_VEC_LOOP(n,
-        {
-            const double2 a = ((const double2 *)rw)[i];
-            const double2 b = ((const double2 *)r)[i];
-            const double2 c = ((const double2 *)w)[i];
-            const double2 d = ((const double2 *)s)[i];
-            const double2 e = ((const double2 *)z)[i];
-            elem(a.x, b.x, c.x, d.x, e.x);
-            elem(a.y, b.y, c.y, d.y, e.y);
-        },
-        { elem(rw[i], r[i], w[i], s[i], z[i]); })
+    vec_loop<VEC>(n, [&](int64_t i, auto width) {
+        constexpr int W = decltype(width)::value;
+        double a[W], b[W], c[W], d[W], e[W];
+        load_row<W>(rw, i, a); load_row<W>(r, i, b); load_row<W>(w, i, c); load_row<W>(s, i, d); load_row<W>(z, i, e);
+#pragma unroll
+        for (int j = 0; j < W; j++) elem(a[j], b[j], c[j], d[j], e[j]);
+    });
     block_sum<kPipeB>(acc, lds);
     if (threadIdx.x == 0)
         for (int j = 0; j < kPipeB; j++) parts[kPipeB * blockIdx.x + j] = acc[j];
@@ -336,12 +289,7 @@ int launch_pipe_dots(hipStream_t s, const LoopArgs &la, int64_t n, const double 
 {
     const int g = vec_grid(n);
     *nparts = g;
-    if (aligned16(rw) && aligned16(r) && aligned16(w) && aligned16(sv) && aligned16(z))
-        hipLaunchKernelGGL(k_pipe_dots<1>, dim3(g), dim3(kBlock), 0, s, la.st, n, rw, r, w, sv, z, parts);
-    else
-        hipLaunchKernelGGL(k_pipe_dots<0>, dim3(g), dim3(kBlock), 0, s, la.st, n, rw, r, w, sv, z, parts);
-    CM_HIP(hipGetLastError());
-    return CUDAMAT_OK;
+    CM_VEC_LAUNCH(all_aligned16(rw, r, w, sv, z), g, k_pipe_dots<VEC>, la.st, n, rw, r, w, sv, z, parts);
 }
 
 }  // namespace cm

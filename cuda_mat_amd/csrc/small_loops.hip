@@ -7,6 +7,8 @@
 #include "kernels.h"
 #include "device.h"
 
+#pragma clang fp contract(off)      // no product-sum here is left to the compiler: fma() is written where one rounding is meant
+
 namespace cm {
 
 // ---------------------------------------------------------------- fused loop for small (L2-resident) systems
@@ -18,25 +20,20 @@ namespace cm {
 //   k_fspmv<.., FUSE_HALF>  alpha; s = r - alpha v' on the fly; x += alpha p'; t = A s;  (t.s, t.t), ||s||^2
 //   k_full                  half-step test, omega, x += omega s, r = s - omega t, (rw.r, ||r||^2)
 // p, v and r are double-buffered (a workgroup may still gather the old vector while another stores the new one).
-// Every value is produced by the same expression as in k_update_p / k_half, so iterates agree with the five-launch
+// Every value is produced by the function k_update_p / k_half call for it (steps.h), so iterates agree with the five-launch
 // loop up to the summation order of ||s||^2 (per SpMV workgroup here, per vector chunk there).
 enum { FUSE_P = 1, FUSE_HALF = 2 };
 
 template <int MODE>
 struct FusedX {
     const double *r, *b1, *b2;     // FUSE_P: b1 = p, b2 = v;  FUSE_HALF: b1 = v
-    double c1, c2;                 // FUSE_P: beta, -omega;    FUSE_HALF: -alpha
+    double c1, c2;                 // FUSE_P: beta, omega;     FUSE_HALF: alpha
     bool first;                    // FUSE_P at iteration 0: p = r already (k_init)
     // the folded vector element from its already-fetched operands (rv = r, v1 = b1, v2 = b2 at the same index)
     __device__ __forceinline__ double combine(double rv, double v1, double v2) const
     {
-        if (MODE == FUSE_P) {
-            if (first) return v1;
-            double pp = fma(c2, v2, v1);                       // pbicgstab.cu:86
-            pp = c1 * pp;                                      // :87
-            return rv + pp;                                    // :88
-        }
-        return fma(c1, v1, rv);                                // :109
+        if (MODE == FUSE_P) return first ? v1 : step_p(rv, v1, v2, c1, c2);
+        return step_r_half(rv, v1, c1);
     }
     __device__ __forceinline__ double operator()(int c) const
     {
@@ -65,18 +62,18 @@ __device__ __forceinline__ bool fused_prologue(const LoopArgs &la, const FuseArg
         X.first = it == 0;
         X.b1 = f.p_old;
         X.b2 = f.v_old;
-        X.c1 = (rho / rhop) * (alpha / omega);                 // :84 (unused at it == 0)
-        X.c2 = -omega;
+        X.c1 = step_beta(rho, rhop, alpha, omega);             // (unused at it == 0)
+        X.c2 = omega;
         alpha_out = 0.0;
     } else {
         double sc[1];
         load_scalars<1>(f.src, sc, lds);
-        const double alpha = st->rho[it & 1] / sc[0];          // :107
+        const double alpha = step_alpha(st->rho[it & 1], sc[0]);
         if (leader()) st->alpha = alpha;
         X.first = false;
         X.b1 = f.v;
         X.b2 = nullptr;
-        X.c1 = -alpha;
+        X.c1 = alpha;
         X.c2 = 0.0;
         alpha_out = alpha;
     }
@@ -120,17 +117,17 @@ template <int MODE>
 __device__ __forceinline__ void fused_finish_row_x(const SpmvArgs &a, const FuseArgs &f, double alpha, int row, double sum,
                                                    const FusedRowOps &o, double xr, double (&acc)[3])
 {
-    if (a.d) sum += o.d * xr;
+    if (a.d) sum = fma(o.d, xr, sum);                          // the shift, as spmv_finish_row_fused adds it
     a.y[row] = sum;                                            // alpha = 1, beta = 0 inside the loop
     if (MODE == FUSE_P) {
         f.p_out[row] = xr;
-        acc[0] += sum * o.w;                                   // rw . v
+        dot_step(acc[0], sum, o.w);                            // rw . v
     } else {
         f.s_out[row] = xr;
-        f.xsol[row] = fma(alpha, o.p, o.x);                    // :110
-        acc[0] += sum * xr;                                    // t . s
-        acc[1] += sum * sum;                                   // t . t
-        acc[2] += xr * xr;                                     // ||s||^2 (:111)
+        f.xsol[row] = step_x_half(o.x, o.p, alpha);
+        dot_step(acc[0], sum, xr);                             // t . s
+        dot_step(acc[1], sum, sum);                            // t . t
+        dot_step(acc[2], xr, xr);                              // ||s||^2 (:111)
     }
 }
 
@@ -162,7 +159,7 @@ __global__ __launch_bounds__(kBlock) void k_fspmv_lanes(SpmvArgs a, int rows_per
     for (int row = row_begin + group; row < row_end; row += RPB) {
         const int s = a.rp[row], e = a.rp[row + 1];
         double sum = 0.0;
-        for (int k = s + lane; k < e; k += L) sum += a.val[k] * X(a.ci[k]);
+        for (int k = s + lane; k < e; k += L) sum = fma(a.val[k], X(a.ci[k]), sum);
         sum = group_sum<L>(sum);
         if (lane == 0) fused_finish_row<MODE>(a, f, X, alpha, row, sum, fused_row_ops<MODE>(a, f, row), acc);
     }
@@ -275,8 +272,8 @@ int launch_fused_spmv(hipStream_t s, const SpmvPlan &plan, const SpmvArgs &a, co
 // drained.  Here the SAME three phases run inside ONE launch: every workgroup owns one tile of R rows for the whole
 // solve -- its matrix entries, row ends and rw stay in registers / LDS -- and the phases are separated by a grid
 // barrier (release fence, one agent-scope atomic arrival, polling load, acquire fence) instead of a launch boundary.
-// Every scalar, stopping test and vector value is produced by the expressions of the fused loop (fused_prologue,
-// fused_finish_row, check_half, check_full); only the partial sums of the last phase are grouped per tile instead
+// Every scalar and vector value is produced by the steps of steps.h, as in the fused loop; the stopping tests restate
+// check_half and check_full (their stores differ); only the partial sums of the last phase are grouped per tile instead
 // of per vector chunk.  All workgroups take every exit decision from the same partial sums, so they leave the loop
 // in the same phase.  The grid is at most one workgroup per two compute units, all resident at once; should the GPU be
 // shared with something that keeps some of them from starting, the barrier's bounded wait raises a flag, every
@@ -405,8 +402,8 @@ __global__ __launch_bounds__(kBlock) void k_resident_loop(SpmvArgs a, ResidentAr
             if (lead) st_shared(&st->rho[it & 1], rho);
             FusedX<FUSE_P> X;
             X.first = it == 0;
-            X.c1 = (rho / rhop) * (alpha / omega);                 // :84 (unused at it == 0)
-            X.c2 = -omega;
+            X.c1 = step_beta(rho, rhop, alpha, omega);             // (unused at it == 0)
+            X.c2 = omega;
 #pragma unroll
             for (int j = 0; j < E; j++) {
                 const int e = tid + j * kBlock;
@@ -418,7 +415,7 @@ __global__ __launch_bounds__(kBlock) void k_resident_loop(SpmvArgs a, ResidentAr
                 double sum = 0.0;
                 for (int j = lo; j < hi; j++) sum += prod[j];
                 p_new = X.combine(r_own, p_own, v_own);
-                if (a.d) sum += d_own * p_new;
+                if (a.d) sum = fma(d_own, p_new, sum);
                 st_shared(&v_b[row], sum);
                 st_shared(&p_b[row], p_new);
                 acc[0] = sum * w_own;                              // rw . v
@@ -443,11 +440,11 @@ __global__ __launch_bounds__(kBlock) void k_resident_loop(SpmvArgs a, ResidentAr
             const double r_own = own ? r[row] : 0.0, v_own = own ? v_b[row] : 0.0;
             double sc[1];
             load_scalars<1>(ScalarSrc{q.parts_rv, G, 2}, sc, lds);
-            alpha = rho_s[it & 1] / sc[0];                         // :107
+            alpha = step_alpha(rho_s[it & 1], sc[0]);
             if (lead) st_shared(&st->alpha, alpha);
             FusedX<FUSE_HALF> X;
             X.first = false;
-            X.c1 = -alpha;
+            X.c1 = alpha;
             X.c2 = 0.0;
 #pragma unroll
             for (int j = 0; j < E; j++) {
@@ -460,10 +457,10 @@ __global__ __launch_bounds__(kBlock) void k_resident_loop(SpmvArgs a, ResidentAr
                 double sum = 0.0;
                 for (int j = lo; j < hi; j++) sum += prod[j];
                 s_new = X.combine(r_own, v_own, 0.0);
-                if (a.d) sum += d_own * s_new;
+                if (a.d) sum = fma(d_own, s_new, sum);
                 t_new = sum;
                 st_shared(&sv[row], s_new);
-                x_half = fma(alpha, p_new, x_cur);                 // :110
+                x_half = step_x_half(x_cur, p_new, alpha);
                 acc[0] = sum * s_new;                              // t . s
                 acc[1] = sum * sum;                                // t . t
                 acc[2] = s_new * s_new;                            // ||s||^2 (:111)
@@ -497,11 +494,11 @@ __global__ __launch_bounds__(kBlock) void k_resident_loop(SpmvArgs a, ResidentAr
                     break;
                 }
             }
-            omega = sc[1] / sc[2];                                 // :137
+            omega = step_omega(sc[1], sc[2]);
             double acc[2] = {0.0, 0.0};
             if (own) {
-                x_cur = fma(omega, s_new, x_half);                 // :139
-                const double rr = fma(-omega, t_new, s_new);       // :140
+                x_cur = step_x_full(x_half, s_new, omega);
+                const double rr = step_r_full(s_new, t_new, omega);
                 st_shared(&sv[row], rr);   // the new residual goes over s (as k_full does)
                 acc[0] = w_own * rr;                               // :81 of i+1
                 acc[1] = rr * rr;                                  // :142

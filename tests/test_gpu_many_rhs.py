@@ -415,3 +415,30 @@ def test_bicgstab_many_drop_in(cm, oracle, golden_dir, form_sw, monkeypatch):
     ok2, X2, _, sts2, _ = cm.bicgstab_many(n, nnz, A.val, A.rowptr, A.colidx, B, 2000, 1e-8)
     assert all(s.plan_reused == 1 for s in sts2)
     np.testing.assert_array_equal(X2, X)
+
+
+@pytest.mark.parametrize("nrhs", [1, 2, 3, 8])
+def test_loop_bits_batched_solve(cm, ctx, sw, nrhs):
+    """three iterations of the batched loop (K = 1, 2, 4 with a padding column, 8) on the diagonal system of
+    test_loop_rounding.py: every column's x and residual history equal the column's own CPU mirror bit for bit -- the steps
+    of csrc/steps.h, a row per thread in the K-column vector kernels, the SpMM's fused dots in k_spmv<64>'s partition"""
+    import test_loop_rounding as L
+    assert ("rows", 0) in L.TELLING and ("rows", 1) in L.TELLING
+    for name, value in (("MANY_FORM", "batched"), ("SPMV_MODE", "csr"), ("SPMV_LANES", L.LANES), ("FUSED", 0), ("RESIDENT", 0)):
+        sw(name, value)
+    cols = [L.system(j) for j in range(nrhs)]
+    a = cols[0][0]
+    s = cm.Solver.from_host_csr(ctx, np.arange(L.N + 1), np.arange(L.N), a)
+    try:
+        dB, dX = _block(ctx, np.stack([c[1] for c in cols], axis=1), L.N), _block(ctx, np.stack([c[2] for c in cols], axis=1), L.N)
+        sts, form = s.solve_many(nrhs, dB, L.N, dX, L.N, loop=cm.LOOP_PBICGSTAB, maxit=L.ITERS, tol=1e-8, flags=cm.FLAG_NO_EXIT)
+        X = _unblock(dX, L.N, nrhs, L.N)
+        hs = [s.history(col=j) for j in range(nrhs)]
+    finally:
+        s.close()
+    assert form == 1 and [st.iters for st in sts] == [L.ITERS] * nrhs
+    for j in range(nrhs):
+        want_x, want_h = L.pinned("rows", j)
+        print("column", j, "entries of x that differ:", L.differing(X[:, j], want_x), "residuals:", L.differing(hs[j], want_h))
+        np.testing.assert_array_equal(hs[j], want_h)
+        np.testing.assert_array_equal(X[:, j], want_x)

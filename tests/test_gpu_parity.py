@@ -1315,6 +1315,32 @@ def test_fused_small_system_loop_equals_five_launch_loop(cm, ctx, oracle, golden
     np.testing.assert_allclose(x1, xs, rtol=1e-6)
 
 
+@pytest.mark.parametrize("layout", ["aligned", "offset8"])
+def test_loop_bits_single_solve(cm, ctx, sw, layout):
+    """three iterations of the five-launch loop on the diagonal system of test_loop_rounding.py: x and the residual history
+    equal the CPU mirror of csrc/steps.h and the kernels' reduction orders bit for bit -- with b and x 16-byte aligned (the
+    pair kernels) and both 8 bytes off (k_init<0> and k_full<0>: a row per thread; k_update_p and k_half see the solver's
+    own vectors and keep pairs).  The mirror tells the two-rounding p-update from the reference's three, fma dot terms from
+    fl(a b) + acc and the order of the two x steps apart on these inputs (test_the_loop_mirror_tells_its_neighbours_apart)."""
+    import test_loop_rounding as L
+    col = {"aligned": 2, "offset8": 0}[layout]
+    assert (layout, col) in L.TELLING
+    a, b, x0 = L.system(col)
+    for name, value in (("SPMV_MODE", "csr"), ("SPMV_LANES", L.LANES), ("FUSED", 0), ("RESIDENT", 0)):
+        sw(name, value)
+    off = 1 if layout == "offset8" else 0
+    s = cm.Solver.from_host_csr(ctx, np.arange(L.N + 1), np.arange(L.N), a)
+    db, dx = ctx.array(np.concatenate([np.zeros(off), b])), ctx.array(np.concatenate([np.zeros(off), x0]))
+    st = s.solve(db.ptr + 8 * off, dx.ptr + 8 * off, loop=cm.LOOP_PBICGSTAB, maxit=L.ITERS, tol=1e-8, flags=cm.FLAG_NO_EXIT)
+    x, h = dx.download()[off:], s.history()
+    s.close()
+    assert (st.iters, st.loop_form) == (L.ITERS, 0)
+    want_x, want_h = L.pinned(layout, col)
+    print(layout, "entries of x that differ:", L.differing(x, want_x), "residuals:", L.differing(h, want_h), h, want_h)
+    np.testing.assert_array_equal(h, want_h)
+    np.testing.assert_array_equal(x, want_x)
+
+
 def test_huge_maxit_does_not_allocate_a_huge_history(cm, ctx, oracle, golden_dir):
     """maxit = 2^30 (a caller's 'no limit'): the residual history is capped at 2^20 entries instead of 16 GB"""
     A = _load(oracle, golden_dir, "mat900")
