@@ -1341,6 +1341,147 @@ def test_loop_bits_single_solve(cm, ctx, sw, layout):
     np.testing.assert_array_equal(x, want_x)
 
 
+# ---- the other loop forms, the shifted loop, the ILU(0) loop, exits and solver reuse against the same mirror (test_loop_rounding.py:
+# FORMS, inputs, pinned_form; what each comparison can tell apart is checked there, without a GPU)
+_LOOP_SWITCHES = {            # SPMV_LANES, FUSED, RESIDENT
+    "five/lanes": (64, 0, 0), "five/stream": (None, 0, 0), "fused/lanes": (64, 1000000, 0), "fused/stream": (None, 1000000, 0),
+    "single": (None, 1000000, 1),
+}
+_LOOP_CASES = [("pbicgstab", False), ("pbicgstab2", False), ("pbicgstab2", True)]
+
+
+def _loop_solver(cm, ctx, sw, form, A, d):
+    """a solver on A (a diagonal as a vector, or test_loop_rounding.Csr) with the switches that select `form`"""
+    import test_loop_rounding as L
+    lanes, fused, resident = _LOOP_SWITCHES[form]
+    for name, value in (("SPMV_MODE", "csr"), ("SPMV_LANES", lanes), ("FUSED", fused), ("RESIDENT", resident)):
+        sw(name, value)
+    if isinstance(A, L.Csr):
+        s = cm.Solver.from_host_csr(ctx, A.rp, A.ci, A.val)
+    else:
+        s = cm.Solver.from_host_csr(ctx, np.arange(len(A) + 1), np.arange(len(A)), A)
+    want = "k_spmv<64>" if lanes else "k_spmv_stream"
+    assert s.spmv_kernel().startswith(want), (form, s.spmv_kernel())       # the plan whose dealing the mirror restates
+    if d is not None:
+        s.set_shift(ctx.array(d))
+    return s
+
+
+def _loop_solve(cm, ctx, s, b, x0, kind, **kw):
+    db, dx = ctx.array(b), ctx.array(x0)          # 16-byte aligned: the pair kernels
+    st = s.solve(db, dx, loop=cm.LOOP_PBICGSTAB if kind == "pbicgstab" else cm.LOOP_PBICGSTAB2, **kw)
+    x, h = dx.download(), s.history()
+    db.free()
+    dx.free()
+    return st, x, h
+
+
+def _assert_loop_bits(tag, got, want, form, iters):
+    import test_loop_rounding as L
+    (st, x, h), (want_x, want_h) = got, want
+    print(tag, "entries of x that differ:", L.differing(x, want_x), "of", len(x), "residuals:",
+          L.differing(h, want_h) if len(h) == len(want_h) else (len(h), len(want_h)), h, want_h)
+    assert (st.loop_form, st.loop_fallbacks, st.iters) == (L.FORMS[form]["loop_form"], 0, iters)
+    np.testing.assert_array_equal(h, want_h)
+    np.testing.assert_array_equal(x, want_x)
+
+
+def _loop_bits_case(cm, ctx, sw, form, which, kind, shifted, iters):
+    import test_loop_rounding as L
+    A, b, x0, d = L.inputs(which, form, shifted)
+    s = _loop_solver(cm, ctx, sw, form, A, d)
+    got = _loop_solve(cm, ctx, s, b, x0, kind, maxit=iters, tol=1e-8, flags=cm.FLAG_NO_EXIT)
+    s.close()
+    _assert_loop_bits("%s %s %s%s %d:" % (form, which, kind, " shifted" if shifted else "", iters), got,
+                      L.pinned_form(which, form, kind, shifted, iters), form, iters)
+
+
+def test_loop_bits_fused_lanes(cm, ctx, sw):
+    """three iterations of the three-launch loop on the lanes-per-row plan (k_fspmv_lanes<64, .> + k_full), diagonal system:
+    x and the history equal the mirror bit for bit.  x is also the five-launch loop's by construction; the history is not
+    (||s||^2 per SpMV workgroup)."""
+    _loop_bits_case(cm, ctx, sw, "fused/lanes", "diagonal", "pbicgstab", False, 3)
+
+
+@pytest.mark.parametrize("iters", [3, 4])
+@pytest.mark.parametrize("kind,shifted", _LOOP_CASES)
+@pytest.mark.parametrize("which", ["diagonal", "banded"])
+def test_loop_bits_fused_stream(cm, ctx, sw, which, kind, shifted, iters):
+    """the three-launch loop on stream tiles (k_fspmv_stream<256, .> + k_full): both loops, the second also as (A + I d), on
+    the diagonal system (3 tiles) and the banded one (4 tiles, every workgroup gathers p' and s at rows another one stored:
+    the double buffers), after an odd and an even number of buffer swaps -- x and the history equal the mirror bit for bit"""
+    _loop_bits_case(cm, ctx, sw, "fused/stream", which, kind, shifted, iters)
+
+
+@pytest.mark.parametrize("iters", [3, 4])
+@pytest.mark.parametrize("kind,shifted", _LOOP_CASES)
+@pytest.mark.parametrize("which", ["diagonal", "banded"])
+def test_loop_bits_single_launch(cm, ctx, sw, which, kind, shifted, iters):
+    """the same cases in the single-launch loop (k_resident_loop<256>): its hand-written dot terms, its third phase's scalar
+    sums and its restated stopping-test stores give the mirror's x and history bit for bit"""
+    _loop_bits_case(cm, ctx, sw, "single", which, kind, shifted, iters)
+
+
+@pytest.mark.parametrize("iters", [3, 4])
+@pytest.mark.parametrize("kind,shifted", _LOOP_CASES)
+def test_loop_bits_five_launches_stream(cm, ctx, sw, kind, shifted, iters):
+    """the five-launch loop on the stream plan, banded system (test_loop_bits_single_solve pins it on the diagonal one, lanes
+    per row): column-order row sums, the tile dealing of the SpMV's dots, the shift in r0 and in every product"""
+    _loop_bits_case(cm, ctx, sw, "five/stream", "banded", kind, shifted, iters)
+
+
+def test_loop_bits_ilu0(cm, ctx, sw):
+    """three iterations of the ILU(0) loop on the diagonal system (L = I, U = diag(a)): the factors are a itself, one
+    application is rhs fl(1 / a_i) bitwise (tri_rows on empty rows), and x += alpha M^-1 p, then x += omega M^-1 r in k_full give
+    the mirror's x and history bit for bit"""
+    import test_loop_rounding as L
+    a, b, x0, _ = L.inputs("diagonal", "five/lanes")
+    s = _loop_solver(cm, ctx, sw, "five/lanes", a, None)
+    s.ilu0()
+    np.testing.assert_array_equal(s.ilu0_values(), a)
+    dr, do = ctx.array(b), ctx.empty(L.N)
+    s.precond_apply(dr, do)
+    np.testing.assert_array_equal(do.download(), b * (1.0 / a))
+    assert L.differing(b * (1.0 / a), b / a) >= L.MIN_DIFFERING_ROWS
+    got = _loop_solve(cm, ctx, s, b, x0, "pbicgstab", precond=cm.PRECOND_ILU0, maxit=L.ITERS, tol=1e-8, flags=cm.FLAG_NO_EXIT)
+    s.close()
+    _assert_loop_bits("ILU(0):", got, L.pinned_ilu0(), "five/lanes", L.ITERS)
+
+
+@pytest.mark.parametrize("exit_at", ["half", "full"])
+@pytest.mark.parametrize("form", ["five/stream", "fused/stream", "single"])
+def test_loop_bits_exits(cm, ctx, sw, form, exit_at):
+    """the banded system solved to a tolerance at which the loop leaves at the half step of iteration 3 / at the full step of
+    iteration 3 (the deciding residual >= 1 % off the tolerance: test_the_exit_cases_end_where_intended): the x the caller
+    receives -- finish() applying x += alpha p in form 0, FUSE_HALF's unconditional store in form 1, x_cur = x_half in form 2 --
+    and the history equal the mirror's bit for bit"""
+    import test_loop_rounding as L
+    A, b, x0, _ = L.inputs("banded", form)
+    tol = L.TOL_HALF if exit_at == "half" else L.TOL_FULL
+    want = L.pinned_exit(form, tol)
+    s = _loop_solver(cm, ctx, sw, form, A, None)
+    got = _loop_solve(cm, ctx, s, b, x0, "pbicgstab", maxit=20, tol=tol)
+    s.close()
+    st = got[0]
+    assert (bool(st.half_exit), bool(st.converged), bool(st.breakdown)) == (want.half_exit, True, False) and want.half_exit == (exit_at == "half")
+    _assert_loop_bits("%s exit at the %s step:" % (form, exit_at), got, (want.x, want.history), form, want.iters)
+
+
+@pytest.mark.parametrize("which", ["diagonal", "banded"])
+@pytest.mark.parametrize("form", ["fused/stream", "single"])
+def test_loop_bits_second_solve_on_one_solver(cm, ctx, sw, form, which):
+    """one solver object, 3 iterations and then 4 from a fresh copy of the same x0: the host has swapped p_a / p_b, v_a / v_b
+    and r / s an odd number of times by then (after every iteration of form 1, after an odd chunk of form 2), and nothing of
+    that leaks into the second solve -- each equals its mirror bit for bit"""
+    import test_loop_rounding as L
+    A, b, x0, d = L.inputs(which, form)
+    s = _loop_solver(cm, ctx, sw, form, A, d)
+    for iters in (3, 4):
+        got = _loop_solve(cm, ctx, s, b, x0, "pbicgstab", maxit=iters, tol=1e-8, flags=cm.FLAG_NO_EXIT)
+        _assert_loop_bits("%s %s, solve of %d iterations:" % (form, which, iters), got, L.pinned_form(which, form, iters=iters), form, iters)
+    s.close()
+
+
 def test_huge_maxit_does_not_allocate_a_huge_history(cm, ctx, oracle, golden_dir):
     """maxit = 2^30 (a caller's 'no limit'): the residual history is capped at 2^20 entries instead of 16 GB"""
     A = _load(oracle, golden_dir, "mat900")
