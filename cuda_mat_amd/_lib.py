@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libcudamat_hip.so")
 OK = 0
 PRECOND_NONE, PRECOND_ILU0, PRECOND_BLOCK_ILU0 = 0, 1, 2
 LOOP_PBICGSTAB, LOOP_PBICGSTAB2, LOOP_PIPELINED = 0, 1, 2
-FLAG_DEBUG, FLAG_PROFILE, FLAG_NO_EXIT, FLAG_X0_ONES = 1, 2, 4, 8
+FLAG_DEBUG, FLAG_PROFILE, FLAG_NO_EXIT, FLAG_X0_ONES, FLAG_GUARD = 1, 2, 4, 8, 16
 
 
 class CudamatError(RuntimeError):
@@ -36,7 +36,7 @@ class Stats(C.Structure):
                 ("loop_form", C.c_int), ("gather_fraction", C.c_double), ("ms_spmv_alone", C.c_double),
                 ("loop_fallbacks", C.c_int), ("restarts", C.c_int), ("t_upload", C.c_double), ("t_setup", C.c_double),
                 ("t_tune", C.c_double), ("spmv_mode", C.c_int), ("plan_reused", C.c_int),
-                ("trsv_groups_l", C.c_int), ("trsv_groups_u", C.c_int)]
+                ("trsv_groups_l", C.c_int), ("trsv_groups_u", C.c_int), ("rho_restarts", C.c_int)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

@@ -105,7 +105,8 @@ struct ScalarSrc {
 // `state` first and returns at once when it is non-zero ("freeze on exit"), so
 // kernels enqueued past the stopping point change nothing.
 struct LoopState {
-    int state;       // 0 running, 1 half-step exit, 2 full-step exit, 3 omega breakdown
+    int state;       // 0 running, 1 half-step exit, 2 full-step exit, 3 omega breakdown, 4 rho lost its last bit: restart
+                     // requested (guarded solves only: check_rho)
     int it;          // the reference's loop counter i
     int pad[2];
     double rho[2];   // rho of iteration it (slot it&1) and it-1

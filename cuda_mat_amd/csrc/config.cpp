@@ -61,6 +61,9 @@ const Option kOptions[] = {
      "0: never fold the vector updates into the SpMVs (three launches per iteration); N: do it for every supported plan up to N rows"},
     OPT_FLAG("RESIDENT", resident, "0: never run the whole loop of a very small system in one launch"),
     OPT_INT("RESIDENT_SPIN_LIMIT", resident_spin_limit, 0, 1 << 30, "polls a grid-barrier wait of the single-launch loop may take"),
+    OPT_FLAG("GUARD", guard, "1: every solve on the context runs as if CUDAMAT_FLAG_GUARD were set: restart from the true residual when rho has lost its last bit, converged = 1 only for a verified iterate (reference loops, one GPU)"),
+    {"GUARD_RHO_ULPS", K_LLONG, nullptr, &Config::guard_rho_ulps, 1, 1LL << 52, nullptr,
+     "guarded solves restart when |rho| <= N * 2^-52 * sum |rw_i r_i| (default 4; 2^52 fires at every iteration >= 1: tests)"},
     OPT_INT("PIPE_RR", pipe_rr, 0, 1 << 20, "residual replacement period of the pipelined loop (0: never)"),
     OPT_FLAG("TRSV_SYNCFREE", trsv_syncfree, "0: one launch per level; 1: dependency-driven launches also for narrow levels"),
     OPT_FLAG("TRSV_LDS", trsv_lds, "0: no single-workgroup LDS-resident triangular solve for small systems"),

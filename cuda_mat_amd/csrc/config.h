@@ -41,6 +41,8 @@ struct Config {
     long long fused = -1;         // FUSED              0: never fold the vector updates into the SpMVs; N: do it up to N rows (-1: short rows up to 3e5)
     int resident = 1;             // RESIDENT           0: never run the whole loop of a very small system in one launch
     int resident_spin_limit = -1; // RESIDENT_SPIN_LIMIT polls a grid-barrier wait of that loop may take (-1: 2^22)
+    int guard = 0;                // GUARD              1: every solve runs as if CUDAMAT_FLAG_GUARD were set (restart on a lost rho, verified convergence)
+    long long guard_rho_ulps = 4; // GUARD_RHO_ULPS     guarded solves restart when |rho| <= N * 2^-52 * sum |rw_i r_i|, 1 .. 2^52
     int pipe_rr = -1;             // PIPE_RR            residual replacement period of the pipelined loop (-1: 32; 0: never)
     // ---- ILU(0) and the triangular solves
     int trsv_syncfree = -1;       // TRSV_SYNCFREE      0: one launch per level; 1: dependency-driven launches also for narrow levels (-1: by level width)

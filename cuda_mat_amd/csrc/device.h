@@ -220,6 +220,22 @@ __device__ __forceinline__ bool check_full(const LoopArgs &la, const double (&sc
     return false;
 }
 
+// The test on rho of a guarded solve (CUDAMAT_FLAG_GUARD), at the top of iteration it >= 1 after check_full, so that a
+// convergence exit wins (at it = 0, rho = r.r).  rho = rw.r and mag = sum |rw_i| |r_i| come from the same terms in the same
+// order (k_full<VEC, true>), so |rho| <= mag holds in floating point too; eps = GUARD_RHO_ULPS * 2^-52 (exact).  When
+// |rho| <= eps * mag -- rho = 0 and a NaN rho included -- rho has not one significant bit left and every later beta would
+// divide rounding noise: state 4, the loop freezes with x the complete iterate of iteration it - 1 (k_full applied both
+// updates) and r, p untouched, and the host restarts from the true residual of x.  Under FLAG_NO_EXIT the test is evaluated
+// and never taken.  Returns true when the caller must return.
+__device__ __forceinline__ bool check_rho(const LoopArgs &la, double rho, double mag, double eps)
+{
+#pragma clang fp contract(off)
+    const bool lost = !(fabs(rho) > eps * mag);
+    if (!lost || la.no_exit) return false;
+    if (leader()) la.st->state = 4;
+    return true;
+}
+
 // ------------------------------------------------- interleaved vectors (batch.h)
 // row i of an n x K row-major block (K in {1, 2, 4, 8}): K contiguous doubles, moved 16 bytes at a time for K >= 2
 template <int K>

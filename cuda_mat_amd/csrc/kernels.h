@@ -150,16 +150,19 @@ int launch_init(hipStream_t s, int64_t n, const double *b, double *r, double *rw
 int launch_init_finish(hipStream_t s, LoopState *st, ScalarSrc init, double tol, double abs_tol, int no_exit, const double *r,
                        int64_t n);
 // p = r + beta (p - omega v), preceded by the full-step test of the previous iteration
+// rho_eps > 0 (guarded solves): `full` holds launch_full(..., guard = true)'s three sums from iteration 1 on, and the test
+// |rho| <= rho_eps * sum |rw_i| |r_i| follows the full-step test (state 4: restart requested)
 int launch_update_p(hipStream_t s, LoopArgs la, ScalarSrc full, int64_t n, const double *r,
-                    double *p, const double *v);
+                    double *p, const double *v, double rho_eps = 0.0);
 // alpha = rho / (rw.v); r -= alpha v; parts[b] = sum r^2   (the half step's x += alpha pw rides in launch_full(..., pw))
 int launch_half(hipStream_t s, LoopArgs la, ScalarSrc rv, int64_t n, double *r, const double *v, double *parts, int *nparts);
 // omega = (t.r)/(t.t); x += omega s; r -= omega t; parts = (rw.r, r.r); it++
 // half.ptr != NULL: evaluate the half-step stopping test from `half` first (fused small-system loop)
 // pw != NULL: x += alpha pw (the half step's update, with the alpha k_half stored) before x += omega s
+// guard: parts = (rw.r, r.r, sum |rw_i| |r_i|), stride 3
 int launch_full(hipStream_t s, LoopArgs la, ScalarSrc tt, int64_t n, double *x, const double *sv,
                 double *r, const double *t, const double *rw, double *parts, int *nparts,
-                ScalarSrc half = ScalarSrc{nullptr, 0, 1}, const double *pw = nullptr);
+                ScalarSrc half = ScalarSrc{nullptr, 0, 1}, const double *pw = nullptr, bool guard = false);
 // pipelined BiCGStab (pipelined.hip): partials of k_pipe_a have stride 3, of k_pipe_b stride 5
 int launch_pipe_seed(hipStream_t s, ScalarSrc init, ScalarSrc rww, double *out5);
 // the hatted (M^-1-applied) vectors of the preconditioned form; all NULL without a preconditioner

@@ -190,18 +190,28 @@ int launch_init_finish(hipStream_t s, LoopState *st, ScalarSrc init, double tol,
 }
 
 // p = r + beta (p - omega v)          pbicgstab.cu:83-89 (axpy, scal, axpy) fused: step_p
-template <int VEC>
+// GUARD (guarded solves): `full` carries a third sum, sum |rw_i| |r_i|, from iteration 1 on (k_full<VEC, true>; at it = 0 the
+// sums are k_init's two), and the test on rho follows the full-step test: check_rho.
+template <int VEC, bool GUARD>
 __global__ __launch_bounds__(kBlock) void k_update_p(LoopArgs la, ScalarSrc full, int64_t n,
-                                                     const double *r, double *p, const double *v)
+                                                     const double *r, double *p, const double *v, double rho_eps)
 {
-    __shared__ double lds[8];
+    __shared__ double lds[GUARD ? 12 : 8];
     LoopState *st = la.st;
     if (uniform_state(st) != 0) return;
     const int it = st->it;
     double sc[2];
-    load_scalars<2>(full, sc, lds);
+    [[maybe_unused]] double mag = 0.0;
+    if (GUARD && it != 0) {
+        double sc3[3];
+        load_scalars<3>(full, sc3, lds);
+        sc[0] = sc3[0]; sc[1] = sc3[1]; mag = sc3[2];
+    } else {
+        load_scalars<2>(full, sc, lds);
+    }
     if (check_full(la, sc)) return;
     const double rho = sc[0];                              // :81  rho = rw.r
+    if (GUARD && it != 0 && check_rho(la, rho, mag, rho_eps)) return;
     const double rhop = st->rho[(it + 1) & 1];             // :80
     const double alpha = st->alpha, omega = st->omega;
     if (leader()) st->rho[it & 1] = rho;
@@ -218,9 +228,10 @@ __global__ __launch_bounds__(kBlock) void k_update_p(LoopArgs la, ScalarSrc full
 }
 
 int launch_update_p(hipStream_t s, LoopArgs la, ScalarSrc full, int64_t n, const double *r,
-                    double *p, const double *v)
+                    double *p, const double *v, double rho_eps)
 {
-    CM_VEC_LAUNCH(all_aligned16(r, p, v), vec_grid(n), k_update_p<VEC>, la, full, n, r, p, v);
+    if (rho_eps > 0.0) CM_VEC_LAUNCH(all_aligned16(r, p, v), vec_grid(n), (k_update_p<VEC, true>), la, full, n, r, p, v, rho_eps);
+    CM_VEC_LAUNCH(all_aligned16(r, p, v), vec_grid(n), (k_update_p<VEC, false>), la, full, n, r, p, v, 0.0);
 }
 
 // alpha = rho/(rw.v); r -= alpha v; ||r||^2     pbicgstab.cu:106-111
@@ -264,12 +275,15 @@ int launch_half(hipStream_t s, LoopArgs la, ScalarSrc rv, int64_t n, double *r, 
 
 // omega = (t.r)/(t.t); x += omega s; r -= omega t; (rw.r, r.r); it++   pbicgstab.cu:135-151
 // s may alias r (no preconditioner): s is read before r is written, per element.
-template <int VEC>
+// GUARD (guarded solves): a third sum rides with the two, sum |rw_i| |r_i| -- the magnitudes rho = rw.r was summed from, term
+// by term in the same order -- and the partials have stride 3 (check_rho in the next k_update_p); the same bytes are moved.
+template <int VEC, bool GUARD>
 __global__ __launch_bounds__(kBlock) void k_full(LoopArgs la, ScalarSrc tt, int64_t n, double *x,
                                                  const double *sv, double *r, const double *t,
                                                  const double *rw, double *parts, ScalarSrc half, const double *pw)
 {
-    __shared__ double lds[8];
+    constexpr int NS = GUARD ? 3 : 2;
+    __shared__ double lds[4 * NS];
     LoopState *st = la.st;
     // With a half-step test inside this launch (fused loop) the state is read once per workgroup, so a
     // workgroup can never split into waves that saw the leader's exit and waves that go on to update x and r.
@@ -285,7 +299,7 @@ __global__ __launch_bounds__(kBlock) void k_full(LoopArgs la, ScalarSrc tt, int6
     double sc[2];
     load_scalars<2>(tt, sc, lds);
     const double omega = step_omega(sc[0], sc[1]);
-    double acc[2] = {0.0, 0.0};
+    double acc[NS] = {};
     // PW: the half step's x += alpha pw (:110), left out by k_half, first -- then :139: two roundings in the reference's order
     auto sweep = [&](auto with_pw) {
         constexpr bool PW = decltype(with_pw)::value != 0;
@@ -304,16 +318,17 @@ __global__ __launch_bounds__(kBlock) void k_full(LoopArgs la, ScalarSrc tt, int6
                 rr[j] = step_r_full(rr[j], tv[j], omega);
                 dot_step(acc[0], ww[j], rr[j]);            // :81 of i+1
                 dot_step(acc[1], rr[j], rr[j]);            // :142
+                if constexpr (GUARD) dot_step(acc[2], fabs(ww[j]), fabs(rr[j]));
             }
             store_row<W>(x, i, xx, kAll); store_row<W>(r, i, rr, kAll);
         });
     };
     if (pw) sweep(Width<1>{});
     else sweep(Width<0>{});
-    block_sum<2>(acc, lds);
+    block_sum<NS>(acc, lds);
     if (threadIdx.x == 0) {
-        parts[2 * blockIdx.x] = acc[0];
-        parts[2 * blockIdx.x + 1] = acc[1];
+#pragma unroll
+        for (int k = 0; k < NS; k++) parts[NS * blockIdx.x + k] = acc[k];
     }
     if (leader()) {
         st->omega = omega;
@@ -323,11 +338,13 @@ __global__ __launch_bounds__(kBlock) void k_full(LoopArgs la, ScalarSrc tt, int6
 }
 
 int launch_full(hipStream_t s, LoopArgs la, ScalarSrc tt, int64_t n, double *x, const double *sv,
-                double *r, const double *t, const double *rw, double *parts, int *nparts, ScalarSrc half, const double *pw)
+                double *r, const double *t, const double *rw, double *parts, int *nparts, ScalarSrc half, const double *pw,
+                bool guard)
 {
     const int g = vec_grid(n);
     *nparts = g;
-    CM_VEC_LAUNCH(all_aligned16(x, sv, r, t, rw, pw), g, k_full<VEC>, la, tt, n, x, sv, r, t, rw, parts, half, pw);
+    if (guard) CM_VEC_LAUNCH(all_aligned16(x, sv, r, t, rw, pw), g, (k_full<VEC, true>), la, tt, n, x, sv, r, t, rw, parts, half, pw);
+    CM_VEC_LAUNCH(all_aligned16(x, sv, r, t, rw, pw), g, (k_full<VEC, false>), la, tt, n, x, sv, r, t, rw, parts, half, pw);
 }
 
 // ---------------------------------------------------------------- BLAS-1 pieces

@@ -12,6 +12,8 @@
 //   iterate_fused     three launches per iteration                      (short rows, <= 3e5 rows, one GPU, M = I)
 //   iterate_reference five launches per iteration                       (everything else; + M^-1, + exchanges when sharded)
 //   iterate_pipelined four launches per iteration, reductions beside the SpMVs (sharded runs)
+// A guarded solve (CUDAMAT_FLAG_GUARD, or the switch GUARD = 1) always takes iterate_reference, with the GUARD instantiations
+// of k_update_p / k_full; cudamat_solver_solve strings its segments together (restarts on a lost rho, verified convergence).
 // The host-side loop (run_host_loop) is shared by the last three: it enqueues iteration k and looks at the progress
 // word iteration k - kLag published through pinned memory (wait_progress, which the batched loop of loops_batch.hip
 // calls too, as it does the history and statistics rules below), so the stream never drains; once a stopping test fires on
@@ -100,7 +102,8 @@ struct Solve {
     const Config *cfg = nullptr;
     hipStream_t st = nullptr;
     int n = 0;
-    bool profile = false, sharded = false, perm = false, pipelined = false, pipe_pc = false;
+    bool profile = false, sharded = false, perm = false, pipelined = false, pipe_pc = false, guard = false;
+    double rho_eps = 0.0;              // guarded solves: GUARD_RHO_ULPS * 2^-52 (check_rho)
     double *x_user = nullptr;          // the caller's x (x itself is the level-major copy while perm)
     int hist_base = 0;
     LoopArgs la{};
@@ -203,6 +206,8 @@ int Solve::setup()
     sharded = s->sharded;
     pipelined = loop == CUDAMAT_LOOP_PIPELINED;
     pipe_pc = pipelined && precond != CUDAMAT_PRECOND_NONE;
+    guard = (flags & CUDAMAT_FLAG_GUARD) != 0;
+    rho_eps = guard ? (double)cfg->guard_rho_ulps * 0x1p-52 : 0.0;       // (exact: at most 2^52 ulps)
     la = LoopArgs{s->st, s->hist + hist_base, s->hist_cap - hist_base, loop, (flags & CUDAMAT_FLAG_NO_EXIT) ? 1 : 0, s->snap_dev, kRing, 0};
     for (int i = 0; i < kRing; i++) s->snap_host[i] = 0ULL;
 
@@ -464,7 +469,7 @@ int Solve::iterate_fused()
 int Solve::iterate_reference()
 {
     // rho, beta, p = r + beta (p - omega v)                     :80-89
-    CM_TRY(launch_update_p(st, la, full_src, n, s->r, s->p, s->v));
+    CM_TRY(launch_update_p(st, la, full_src, n, s->r, s->p, s->v, rho_eps));     // (guarded: + the test on rho)
     const double *pw = s->p;
     if (precond) {                                            // :92-98
         prof_mark();
@@ -526,8 +531,9 @@ int Solve::iterate_reference()
         tt_src = ScalarSrc{s->red + 2, 0, 1};
     }
     // omega, x += alpha pw, x += omega s, r -= omega t, (rw.r, ||r||), i++     :110, :137-151
-    CM_TRY(launch_full(st, la, tt_src, n, x, sv, s->r, s->t, s->rw, s->parts_full, &np_full, ScalarSrc{nullptr, 0, 1}, pw));
-    full_src = ScalarSrc{s->parts_full, np_full, 2};
+    // (guarded: + sum |rw_i| |r_i| as a third partial)
+    CM_TRY(launch_full(st, la, tt_src, n, x, sv, s->r, s->t, s->rw, s->parts_full, &np_full, ScalarSrc{nullptr, 0, 1}, pw, guard));
+    full_src = ScalarSrc{s->parts_full, np_full, guard ? 3 : 2};
     if (sharded) {
         CM_TRY(launch_reduce_parts(st, full_src, 2, s->red + 4, 0));
         CM_TRY(allreduce(s, s->red + 4, 2));
@@ -592,6 +598,7 @@ int Solve::finish(bool *precond_gave_up, cudamat_stats *out)
         CM_HIP(hipStreamSynchronize(st));
     }
     const LoopState fin = s->st_ring[0];
+    s->last_state = fin.state;
     if (pipelined && fin.state == 1) {      // left through the half step: the iterate is x + alpha p, kept in xh
         CM_HIP(hipMemcpyAsync(x, s->pxh, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
         CM_HIP(hipStreamSynchronize(st));
@@ -684,7 +691,7 @@ int solve_once(cudamat_solver *s, const double *b, double *x, int precond, int l
     CM_TRY(q.setup());
     Range range_loop("cudamat: iteration loop (enqueue + lagged checks)");
     if (q.pipelined) CM_TRY(q.pipelined_prologue());
-    q.loop_form = q.wants_fused() ? 1 : 0;
+    q.loop_form = !q.guard && q.wants_fused() ? 1 : 0;       // (a guarded solve: five launches, whatever the system's size)
     if (q.loop_form == 1 && !s->v2) {
         const size_t nb = sizeof(double) * (size_t)(s->n_pad > 0 ? s->n_pad : 1);
         CM_TRY(dev_alloc((void **)&s->v2, nb));
@@ -753,6 +760,16 @@ int solve_guarded(cudamat_solver *s, const double *b, double *x, int precond, in
 extern "C" int cudamat_solver_solve(cudamat_solver *s, const double *b, double *x, int precond,
                                     int loop, int maxit, double tol, int flags, cudamat_stats *out)
 {
+    CM_ARG(s, "null pointer");
+    if (s->ctx->cfg.guard) flags |= CUDAMAT_FLAG_GUARD;
+    const bool guard = (flags & CUDAMAT_FLAG_GUARD) != 0;
+    const bool exits = !(flags & CUDAMAT_FLAG_NO_EXIT);
+    if (guard) {
+        CM_ARG(loop != CUDAMAT_LOOP_PIPELINED,
+               "CUDAMAT_FLAG_GUARD does not cover CUDAMAT_LOOP_PIPELINED, which verifies its iterates itself");
+        CM_ARG(!s->sharded, "CUDAMAT_FLAG_GUARD does not cover sharded solvers yet (its third sum would have to ride in the all-reduce)");
+        CM_ARG(!exits || tol > 0.0, "CUDAMAT_FLAG_GUARD needs tol > 0: its restarts aim at tol * ||r0||");
+    }
     cudamat_stats st0;
     CM_TRY(solve_guarded(s, b, x, precond, loop, maxit, tol, flags, &st0, 0.0));
     // The pipelined loop carries r, w = A r, s = A p, z = A s by recurrences; over a few hundred iterations their rounding
@@ -760,7 +777,7 @@ extern "C" int cudamat_solver_solve(cudamat_solver *s, const double *b, double *
     // against a tolerance of 1e-9).  So an iterate that this loop calls converged is VERIFIED: a restart from it computes
     // the true residual b - A x (one SpMV); within twice the target it is accepted, otherwise the loop goes on from
     // there towards the same absolute target -- at most three times, within the caller's maxit.
-    if (loop == CUDAMAT_LOOP_PIPELINED && st0.converged && !(flags & CUDAMAT_FLAG_NO_EXIT) && st0.nrm0 > 0.0) {
+    if (loop == CUDAMAT_LOOP_PIPELINED && st0.converged && exits && st0.nrm0 > 0.0) {
         const double target = tol * st0.nrm0;
         for (int r = 0; r < 3 && st0.converged && st0.iters < maxit; r++) {
             cudamat_stats st2;
@@ -770,6 +787,47 @@ extern "C" int cudamat_solver_solve(cudamat_solver *s, const double *b, double *
             st0.nrm = st2.nrm;                       // the true residual of the verified iterate (st2.nrm0) or the loop's last
             if (st2.iters == 0 && st2.converged) break;
             st0.restarts++;
+            st0.iters += st2.iters;
+            st0.converged = st2.converged;
+            st0.half_exit = st2.half_exit;
+            st0.breakdown = st2.breakdown;
+        }
+    }
+    // Guarded solves of the reference loops: the same restart -- Solve::setup forms r = b - (A + d) x, rw = p = r and
+    // rho = alpha = omega = 1 from the current x, towards the FIRST segment's absolute target, the history appended --
+    //   - after a segment that the test on rho ended (state 4; rho_restarts): such a segment has completed at least one
+    //     iteration, so the restarts are bounded by maxit;
+    //   - after a segment that reported convergence, to verify it as above (restarts, at most three).  A segment that
+    //     starts within twice the target ends at once, 'converged', with its true residual as nrm: only that ends a guarded
+    //     solve with converged = 1.  When the three are spent, or no iteration is left, one more evaluation of the true
+    //     residual (a segment of no iterations) decides, and a failure returns converged = 0 with that residual as nrm.
+    // Whatever else ends a segment (maxit, a refused range, a NaN residual, the |omega| guard) ends the solve as ever.
+    if (guard && exits) {
+        const double target = tol * st0.nrm0;
+        int state = s->last_state;
+        while (target > 0.0 && (state == 4 || st0.converged)) {
+            const bool verify = state != 4;
+            const int left = verify && st0.restarts >= 3 ? 0 : maxit - st0.iters;
+            if (!verify) st0.rho_restarts++;
+            cudamat_stats st2;
+            CM_TRY(solve_guarded(s, b, x, precond, loop, left, tol, flags & ~CUDAMAT_FLAG_X0_ONES, &st2, target));
+            state = s->last_state;
+            st0.t_solve += st2.t_solve;
+            st0.t_total += st2.t_total;
+            st0.nrm = st2.nrm;
+            if (state == 2 && st2.iters == 0) {      // the true residual of x is within twice the target: done
+                                                     // (not a half-step exit of iteration 0, which reports 0 iterations too)
+                st0.converged = 1;
+                st0.breakdown = 0;
+                break;
+            }
+            if (verify && left == 0) {               // the last evaluation failed: x is returned as what it is
+                st0.converged = 0;
+                st0.half_exit = 0;
+                st0.breakdown = st2.breakdown;       // (a true residual that is not finite: init_refusal)
+                break;
+            }
+            if (verify) st0.restarts++;
             st0.iters += st2.iters;
             st0.converged = st2.converged;
             st0.half_exit = st2.half_exit;

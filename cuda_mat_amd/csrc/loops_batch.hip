@@ -22,7 +22,7 @@
 // against the same number of iterations of the loop a single solve uses (cudamat_solver_solve, which picks the one- or
 // three-launch loops of small systems), and runs batched only when that is faster than kc single solves.  Everything the batched
 // form does not cover (ILU(0) unless MANY_PRECOND asks for it, and then hybrid factors in level-major spaces; block-Jacobi ILU(0),
-// the pipelined loop, sharded solvers, the DEBUG / PROFILE flags) and a failed allocation of its buffers run column by column: cudamat_solver_solve once per column, bit for bit what a caller's loop would do.
+// the pipelined loop, sharded solvers, the DEBUG / PROFILE / GUARD flags) and a failed allocation of its buffers run column by column: cudamat_solver_solve once per column, bit for bit what a caller's loop would do.
 // Per-column shifts (D != NULL): the batched form transposes D into one more interleaved block (many.dk, padding columns 0) and
 // every SpMM of the loop -- r0 = b - (A0 + I d_j) x0_j included -- adds dk_j .* x_j where it would add d .* x_j; the solver's own
 // shift is not read.  Column by column, the solver's shift points at column j of D for the length of that column's solve (a
@@ -430,7 +430,10 @@ extern "C" int cudamat_solver_solve_shifts(cudamat_solver *s, int nrhs, const do
     std::vector<std::vector<double>> hists((size_t)nrhs);
     double t_solve = 0.0, t_tune = 0.0;
     bool any_batched = false;
-    const bool one_gpu = !s->sharded && s->n_cols == s->n && s->n > 0 && !(flags & (CUDAMAT_FLAG_DEBUG | CUDAMAT_FLAG_PROFILE));
+    // (a guarded solve -- CUDAMAT_FLAG_GUARD or the switch GUARD -- runs column by column: each column a guarded cudamat_solver_solve)
+    const bool guarded = (flags & CUDAMAT_FLAG_GUARD) || cfg.guard;
+    const bool one_gpu = !s->sharded && s->n_cols == s->n && s->n > 0 && !(flags & (CUDAMAT_FLAG_DEBUG | CUDAMAT_FLAG_PROFILE)) &&
+                         !guarded;
     const bool plain = precond == CUDAMAT_PRECOND_NONE && (loop == CUDAMAT_LOOP_PBICGSTAB || loop == CUDAMAT_LOOP_PBICGSTAB2) && one_gpu;
     // ILU(0): only when MANY_PRECOND asks for it (0 = columns, the default: today's behaviour bit for bit), the reference loop,
     // and factors the multi-column triangular solves cover (trsm.h); set up on first use as Solve::setup does it

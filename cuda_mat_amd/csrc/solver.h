@@ -101,6 +101,7 @@ struct cudamat_solver {
     int hist_cap = 0;
     int hist_count = 0;
     int last_loop = 0;
+    int last_state = 0;        // LoopState.state the last solve segment ended in (4: the test on rho asked for a restart)
 
     // profiling events
     std::vector<hipEvent_t> prof_ev;

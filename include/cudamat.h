@@ -79,6 +79,13 @@ extern "C" {
                                        fixed-length timing windows (bench.py)           */
 #define CUDAMAT_FLAG_X0_ONES    8   /* start from x0 = 1 (pbicgstab.cu:306-308,827-831)
                                        instead of the contents of x                     */
+#define CUDAMAT_FLAG_GUARD      16  /* guarded solve (LOOP_PBICGSTAB / LOOP_PBICGSTAB2, one GPU):
+                                       the loop restarts from the true residual b - A x when rho = rw.r has lost its last
+                                       significant bit (|rho| <= GUARD_RHO_ULPS * 2^-52 * sum |rw_i r_i|, the textbook
+                                       BiCGSTAB breakdown), and converged = 1 is returned only for an iterate whose TRUE
+                                       residual is within twice tol * ||r0||.  Needs tol > 0 (or FLAG_NO_EXIT, which runs
+                                       the guarded kernels without ever taking the test).  The switch GUARD = 1 sets it
+                                       for every solve of a context.  Off by default: a departure from the reference.    */
 
 typedef struct cudamat_ctx cudamat_ctx;         /* device + stream + reduction workspace  */
 typedef struct cudamat_solver cudamat_solver;   /* one HBM-resident linear system          */
@@ -121,8 +128,9 @@ typedef struct cudamat_stats {
                             * loop took beyond this                                                            */
     int loop_fallbacks;    /* solves of this solver that were discarded and redone with the three-launch loop because a
                             * grid barrier of the single-launch loop ran into its bound (GPU shared; 0 in a healthy run) */
-    int restarts;          /* pipelined loop only: how often an iterate it called converged failed the check of its TRUE
-                            * residual (one SpMV) and the loop was restarted from it (0 in most solves, at most 3)       */
+    int restarts;          /* how often an iterate the loop called converged failed the check of its TRUE residual (one
+                            * SpMV) and the loop was restarted from it (0 in most solves, at most 3): the pipelined loop
+                            * always checks, the reference loops under CUDAMAT_FLAG_GUARD                                */
     /* where a call's time went beyond t_analysis / t_factor / t_solve (the reference prints "total delta time" next to
      * "algorithm delta time", example.cpp:364-365; pbicgstab.cu:365-374):                                              */
     double t_upload;       /* s, cudamat_solve / cudamat_solve_sharded: device allocations + host-to-device copies       */
@@ -136,6 +144,8 @@ typedef struct cudamat_stats {
      * application of L^-1 (U^-1) = `groups` dependency-driven launches over the entries inside a group + `groups - 1`
      * blocked two-phase SpMVs over the entries whose column lies in an earlier group.  0: the factor is not split.    */
     int trsv_groups_l;     int trsv_groups_u;
+    int rho_restarts;      /* CUDAMAT_FLAG_GUARD: how often the test on rho fired and the solve was restarted from the true
+                            * residual of its iterate (0 without the flag)                                               */
 } cudamat_stats;
 
 /* Collectives for a row-sharded solve.  Either supplied by the host program (e.g.
@@ -321,8 +331,9 @@ int cudamat_solver_solve(cudamat_solver *s, const double *b, double *x, int prec
                          int loop, int maxit, double tol, int flags, cudamat_stats *st);
 /* residual-norm history of the last solve: LOOP_PBICGSTAB: hist[2i], hist[2i+1] =
  * norm after the half / full step of iteration i; LOOP_PBICGSTAB2: hist[i].  (LOOP_PIPELINED
- * as LOOP_PBICGSTAB; when that loop was restarted after the check of its true residual --
- * cudamat_stats.restarts -- the segments follow one another.)
+ * as LOOP_PBICGSTAB.  When a solve was restarted -- after the check of its true residual,
+ * cudamat_stats.restarts, or under CUDAMAT_FLAG_GUARD after the test on rho, cudamat_stats.rho_restarts --
+ * the segments follow one another.)
  * Copies min(cap, available) doubles to the HOST buffer, returns the count in *count. */
 int cudamat_solver_history(cudamat_solver *s, double *hist_host, int cap, int *count);
 
@@ -336,8 +347,8 @@ int cudamat_solver_spmm(cudamat_solver *s, int nrhs, const double *X, int ldx, d
  * stopping tests and history.  PRECOND_NONE with LOOP_PBICGSTAB / LOOP_PBICGSTAB2 on one GPU may run batched (up to 8
  * columns per launch; a column's result then depends on its own data only, not on the batch); so may PRECOND_ILU0 with
  * LOOP_PBICGSTAB when the switch MANY_PRECOND = batched | auto asks for it (default: columns) and the factors are covered
- * (see cudamat_solver_precond_apply_many); everything else, and the switch MANY_FORM = columns, runs cudamat_solver_solve
- * once per column.  MANY_FORM = auto (default) times both forms at the
+ * (see cudamat_solver_precond_apply_many); everything else -- CUDAMAT_FLAG_GUARD included: each column is then a guarded
+ * solve --, and the switch MANY_FORM = columns, runs cudamat_solver_solve once per column.  MANY_FORM = auto (default) times both forms at the
  * first such call of the solver (per loop and batch width) and takes the faster.  st: nrhs entries or NULL -- per column
  * iters, half_exit, converged, breakdown, nrm0, nrm, spmv_mode; t_solve / t_total are those of the whole call, t_tune
  * includes the timing of the form choice.  *form (may be NULL): 1 when columns ran batched, 0 column by column.        */
@@ -360,7 +371,7 @@ int cudamat_solver_trsm_kernel(cudamat_solver *s, int nrhs, char *name, int cap)
  * cudamat_solver_solve_shifts: (A0 + diag(D_j)) x_j = b_j, everything else as cudamat_solver_solve_many (statistics, histories,
  * *form, MANY_FORM -- auto times both forms with shifts in place, once per solver, loop and batch width).  The batched form
  * covers what it covers there; the rest (MANY_FORM = columns, LOOP_PIPELINED, sharded solvers -- D then holds the local rows --,
- * FLAG_DEBUG / FLAG_PROFILE, no room for the buffers) runs set_shift(D_j) + cudamat_solver_solve per column, bit for bit.  The
+ * FLAG_DEBUG / FLAG_PROFILE / FLAG_GUARD, no room for the buffers) runs set_shift(D_j) + cudamat_solver_solve per column, bit for bit.  The
  * (A0 + I d) variant has no preconditioner (pbicgstab.h:110): precond != CUDAMAT_PRECOND_NONE with D is CUDAMAT_ERR_ARG.      */
 int cudamat_solver_spmm_shifts(cudamat_solver *s, int nrhs, const double *X, int ldx, const double *D, int ldd, double *Y,
                                int ldy);
