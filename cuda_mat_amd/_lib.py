@@ -144,6 +144,7 @@ _SIGS = {
     "cudamat_plan_cache_clear": (C.c_int, []),
     "cudamat_pool_trim": (C.c_int, []),
     "cudamat_mem_info": (C.c_int, [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "cudamat_mem_live": (C.c_int, [C.POINTER(C.c_size_t)]),
     "cudamat_poisson5_nnz": (C.c_int64, [C.c_int, C.c_int]),
     "cudamat_gen_poisson5": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, _P]),
     "cudamat_rand_row_nnz": (C.c_int, [C.c_int64, C.c_int]),

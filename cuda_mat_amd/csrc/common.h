@@ -22,6 +22,7 @@ bool pool_split(void *p, size_t offset);      // one block in use becomes two, e
 unsigned pool_generation();                   // moves whenever a segment went back to the driver
 bool pool_enabled();
 void pool_trim();                 // free blocks back to the driver (cudamat_plan_cache_clear, out-of-memory retries)
+size_t pool_live();               // allocations of this library that are in use: every hipMalloc counted, every hipFree discounted
 size_t pool_free_bytes();         // what the current device's pool could hand out without asking the driver
 
 }  // namespace cm
@@ -122,15 +123,17 @@ enum Check { CHECK_NONE = 0, CHECK_HALF = 1, CHECK_FULL = 2 };
 
 }  // namespace cm
 
+#include "devmem.h"      // the allocator and the owners: after the declarations above, which it uses
+
 struct cudamat_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    double *parts = nullptr;   // kMaxParts * 2 doubles scratch for the standalone dot/nrm2
+    cm::DevBuf<double> parts;  // kMaxParts * 2 doubles scratch for the standalone dot/nrm2
     // 64 KB of device scratch for the small read-backs of the set-up stages (flags, counters, a value-dictionary probe table):
     // those stages then neither allocate nor free -- hipFree waits for EVERY stream of the device, and the host-pointer entry
     // point runs them while an upload is in flight on another stream (dropin.hip).  One user at a time: the context's stream.
-    void *scratch = nullptr;
+    cm::DevBuf<char> scratch;
     cm::Config cfg;            // the switches everything running on this context reads (config.h)
     // does this device's LDS serve equal addresses of one ds_add_f64 in lane order?  (-1 not probed yet, 1 yes, 0 no:
     // spmv_pb.hip pb_strict_for; the blocked SpMV's default phase 2 is bit-exact only when it does)

@@ -127,13 +127,12 @@ extern "C" int cudamat_ctx_create(int device, void *stream, cudamat_ctx **out)
         if (e != hipSuccess) { delete c; return fail_hip(e, "hipStreamCreate", __FILE__, __LINE__); }
         c->own_stream = true;
     }
-    hipError_t e = hipMalloc((void **)&c->parts, sizeof(double) * 2 * kMaxParts);
-    if (e == hipSuccess) e = hipMalloc(&c->scratch, kCtxScratchBytes);
-    if (e != hipSuccess) {
-        if (c->parts) CM_DROP(hipFree(c->parts));
+    int rc = c->parts.alloc(2 * kMaxParts);
+    if (rc == CUDAMAT_OK) rc = c->scratch.alloc(kCtxScratchBytes);
+    if (rc != CUDAMAT_OK) {
         if (c->own_stream) CM_DROP(hipStreamDestroy(c->stream));
         delete c;
-        return fail_hip(e, "hipMalloc(parts)", __FILE__, __LINE__);
+        return rc;
     }
     *out = c;
     return CUDAMAT_OK;
@@ -144,8 +143,8 @@ extern "C" int cudamat_ctx_destroy(cudamat_ctx *ctx)
     if (!ctx) return CUDAMAT_OK;
     CM_DROP(hipSetDevice(ctx->device));
     CM_DROP(hipStreamSynchronize(ctx->stream));
-    CM_DROP(hipFree(ctx->parts));
-    CM_DROP(hipFree(ctx->scratch));
+    ctx->parts.reset();
+    ctx->scratch.reset();
     if (ctx->own_stream) CM_DROP(hipStreamDestroy(ctx->stream));
     delete ctx;
     return CUDAMAT_OK;
@@ -200,13 +199,7 @@ extern "C" int cudamat_malloc(cudamat_ctx *ctx, size_t bytes, void **dev)
 {
     CM_ARG(ctx && dev, "null pointer");
     CM_HIP(hipSetDevice(ctx->device));
-    *dev = nullptr;
-    hipError_t e = hipMalloc(dev, bytes ? bytes : 16);
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? CUDAMAT_ERR_NOMEM : CUDAMAT_ERR_HIP;
-    }
-    return CUDAMAT_OK;
+    return dev_alloc((char **)dev, bytes);
 }
 
 extern "C" int cudamat_free(cudamat_ctx *ctx, void *dev)
@@ -327,10 +320,9 @@ extern "C" int cudamat_spmv(cudamat_ctx *ctx, int n, const int *rowptr, const in
     a.loop = LoopArgs{nullptr, nullptr, 0, 0, 0};
     a.check = CHECK_NONE;
     int rc = launch_spmv(ctx->stream, plan, a);
-    if (plan.tiles) {                      // the tile tables live only for this call
+    if (plan.tiles) {                      // the tile tables live only for this call: `plan` releases them
         const int rc_sync = CM_RC(hipStreamSynchronize(ctx->stream));
         if (!rc) rc = rc_sync;
-        plan_spmv_free(&plan);
     }
     return rc;
 }

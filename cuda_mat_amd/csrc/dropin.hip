@@ -243,6 +243,13 @@ extern "C" int cudamat_mem_info(int device, size_t *driver_free, size_t *driver_
     return CUDAMAT_OK;
 }
 
+extern "C" int cudamat_mem_live(size_t *allocations)
+{
+    CM_ARG(allocations, "null pointer");
+    *allocations = pool_live();
+    return CUDAMAT_OK;
+}
+
 namespace {
 
 struct HostSystem {
@@ -263,15 +270,16 @@ int build_or_reuse_candidate(cudamat_ctx *ctx, const Config &cfg, const HostSyst
 {
     const double t0 = now_s();
     const int n = h.n, nnz = h.nnz, base = h.base;
-    int *d_rp = nullptr, *d_ci = nullptr, *flag = nullptr, *tmp = nullptr;
-    double *d_val = nullptr;
+    DevBuf<int> d_rp, d_ci, flag, tmp;         // the scratch copies of this call: released on the way out
+    DevBuf<double> d_val;
     int rc = CUDAMAT_OK;
     *reused = false;
     *s_out = nullptr;
+    CM_HIP(hipSetDevice(ctx->device));
     do {
-        if ((rc = cudamat_malloc(ctx, sizeof(int) * ((size_t)n + 1), (void **)&d_rp))) break;
-        if ((rc = cudamat_malloc(ctx, sizeof(int) * (size_t)nnz, (void **)&d_ci))) break;
-        if ((rc = cudamat_malloc(ctx, sizeof(double) * (size_t)nnz, (void **)&d_val))) break;
+        if ((rc = d_rp.alloc((size_t)n + 1))) break;
+        if ((rc = d_ci.alloc((size_t)nnz))) break;
+        if ((rc = d_val.alloc((size_t)nnz))) break;
         {
             Uploader up;
             up.add(d_rp, h.iA, sizeof(int) * ((size_t)n + 1));            // pbicgstab.cu:313-315
@@ -287,10 +295,10 @@ int build_or_reuse_candidate(cudamat_ctx *ctx, const Config &cfg, const HostSyst
         // the cached solver holds the matrix rebased to 0: compare the uploaded arrays with it on the device
         int hflag = 1;
         cudamat_solver *c = g_cache.s;
-        if ((rc = cudamat_malloc(ctx, sizeof(int), (void **)&flag))) break;
+        if ((rc = flag.alloc(1))) break;
         // (a flag word that could not be cleared would make any matrix look "different": fail the call instead)
         if ((rc = CM_RC(hipMemsetAsync(flag, 0, sizeof(int), ctx->stream)))) break;
-        rc = cudamat_malloc(ctx, sizeof(int) * ((size_t)nnz > (size_t)n + 1 ? (size_t)nnz : (size_t)n + 1), (void **)&tmp);
+        rc = tmp.alloc((size_t)nnz > (size_t)n + 1 ? (size_t)nnz : (size_t)n + 1);
         if (!rc) rc = launch_rebase(ctx->stream, (int64_t)n + 1, d_rp, -base, tmp);
         if (!rc) rc = device_equal(ctx->stream, tmp, c->rp, sizeof(int) * ((size_t)n + 1), flag);
         if (!rc && nnz) rc = launch_rebase(ctx->stream, nnz, d_ci, -base, tmp);
@@ -309,9 +317,7 @@ int build_or_reuse_candidate(cudamat_ctx *ctx, const Config &cfg, const HostSyst
             rc = cudamat_solver_create(ctx, n, n, nnz, d_rp, d_ci, d_val, base, s_out);
         }
     } while (0);
-    void *ptrs[] = {d_rp, d_ci, d_val, flag, tmp};
-    for (void *p : ptrs)
-        if (p) cudamat_free(ctx, p);
+    CM_DROP(hipStreamSynchronize(ctx->stream));        // (nothing enqueued above may outlive the scratch copies)
     return rc;
 }
 
@@ -467,9 +473,7 @@ int build_beside_upload(cudamat_ctx *ctx, const Config &cfg, const HostSystem &h
         if (pb_open && !blocked) { pb_build_abort(&pb); pb_open = false; }        // another form: ensure_spmv_mode decides at the solve
         if (pb_open && !piecewise) {
             if ((rc = ensure_valdict(s))) break;
-            if (s->vd.n > 0) {                           // 8-bit indices instead of the fp64 values
-                CM_DROP(hipFree(pb.p.pv));
-                pb.p.pv = nullptr;
+            if (s->vd.n > 0) {                           // 8-bit indices instead of the fp64 values (which pb_build_values releases)
                 if ((rc = pb_build_values(st, &pb, &s->vd))) { pb_open = false; break; }
             }
             if ((rc = pb_build_fill(st, &pb, s->rp, s->ci, s->val, &s->vd, 0, pb.p.NSUB))) { pb_open = false; break; }
@@ -516,7 +520,7 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
         CM_TRY(cudamat_ctx_create(0, nullptr, &ctx));
         ctx->cfg.pb_place = cfg.pb_place;          // (the one switch this entry point overrides, see cudamat_solve)
     }
-    double *d_b = nullptr, *d_x = nullptr, *d_d = nullptr;
+    DevBuf<double> d_b, d_x, d_d;              // the call's right-hand sides, iterates and shifts on the device
     cudamat_solver *s = nullptr;
     bool reused = false, built_ilu = false;
     int rc = CUDAMAT_OK;
@@ -524,9 +528,10 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
     memset(&st, 0, sizeof(st));
     double t_up = 0.0;
     do {
-        if ((rc = cudamat_malloc(ctx, sizeof(double) * (size_t)n * (size_t)h.nrhs, (void **)&d_b))) break;
-        if ((rc = cudamat_malloc(ctx, sizeof(double) * (size_t)n * (size_t)h.nrhs, (void **)&d_x))) break;
-        if (h.d && (rc = cudamat_malloc(ctx, sizeof(double) * h.d_count(), (void **)&d_d))) break;
+        if ((rc = CM_RC(hipSetDevice(ctx->device)))) break;
+        if ((rc = d_b.alloc((size_t)n * (size_t)h.nrhs))) break;
+        if ((rc = d_x.alloc((size_t)n * (size_t)h.nrhs))) break;
+        if (h.d && (rc = d_d.alloc(h.d_count()))) break;
         if (candidate) {
             if ((rc = build_or_reuse_candidate(ctx, cfg, h, d_b, d_x, d_d, &s, &reused, &t_up))) break;
         } else {
@@ -570,17 +575,17 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
         g_cache.n = n; g_cache.nnz = nnz; g_cache.base = base;
         g_cache.d_d = nullptr;
         if (!h.shifts) {
-            g_cache.d_d = d_d;           // the solver points at it (set_shift); replaced by the next call
-            d_d = nullptr;
+            g_cache.d_d = d_d.release(); // the solver points at it (set_shift); replaced by the next call
         }
     } else {
         if (s) cudamat_solver_destroy(s);
         if (old && old != s) cudamat_solver_destroy(old);
         g_cache.s = nullptr;
     }
-    void *ptrs[] = {d_b, d_x, d_d};
-    for (void *p : ptrs)
-        if (p) cudamat_free(ctx, p);
+    CM_DROP(hipStreamSynchronize(ctx->stream));
+    d_b.reset();                         // (before the context may go)
+    d_x.reset();
+    d_d.reset();
     if (!g_cache.s) {                    // nothing kept: the context goes too
         if (g_cache.d_d) { cudamat_free(ctx, g_cache.d_d); g_cache.d_d = nullptr; }
         cudamat_ctx_destroy(ctx);

@@ -26,7 +26,7 @@ inline int pick_lanes(double mean)
 struct TriHost {   // host-side launch plan kept next to the TriFactor
     std::vector<int> seg_begin, seg_end;   // level ranges; a segment with end-begin > 1 is a small-level run
     std::vector<int> seg_group;            // group of every segment (segments never straddle groups)
-    int *level_ptr_dev = nullptr;
+    DevBuf<int> level_ptr_dev;
     int lanes = 8;
     // hybrid solve (see split_factor): levels are cut into a few consecutive GROUPS; entries whose column
     // belongs to an EARLIER group ("far") are applied per group by one blocked two-phase SpMV, only the
@@ -34,15 +34,15 @@ struct TriHost {   // host-side launch plan kept next to the TriFactor
     bool hybrid = false;
     std::vector<int> grp_level;            // K+1 level boundaries of the groups
     std::vector<PbPlan> far;               // far[g]: rows of group g x columns of groups < g
-    double *far_buf = nullptr;             // n doubles in level-major row order: far_g . out
-    int *lev_dev = nullptr;                // device: level of every original row (kept until the split)
+    DevBuf<double> far_buf;                // n doubles in level-major row order: far_g . out
+    DevBuf<int> lev_dev;                   // device: level of every original row (kept until the split)
     bool want_hybrid = false;              // this factor alone would take the hybrid solve (the two factors decide together)
     bool syncfree = false;                 // one dependency-driven launch per group instead of one launch per level
     int spin_limit = kSpinLimit;
     int nap = 2;                           // s_sleep between polls (0 / 1 / 2 / 4 measured equal within noise)
     int occ = 8;                           // workgroups per CU the dependency-driven launch may keep resident
     bool lds = false;                      // n <= 16384, narrow levels: the whole solve in one workgroup, x in LDS
-    unsigned *tickets = nullptr;           // device: one chunk-ticket counter per dependency-driven launch (group)
+    DevBuf<unsigned> tickets;              // device: one chunk-ticket counter per dependency-driven launch (group)
     int pb_strict = 0;                     // Config::pb_strict at set-up: passed to the far parts' phase 2
 };
 
@@ -56,23 +56,25 @@ inline bool segment_is_wide(const TriFactor &F, const TriHost &H, size_t g)
 
 }  // namespace cm
 
-// the launch plans hang off the solver as an opaque pointer (keeps solver.h light)
+// the launch plans hang off the solver behind a pointer (keeps solver.h light)
 struct IluPlans {
     cm::TriHost L, U;
-    int *err_host = nullptr, *err_dev = nullptr;   // pinned word a timed-out spin of k_trsv_syncfree sets
+    cm::PinnedBuf<int> err_host;                    // pinned word a timed-out spin of k_trsv_syncfree sets
+    int *err_dev = nullptr;                         // ... as the device sees it
     // between the pattern-only analysis and the numeric part of ilu0_setup (the drop-in call runs the former beside its upload)
-    int *d_flags = nullptr, *d_lev = nullptr;
+    cm::DevBuf<int> d_flags, d_lev;
     int maxrow_all = 0;
     bool analysed = false;
     std::vector<void *> deferred;                   // temporaries of an analysis that ran beside an upload, freed after it
     // level-major index spaces (both factors hybrid): U-position of every original row (the column map of the permuted
     // matrix, solver.hip ensure_perm_matrix), scratch vectors of the original-space wrapper (precond_apply_any)
-    int *posU = nullptr;
-    double *perm_a = nullptr, *perm_b = nullptr;
+    cm::DevBuf<int> posU;
+    cm::DevBuf<double> perm_a, perm_b;
+    ~IluPlans();                                    // flushes `deferred` (ilu.hip)
 };
 
 inline IluPlans *plans_of(cudamat_solver *s, bool create)
 {
-    if (!s->ilu_plans && create) s->ilu_plans = new IluPlans();
-    return (IluPlans *)s->ilu_plans;
+    if (!s->ilu_plans && create) s->ilu_plans.reset(new IluPlans());
+    return s->ilu_plans.get();
 }

@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "device.h"
 #include "ilu.h"
 
 using namespace cm;
@@ -51,17 +52,22 @@ static void afree(void *p)
     if (t_deferred) t_deferred->push_back(p);
     else CM_DROP(hipFree(p));
 }
-
-template <typename T>
-static int dalloc(T **p, size_t count)
+static void flush_deferred(std::vector<void *> &parked)
 {
-    *p = nullptr;
-    hipError_t e = hipMalloc((void **)p, sizeof(T) * (count ? count : 1));
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%zu bytes) failed: %s", sizeof(T) * count, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? CUDAMAT_ERR_NOMEM : CUDAMAT_ERR_HIP;
-    }
-    return CUDAMAT_OK;
+    for (void *q : parked) CM_DROP(hipFree(q));
+    parked.clear();
+}
+
+// a temporary of that analysis, and of nothing else: whatever is parked here stays allocated through the upload
+template <typename T>
+using AnalysisTmp = Owned<T, afree>;
+template <typename T>
+static int tmp_alloc(AnalysisTmp<T> &o, size_t count)
+{
+    T *p = nullptr;
+    const int rc = dev_alloc(&p, count);
+    o.adopt(p);
+    return rc;
 }
 
 // ---------------------------------------------------------------- analysis kernels
@@ -342,65 +348,40 @@ __global__ __launch_bounds__(64 * WAVES) void k_ilu0_level_fast(int row_begin, i
 }
 
 
-static void free_factor(TriFactor &F)
+}  // namespace cm
+
+// what an analysis beside an upload parked; the blocked far parts are PbPlans, which are freed by hand (spmv_pb.h)
+IluPlans::~IluPlans()
 {
-    void *ptrs[] = {F.rp, F.ci, F.val, F.row_of, F.dinv};
-    for (void *p : ptrs)
-        if (p) CM_DROP(hipFree(p));
-    if (F.lm && F.rhs_of) CM_DROP(hipFree(F.rhs_of));       // (in original space the maps alias row_of)
-    F = TriFactor();
+    cm::flush_deferred(deferred);
+    for (cm::TriHost *h : {&L, &U})
+        for (cm::PbPlan &fp : h->far) cm::pb_free(&fp);
 }
 
-static void free_levels(TriHost &H)
-{
-    if (H.lev_dev) CM_DROP(hipFree(H.lev_dev));
-    H.lev_dev = nullptr;
-}
+namespace cm {
 
 int ilu0_release(cudamat_solver *s)
 {
-    free_factor(s->L);
-    free_factor(s->U);
+    s->L = TriFactor();
+    s->U = TriFactor();
     pb_free(&s->pb_perm);
     valdict_free(&s->vd_perm);
-    if (s->x_perm) { CM_DROP(hipFree(s->x_perm)); s->x_perm = nullptr; }
-    if (s->b_perm) { CM_DROP(hipFree(s->b_perm)); s->b_perm = nullptr; }
+    s->x_perm.reset();
+    s->b_perm.reset();
     s->perm_ready = false;
     s->perm_failed = false;
-    if (s->lu) CM_DROP(hipFree(s->lu));
-    if (s->diag_pos) CM_DROP(hipFree(s->diag_pos));
-    if (s->pm_owned) {
-        if (s->pm_rp) CM_DROP(hipFree(s->pm_rp));
-        if (s->pm_ci) CM_DROP(hipFree(s->pm_ci));
-        if (s->pm_val) CM_DROP(hipFree(s->pm_val));
-    }
+    s->lu.reset();
+    s->diag_pos.reset();
+    s->pm_own_rp.reset();
+    s->pm_own_ci.reset();
+    s->pm_own_val.reset();
     s->pm_rp = s->pm_ci = nullptr;
     s->pm_val = nullptr;
     s->pm_nnz = 0;
     s->pm_owned = false;
     s->ilu_block = false;
-    s->lu = nullptr;
-    s->diag_pos = nullptr;
     s->has_ilu = false;
-    if (IluPlans *pl = (IluPlans *)s->ilu_plans) {
-        if (pl->L.level_ptr_dev) CM_DROP(hipFree(pl->L.level_ptr_dev));
-        if (pl->U.level_ptr_dev) CM_DROP(hipFree(pl->U.level_ptr_dev));
-        for (TriHost *h : {&pl->L, &pl->U}) {
-            for (PbPlan &fp : h->far) pb_free(&fp);
-            if (h->far_buf) CM_DROP(hipFree(h->far_buf));
-            if (h->tickets) CM_DROP(hipFree(h->tickets));
-            free_levels(*h);
-        }
-        if (pl->err_host) CM_DROP(hipHostFree(pl->err_host));
-        if (pl->d_flags) CM_DROP(hipFree(pl->d_flags));
-        if (pl->d_lev) CM_DROP(hipFree(pl->d_lev));
-        for (void *q : pl->deferred) CM_DROP(hipFree(q));
-        if (pl->posU) CM_DROP(hipFree(pl->posU));
-        if (pl->perm_a) CM_DROP(hipFree(pl->perm_a));
-        if (pl->perm_b) CM_DROP(hipFree(pl->perm_b));
-        delete pl;
-        s->ilu_plans = nullptr;
-    }
+    s->ilu_plans.reset();
     return CUDAMAT_OK;
 }
 
@@ -408,28 +389,6 @@ int ilu0_release(cudamat_solver *s)
 // scanned by one workgroup each, one workgroup over the tile totals, tile offsets added.  (Round 3: the host loops over
 // 1e7 counts -- two device-to-host copies, a serial scan, two uploads per factor -- were ~40 ms each at C5.)
 constexpr int kScanTile = 4096;
-
-__device__ __forceinline__ int wg_exclusive_scan(int v, int *lds_waves, int *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) lds_waves[wave] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < kBlock / 64; w++) {
-        const int t = lds_waves[w];
-        if (w < wave) base += t;
-        tot += t;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
 
 __global__ __launch_bounds__(kBlock) void k_scan_tiles(int n, const int *in, int *out, int *tile_sum)
 {
@@ -440,7 +399,7 @@ __global__ __launch_bounds__(kBlock) void k_scan_tiles(int n, const int *in, int
         const long long i = t0 + c + threadIdx.x;
         const int v = i < n ? in[i] : 0;
         int total;
-        const int ex = wg_exclusive_scan(v, lds_waves, &total);
+        const int ex = block_scan_int(v, lds_waves, &total);
         if (i < n) out[i] = run + ex;
         run += total;
     }
@@ -455,7 +414,7 @@ __global__ __launch_bounds__(kBlock) void k_scan_tile_sums(int ntiles, int *tile
         const int i = c + threadIdx.x;
         const int v = i < ntiles ? tile_sum[i] : 0;
         int total;
-        const int ex = wg_exclusive_scan(v, lds_waves, &total);
+        const int ex = block_scan_int(v, lds_waves, &total);
         if (i < ntiles) tile_sum[i] = run + ex;
         run += total;
     }
@@ -473,15 +432,13 @@ static int device_exclusive_scan(hipStream_t st, int n, const int *in, int *out)
 {
     if (n <= 0) { CM_HIP(hipMemsetAsync(out, 0, sizeof(int), st)); return CUDAMAT_OK; }
     const int ntiles = (n + kScanTile - 1) / kScanTile;
-    int *tile_sum = nullptr;
-    CM_TRY(dalloc(&tile_sum, (size_t)ntiles));
+    AnalysisTmp<int> tile_sum;
+    CM_TRY(tmp_alloc(tile_sum, (size_t)ntiles));
     hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(kBlock), 0, st, n, in, out, tile_sum);
     hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(kBlock), 0, st, ntiles, tile_sum, n, out);
     hipLaunchKernelGGL(k_scan_add, dim3((unsigned)(((long long)n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, n, tile_sum, out);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    afree(tile_sum);
-    CM_HIP(e);
+    CM_HIP(hipGetLastError());
+    CM_HIP(hipStreamSynchronize(st));
     return CUDAMAT_OK;
 }
 
@@ -525,7 +482,7 @@ __global__ __launch_bounds__(kBlock) void k_lsort_scan_digit(int nchunks, int *c
         const int i = c0 + threadIdx.x;
         const int v = i < nchunks ? c[i] : 0;
         int total;
-        const int ex = wg_exclusive_scan(v, lds_waves, &total);
+        const int ex = block_scan_int(v, lds_waves, &total);
         if (i < nchunks) c[i] = run + ex;
         run += total;
     }
@@ -537,7 +494,7 @@ __global__ __launch_bounds__(kBlock) void k_lsort_scan_tot(const int *tot, int *
     static_assert(kBlock == 256, "one digit per thread");
     __shared__ int lds_waves[kBlock / 64];
     int total;
-    base[threadIdx.x] = wg_exclusive_scan(tot[threadIdx.x], lds_waves, &total);
+    base[threadIdx.x] = block_scan_int(tot[threadIdx.x], lds_waves, &total);
 }
 
 __global__ __launch_bounds__(kBlock) void k_lsort_scatter(int n, const int *key_in, const int *row_in, int shift, int nchunks,
@@ -630,59 +587,52 @@ __global__ __launch_bounds__(kBlock) void k_factor_len(int n, const int *row_of,
 
 // rows sorted by (level, row): *row_of_out (n ints) and *level_ptr_dev_out (levels + 1 ints) are the caller's afterwards;
 // level_ptr: the same table on the host.  n > 0.
-static int sort_rows_by_level(hipStream_t st, int n, const int *d_lev, int **row_of_out, std::vector<int> &level_ptr, int **level_ptr_dev_out)
+static int sort_rows_by_level(hipStream_t st, int n, const int *d_lev, DevBuf<int> *row_of_out, std::vector<int> &level_ptr,
+                              DevBuf<int> *level_ptr_dev_out)
 {
-    *row_of_out = nullptr;
-    *level_ptr_dev_out = nullptr;
-    int *kb[2] = {nullptr, nullptr}, *rb[2] = {nullptr, nullptr}, *cnt = nullptr, *tot = nullptr, *maxv = nullptr, *lp = nullptr;
-    int rc = CUDAMAT_OK;
-    do {
-        if ((rc = dalloc(&maxv, 1))) break;
-        if (hipMemsetAsync(maxv, 0, sizeof(int), st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
-        const unsigned gmax = (unsigned)std::min<long long>(((long long)n + kBlock - 1) / kBlock, 4096);
-        hipLaunchKernelGGL(k_max_int, dim3(gmax), dim3(kBlock), 0, st, n, d_lev, maxv);
-        int maxlev = 0;
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&maxlev, maxv, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("level maximum failed"); break; }
-        const int nlev = maxlev + 1;
-        const int passes = nlev <= (1 << 8) ? 1 : nlev <= (1 << 16) ? 2 : nlev <= (1 << 24) ? 3 : 4;
-        const int nchunks = (int)(((long long)n + kLsChunk - 1) / kLsChunk);
-        const unsigned grid = (unsigned)((nchunks + kLsWaves - 1) / kLsWaves);
-        if ((rc = dalloc(&cnt, (size_t)256 * nchunks))) break;
-        if ((rc = dalloc(&tot, 512))) break;                    // totals, then bases
-        for (int q = 0; q < (passes > 1 ? 2 : 1) && !rc; q++) {
-            rc = dalloc(&kb[q], (size_t)n);
-            if (!rc) rc = dalloc(&rb[q], (size_t)n);
-        }
-        if (rc) break;
-        const int *key_in = d_lev, *row_in = nullptr;
-        int last = 0;
-        for (int p = 0; p < passes; p++) {
-            const int o = p & 1;
-            hipLaunchKernelGGL(k_lsort_hist, dim3(grid), dim3(kBlock), 0, st, n, key_in, 8 * p, nchunks, cnt);
-            hipLaunchKernelGGL(k_lsort_scan_digit, dim3(256), dim3(kBlock), 0, st, nchunks, cnt, tot);
-            hipLaunchKernelGGL(k_lsort_scan_tot, dim3(1), dim3(kBlock), 0, st, tot, tot + 256);
-            hipLaunchKernelGGL(k_lsort_scatter, dim3(grid), dim3(kBlock), 0, st, n, key_in, row_in, 8 * p, nchunks, cnt, tot + 256, kb[o], rb[o]);
-            key_in = kb[o];
-            row_in = rb[o];
-            last = o;
-        }
-        if (hipGetLastError() != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("level sort launch failed"); break; }
-        if ((rc = dalloc(&lp, (size_t)nlev + 1))) break;
-        hipLaunchKernelGGL(k_level_ptr, dim3((unsigned)(((long long)n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, n, kb[last], lp);
-        level_ptr.assign((size_t)nlev + 1, 0);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(level_ptr.data(), lp, sizeof(int) * ((size_t)nlev + 1), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("level sort failed"); break; }
-        if (level_ptr[0] != 0 || level_ptr[(size_t)nlev] != n) { rc = CUDAMAT_ERR_HIP; set_error("level sort: inconsistent level table"); break; }
-        *row_of_out = rb[last];
-        rb[last] = nullptr;
-        *level_ptr_dev_out = lp;
-        lp = nullptr;
-    } while (0);
-    void *tmp[] = {kb[0], kb[1], rb[0], rb[1], cnt, tot, maxv, lp};
-    for (void *q : tmp) afree(q);
-    return rc;
+    row_of_out->reset();
+    level_ptr_dev_out->reset();
+    AnalysisTmp<int> kb[2], rb[2], cnt, tot, maxv, lp;
+    CM_TRY(tmp_alloc(maxv, 1));
+    if (hipMemsetAsync(maxv, 0, sizeof(int), st) != hipSuccess) return CUDAMAT_ERR_HIP;
+    const unsigned gmax = (unsigned)std::min<long long>(((long long)n + kBlock - 1) / kBlock, 4096);
+    hipLaunchKernelGGL(k_max_int, dim3(gmax), dim3(kBlock), 0, st, n, d_lev, maxv);
+    int maxlev = 0;
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&maxlev, maxv, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) { set_error("level maximum failed"); return CUDAMAT_ERR_HIP; }
+    const int nlev = maxlev + 1;
+    const int passes = nlev <= (1 << 8) ? 1 : nlev <= (1 << 16) ? 2 : nlev <= (1 << 24) ? 3 : 4;
+    const int nchunks = (int)(((long long)n + kLsChunk - 1) / kLsChunk);
+    const unsigned grid = (unsigned)((nchunks + kLsWaves - 1) / kLsWaves);
+    CM_TRY(tmp_alloc(cnt, (size_t)256 * nchunks));
+    CM_TRY(tmp_alloc(tot, 512));                    // totals, then bases
+    for (int q = 0; q < (passes > 1 ? 2 : 1); q++) {
+        CM_TRY(tmp_alloc(kb[q], (size_t)n));
+        CM_TRY(tmp_alloc(rb[q], (size_t)n));
+    }
+    const int *key_in = d_lev, *row_in = nullptr;
+    int last = 0;
+    for (int p = 0; p < passes; p++) {
+        const int o = p & 1;
+        hipLaunchKernelGGL(k_lsort_hist, dim3(grid), dim3(kBlock), 0, st, n, key_in, 8 * p, nchunks, cnt);
+        hipLaunchKernelGGL(k_lsort_scan_digit, dim3(256), dim3(kBlock), 0, st, nchunks, cnt, tot);
+        hipLaunchKernelGGL(k_lsort_scan_tot, dim3(1), dim3(kBlock), 0, st, tot, tot + 256);
+        hipLaunchKernelGGL(k_lsort_scatter, dim3(grid), dim3(kBlock), 0, st, n, key_in, row_in, 8 * p, nchunks, cnt, tot + 256, kb[o], rb[o]);
+        key_in = kb[o];
+        row_in = rb[o];
+        last = o;
+    }
+    if (hipGetLastError() != hipSuccess) { set_error("level sort launch failed"); return CUDAMAT_ERR_HIP; }
+    CM_TRY(tmp_alloc(lp, (size_t)nlev + 1));
+    hipLaunchKernelGGL(k_level_ptr, dim3((unsigned)(((long long)n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, n, kb[last], lp);
+    level_ptr.assign((size_t)nlev + 1, 0);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(level_ptr.data(), lp, sizeof(int) * ((size_t)nlev + 1), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) { set_error("level sort failed"); return CUDAMAT_ERR_HIP; }
+    if (level_ptr[0] != 0 || level_ptr[(size_t)nlev] != n) { set_error("level sort: inconsistent level table"); return CUDAMAT_ERR_HIP; }
+    row_of_out->adopt(rb[last].release());         // the two results change owner; the rest is released as temporaries are
+    level_ptr_dev_out->adopt(lp.release());
+    return CUDAMAT_OK;
 }
 
 // levels -> level-major permutation (stable: rows of a level stay in increasing order)
@@ -739,7 +689,7 @@ static int build_levels(cudamat_solver *s, bool upper, int *d_lev, int *d_flags,
     CM_STAMP(upper ? "U levels (device)" : "L levels (device)");
     // the level of every original row stays on the device until the far / near split (split_factor); d_lev is the
     // caller's scratch and serves the other factor next
-    CM_TRY(dalloc(&H.lev_dev, (size_t)n));
+    CM_TRY(H.lev_dev.alloc((size_t)n));
     if (n) CM_HIP(hipMemcpyAsync(H.lev_dev, d_lev, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, st));
     // stable sort of the rows by level, the level table, the factor's row pointers in that order: all on the device
     if (n > 0) {
@@ -748,22 +698,21 @@ static int build_levels(cudamat_solver *s, bool upper, int *d_lev, int *d_flags,
     } else {
         F.nlevels = 0;
         F.level_ptr.assign(1, 0);
-        CM_TRY(dalloc(&F.row_of, 0));
-        CM_TRY(dalloc(&H.level_ptr_dev, 1));
+        CM_TRY(F.row_of.alloc(0));
+        CM_TRY(H.level_ptr_dev.alloc(1));
         CM_HIP(hipMemsetAsync(H.level_ptr_dev, 0, sizeof(int), st));
     }
     const int nlev = F.nlevels;
     CM_STAMP("level sort (device)");
-    CM_TRY(dalloc(&F.rp, (size_t)n + 1));
+    CM_TRY(F.rp.alloc((size_t)n + 1));
     {
-        int *d_len = nullptr;
-        CM_TRY(dalloc(&d_len, (size_t)n));
+        AnalysisTmp<int> d_len;
+        CM_TRY(tmp_alloc(d_len, (size_t)n));
         if (n) hipLaunchKernelGGL(k_factor_len, dim3((unsigned)(((long long)n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, n, F.row_of, s->pm_rp,
                                   s->diag_pos, upper ? 1 : 0, d_len);
         int rcs = hipGetLastError() == hipSuccess ? device_exclusive_scan(st, n, d_len, F.rp) : CUDAMAT_ERR_HIP;
         int total = 0;
         if (!rcs && hipMemcpy(&total, F.rp + n, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) rcs = CUDAMAT_ERR_HIP;
-        afree(d_len);
         if (rcs) { set_error("factor row pointers failed"); return rcs; }
         F.nnz = total;
     }
@@ -968,9 +917,9 @@ int launch_sort_rows(hipStream_t st, int nrows, const int *src_rp, const int *sr
     return CUDAMAT_OK;
 }
 
-static int split_factor(cudamat_solver *s, TriFactor &F, TriHost &H, const int *pos)
+// the split itself; on failure F is intact and split_factor takes back what H holds of it
+static int split_factor_build(cudamat_solver *s, TriFactor &F, TriHost &H, const int *pos)
 {
-    if (!H.hybrid) return CUDAMAT_OK;
     hipStream_t st = s->ctx->stream;
     const int n = s->n;
     const int K = (int)H.grp_level.size() - 1;
@@ -980,68 +929,71 @@ static int split_factor(cudamat_solver *s, TriFactor &F, TriHost &H, const int *
     if (K > 128) { set_error("factor split: more than 128 groups"); return CUDAMAT_ERR_ARG; }
     gc.K = K;
     for (int g = 0; g <= K; g++) gc.start[g] = F.level_ptr[(size_t)H.grp_level[(size_t)g]];
-    int *d_cn = nullptr, *d_cf = nullptr, *nrp = nullptr, *qrp = nullptr, *nci = nullptr, *qci = nullptr, *ci_new = nullptr;
-    double *nval = nullptr, *qval = nullptr;
+    DevBuf<int> d_cn, d_cf, nrp, qrp, nci, qci, ci_new;
+    DevBuf<double> nval, qval;
+    CM_TRY(d_cn.alloc((size_t)n));
+    CM_TRY(d_cf.alloc((size_t)n));
+    CM_TRY(ci_new.alloc((size_t)(F.nnz > 0 ? F.nnz : 1)));
+    constexpr int kSplitWaves = 4;
+    const unsigned grid = (unsigned)((n + kSplitWaves - 1) / kSplitWaves);
+    hipLaunchKernelGGL(k_split_count<kSplitWaves>, dim3(grid), dim3(64 * kSplitWaves), 0, st, n, F.rp, F.ci, pos, gc, ci_new, d_cn, d_cf);
+    // row pointers of the near and the far part: prefix sums on the device; the host needs the two totals and the far
+    // pointer at the group boundaries only
+    CM_TRY(nrp.alloc((size_t)n + 1));
+    CM_TRY(qrp.alloc((size_t)n + 1));
+    CM_TRY(device_exclusive_scan(st, n, d_cn, nrp));
+    CM_TRY(device_exclusive_scan(st, n, d_cf, qrp));
+    int tot_near = 0, tot_far = 0;
+    std::vector<int> hf_grp((size_t)K + 1, 0);
+    bool copied = hipMemcpy(&tot_near, nrp + n, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess &&
+                  hipMemcpy(&tot_far, qrp + n, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+    for (int g = 0; g <= K && copied; g++)
+        copied = hipMemcpy(&hf_grp[(size_t)g], qrp + F.level_ptr[(size_t)H.grp_level[(size_t)g]], sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+    if (!copied) { set_error("factor split scan failed"); return CUDAMAT_ERR_HIP; }
+    const int64_t nnz_near = tot_near, nnz_far = tot_far;
+    CM_STAMP("split count + device scan");
+    CM_TRY(nci.alloc((size_t)nnz_near));
+    CM_TRY(nval.alloc((size_t)nnz_near));
+    CM_TRY(qci.alloc((size_t)nnz_far));
+    CM_TRY(qval.alloc((size_t)nnz_far));
+    // (far rows come out in increasing level-major column order, as the blocked builder needs them)
+    hipLaunchKernelGGL(k_split_fill<kSplitWaves>, dim3(grid), dim3(64 * kSplitWaves), 0, st, n, F.rp, ci_new, F.val, gc, nrp, nci,
+                       nval, qrp, qci, qval);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { set_error("factor split failed"); return CUDAMAT_ERR_HIP; }
+    CM_STAMP("split fill (far rows sorted)");
+    // one blocked SpMV plan per group: rows of the group (level-major, contiguous) x the columns of the EARLIER
+    // groups -- in level-major space those are the positions [0, r0), so only that prefix of `out` is tiled
+    H.far.assign((size_t)K, PbPlan());
     int rc = CUDAMAT_OK;
-    do {
-        if ((rc = dalloc(&d_cn, (size_t)n))) break;
-        if ((rc = dalloc(&d_cf, (size_t)n))) break;
-        if ((rc = dalloc(&ci_new, (size_t)(F.nnz > 0 ? F.nnz : 1)))) break;
-        constexpr int kSplitWaves = 4;
-        const unsigned grid = (unsigned)((n + kSplitWaves - 1) / kSplitWaves);
-        hipLaunchKernelGGL(k_split_count<kSplitWaves>, dim3(grid), dim3(64 * kSplitWaves), 0, st, n, F.rp, F.ci, pos, gc, ci_new, d_cn, d_cf);
-        // row pointers of the near and the far part: prefix sums on the device; the host needs the two totals and the far
-        // pointer at the group boundaries only
-        if ((rc = dalloc(&nrp, (size_t)n + 1))) break;
-        if ((rc = dalloc(&qrp, (size_t)n + 1))) break;
-        if ((rc = device_exclusive_scan(st, n, d_cn, nrp))) break;
-        if ((rc = device_exclusive_scan(st, n, d_cf, qrp))) break;
-        int tot_near = 0, tot_far = 0;
-        std::vector<int> hf_grp((size_t)K + 1, 0);
-        bool copied = hipMemcpy(&tot_near, nrp + n, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess &&
-                      hipMemcpy(&tot_far, qrp + n, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
-        for (int g = 0; g <= K && copied; g++)
-            copied = hipMemcpy(&hf_grp[(size_t)g], qrp + F.level_ptr[(size_t)H.grp_level[(size_t)g]], sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
-        if (!copied) { rc = CUDAMAT_ERR_HIP; set_error("factor split scan failed"); break; }
-        const int64_t nnz_near = tot_near, nnz_far = tot_far;
-        CM_STAMP("split count + device scan");
-        if ((rc = dalloc(&nci, (size_t)nnz_near))) break;
-        if ((rc = dalloc(&nval, (size_t)nnz_near))) break;
-        if ((rc = dalloc(&qci, (size_t)nnz_far))) break;
-        if ((rc = dalloc(&qval, (size_t)nnz_far))) break;
-        // (far rows come out in increasing level-major column order, as the blocked builder needs them)
-        hipLaunchKernelGGL(k_split_fill<kSplitWaves>, dim3(grid), dim3(64 * kSplitWaves), 0, st, n, F.rp, ci_new, F.val, gc, nrp, nci,
-                           nval, qrp, qci, qval);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("factor split failed"); break; }
-        CM_STAMP("split fill (far rows sorted)");
-        // one blocked SpMV plan per group: rows of the group (level-major, contiguous) x the columns of the EARLIER
-        // groups -- in level-major space those are the positions [0, r0), so only that prefix of `out` is tiled
-        H.far.assign((size_t)K, PbPlan());
-        for (int g = 1; g < K && !rc; g++) {
-            const int r0 = F.level_ptr[(size_t)H.grp_level[(size_t)g]], r1 = F.level_ptr[(size_t)H.grp_level[(size_t)g + 1]];
-            const int64_t cnt = (int64_t)hf_grp[(size_t)g + 1] - hf_grp[(size_t)g];
-            if (r1 <= r0 || cnt <= 0) continue;
-            rc = pb_build(st, s->ctx->cfg, r1 - r0, r0, cnt, qrp + r0, qci, qval, &H.far[(size_t)g]);
-        }
-        CM_STAMP("far plans (pb_build)");
-        if (rc) break;
-        if ((rc = dalloc(&H.far_buf, (size_t)n))) break;
-        if (hipMemsetAsync(H.far_buf, 0, sizeof(double) * (size_t)n, st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
-        // the level kernels keep only the near entries
-        CM_DROP(hipFree(F.rp)); CM_DROP(hipFree(F.ci)); CM_DROP(hipFree(F.val));
-        F.rp = nrp; F.ci = nci; F.val = nval;
-        F.nnz = nnz_near;
-        nrp = nullptr; nci = nullptr; nval = nullptr;
-        H.lanes = pick_lanes(n ? (double)F.nnz / n : 1.0);
-    } while (0);
-    void *tmp[] = {d_cn, d_cf, nrp, qrp, nci, qci, nval, qval, ci_new};
-    for (void *q : tmp)
-        if (q) CM_DROP(hipFree(q));
-    free_levels(H);
+    for (int g = 1; g < K && !rc; g++) {
+        const int r0 = F.level_ptr[(size_t)H.grp_level[(size_t)g]], r1 = F.level_ptr[(size_t)H.grp_level[(size_t)g + 1]];
+        const int64_t cnt = (int64_t)hf_grp[(size_t)g + 1] - hf_grp[(size_t)g];
+        if (r1 <= r0 || cnt <= 0) continue;
+        rc = pb_build(st, s->ctx->cfg, r1 - r0, r0, cnt, qrp + r0, qci, qval, &H.far[(size_t)g]);
+    }
+    CM_STAMP("far plans (pb_build)");
+    CM_TRY(rc);
+    CM_TRY(H.far_buf.alloc((size_t)n));
+    CM_HIP(hipMemsetAsync(H.far_buf, 0, sizeof(double) * (size_t)n, st));
+    // the level kernels keep only the near entries: the whole factor's arrays are released here, now that the far plans
+    // are built, not earlier
+    F.rp = std::move(nrp);
+    F.ci = std::move(nci);
+    F.val = std::move(nval);
+    F.nnz = nnz_near;
+    H.lanes = pick_lanes(n ? (double)F.nnz / n : 1.0);
+    return CUDAMAT_OK;
+}
+
+static int split_factor(cudamat_solver *s, TriFactor &F, TriHost &H, const int *pos)
+{
+    if (!H.hybrid) return CUDAMAT_OK;
+    const int rc = split_factor_build(s, F, H, pos);
+    H.lev_dev.reset();
     if (rc) {   // e.g. not enough memory for the blocked copies: keep the pure level solve (F is intact)
         for (PbPlan &pl : H.far) pb_free(&pl);
         H.far.clear();
-        if (H.far_buf) { CM_DROP(hipFree(H.far_buf)); H.far_buf = nullptr; }
+        H.far_buf.reset();
         H.hybrid = false;
         return rc == CUDAMAT_ERR_NOMEM ? CUDAMAT_OK : rc;
     }
@@ -1051,9 +1003,9 @@ static int split_factor(cudamat_solver *s, TriFactor &F, TriHost &H, const int *
 static int fill_factor(cudamat_solver *s, bool upper, TriFactor &F)
 {
     const int n = s->n;
-    if (!F.ci) CM_TRY(dalloc(&F.ci, (size_t)F.nnz));
-    if (!F.val) CM_TRY(dalloc(&F.val, (size_t)F.nnz));
-    if (upper && !F.dinv) CM_TRY(dalloc(&F.dinv, (size_t)n));
+    if (!F.ci) CM_TRY(F.ci.alloc((size_t)F.nnz));
+    if (!F.val) CM_TRY(F.val.alloc((size_t)F.nnz));
+    if (upper && !F.dinv) CM_TRY(F.dinv.alloc((size_t)n));
     if (!n) return CUDAMAT_OK;
     const long long threads = (long long)n * 8;
     const unsigned grid = (unsigned)((threads + kBlock - 1) / kBlock);
@@ -1111,113 +1063,116 @@ static int select_precond_matrix(cudamat_solver *s)
     hipStream_t st = s->ctx->stream;
     const int n = s->n;
     const long long c0 = (long long)s->comm.rank * s->n_pad;
-    int *first = nullptr, *cnt = nullptr;
-    int rc = CUDAMAT_OK;
+    DevBuf<int> first, cnt;
     s->pm_owned = true;
-    do {
-        if ((rc = dalloc(&first, (size_t)n))) break;
-        if ((rc = dalloc(&cnt, (size_t)n))) break;
-        const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
-        if (n) hipLaunchKernelGGL(k_block_count, dim3(grid), dim3(kBlock), 0, st, n, s->rp, s->ci, c0, first, cnt);
-        std::vector<int> h((size_t)n), brp((size_t)n + 1, 0);
-        if (n && (hipMemcpyAsync(h.data(), cnt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                  hipStreamSynchronize(st) != hipSuccess)) { rc = CUDAMAT_ERR_HIP; set_error("block count failed"); break; }
-        for (int i = 0; i < n; i++) brp[(size_t)i + 1] = brp[(size_t)i] + h[(size_t)i];
-        s->pm_nnz = brp[(size_t)n];
-        if ((rc = dalloc(&s->pm_rp, (size_t)n + 1))) break;
-        if ((rc = dalloc(&s->pm_ci, (size_t)s->pm_nnz))) break;
-        if ((rc = dalloc(&s->pm_val, (size_t)s->pm_nnz))) break;
-        if (hipMemcpy(s->pm_rp, brp.data(), sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice) != hipSuccess) {
-            rc = CUDAMAT_ERR_HIP; set_error("block row pointers upload failed"); break;
-        }
-        const unsigned grid8 = (unsigned)(((long long)n * 8 + kBlock - 1) / kBlock);
-        if (n) hipLaunchKernelGGL(k_block_fill, dim3(grid8), dim3(kBlock), 0, st, n, s->ci, s->val, c0, first, s->pm_rp,
-                                  s->pm_ci, s->pm_val);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-            rc = CUDAMAT_ERR_HIP; set_error("block extraction failed"); break;
-        }
-    } while (0);
-    if (first) CM_DROP(hipFree(first));
-    if (cnt) CM_DROP(hipFree(cnt));
-    return rc;       // on failure ilu0_setup's error path releases the partial copy
+    CM_TRY(first.alloc((size_t)n));
+    CM_TRY(cnt.alloc((size_t)n));
+    const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
+    if (n) hipLaunchKernelGGL(k_block_count, dim3(grid), dim3(kBlock), 0, st, n, s->rp, s->ci, c0, first, cnt);
+    std::vector<int> h((size_t)n), brp((size_t)n + 1, 0);
+    if (n && (hipMemcpyAsync(h.data(), cnt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+              hipStreamSynchronize(st) != hipSuccess)) { set_error("block count failed"); return CUDAMAT_ERR_HIP; }
+    for (int i = 0; i < n; i++) brp[(size_t)i + 1] = brp[(size_t)i] + h[(size_t)i];
+    s->pm_nnz = brp[(size_t)n];
+    CM_TRY(s->pm_own_rp.alloc((size_t)n + 1));
+    CM_TRY(s->pm_own_ci.alloc((size_t)s->pm_nnz));
+    CM_TRY(s->pm_own_val.alloc((size_t)s->pm_nnz));
+    s->pm_rp = s->pm_own_rp;
+    s->pm_ci = s->pm_own_ci;
+    s->pm_val = s->pm_own_val;
+    if (hipMemcpy(s->pm_rp, brp.data(), sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("block row pointers upload failed");
+        return CUDAMAT_ERR_HIP;
+    }
+    const unsigned grid8 = (unsigned)(((long long)n * 8 + kBlock - 1) / kBlock);
+    if (n) hipLaunchKernelGGL(k_block_fill, dim3(grid8), dim3(kBlock), 0, st, n, s->ci, s->val, c0, first, s->pm_rp,
+                              s->pm_ci, s->pm_val);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        set_error("block extraction failed");
+        return CUDAMAT_ERR_HIP;
+    }
+    return CUDAMAT_OK;       // (on failure ilu0_analysis releases the partial copy)
+}
+
+// a failed set-up leaves nothing behind; its message survives the release
+static int ilu0_fail(cudamat_solver *s, int rc)
+{
+    char saved[512];
+    snprintf(saved, sizeof(saved), "%s", cudamat_last_error());
+    ilu0_release(s);
+    set_error("%s", saved);
+    return rc;
 }
 
 // The PATTERN-ONLY part of the set-up (pbicgstab.cu:336-347: the two csrsv analyses; plus the diagonal positions and the
 // longest row): needs rp / ci only, so the drop-in entry point runs it while the values are still being uploaded
 // (ilu0_analyse_early); ilu0_setup runs it itself when nobody has.  Leaves its scratch (flags, levels) in the plans.
-static int ilu0_analysis(cudamat_solver *s, bool block)
+static int ilu0_analysis_body(cudamat_solver *s, bool block)
 {
-    ilu0_release(s);
-    if (int rc0 = select_precond_matrix(s)) {
-        char saved[512];
-        snprintf(saved, sizeof(saved), "%s", cudamat_last_error());
-        ilu0_release(s);
-        set_error("%s", saved);
-        return rc0;
-    }
+    CM_TRY(select_precond_matrix(s));
     s->ilu_block = block;
     hipStream_t st = s->ctx->stream;
     const int n = s->n;
     IluPlans *pl = plans_of(s, true);
-    int *&d_flags = pl->d_flags, *&d_lev = pl->d_lev;
-    int rc = CUDAMAT_OK;
     const double t0 = now_s();
     double t_stamp = t0;
-    do {
-        if ((rc = dalloc(&d_flags, 5))) break;     // [0..1] flags, [2] ticket counter of k_levels_dep, [3] longest row
-        if ((rc = dalloc(&d_lev, (size_t)n))) break;
-        if (hipHostMalloc((void **)&pl->err_host, sizeof(int), hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer((void **)&pl->err_dev, pl->err_host, 0) != hipSuccess) {
-            rc = CUDAMAT_ERR_HIP; set_error("pinned status word allocation failed"); break;
-        }
-        *pl->err_host = 0;
-        if ((rc = dalloc(&s->diag_pos, (size_t)n))) break;
-        if (hipMemsetAsync(d_flags, 0, 2 * sizeof(int), st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
-        if (n) {
-            hipLaunchKernelGGL(k_find_diag, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, n, s->pm_rp, s->pm_ci,
-                               s->diag_pos, d_flags);
-        }
-        int hflags[2] = {0, 0};
-        if (hipMemcpyAsync(hflags, d_flags, sizeof(hflags), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("find_diag failed"); break; }
-        if (hflags[1]) {
-            set_error("ILU(0): row %d has no diagonal entry (pbicgstab.h:118 requires A[i,i] != 0)", hflags[1] - 1);
-            rc = CUDAMAT_ERR_ZERO_PIVOT;
-            break;
-        }
-        CM_STAMP("find diag");
-        // ---- analysis (pbicgstab.cu:336-347)
-        if ((rc = build_levels(s, false, d_lev, d_flags, s->L, pl->L, pl->err_host, pl->err_dev))) break;
-        s->t_analysis_l = now_s() - t0;
-        const double tu = now_s();
-        if ((rc = build_levels(s, true, d_lev, d_flags, s->U, pl->U, pl->err_host, pl->err_dev))) break;
-        int maxrow_all = 0;
-        if (n) {           // the longest row of the pattern (LDS staging of the factorisation, sortable far rows)
-            if (hipMemsetAsync(d_flags + 3, 0, sizeof(int), st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
-            hipLaunchKernelGGL(k_max_row_len, dim3((unsigned)std::min<long long>(((long long)n + kBlock - 1) / kBlock, 4096)), dim3(kBlock), 0, st,
-                               n, s->pm_rp, d_flags + 3);
-            if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&maxrow_all, d_flags + 3, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("row length maximum failed"); break; }
-        }
-        {
-            // the two factors take the hybrid solve TOGETHER: they then share the level-major index spaces (L's output
-            // feeds U's right-hand side, U's output the permuted matrix of the preconditioned loop)
-            const bool hybrid = pl->L.want_hybrid && pl->U.want_hybrid && maxrow_all <= kSortRowMax;
-            plan_groups(s->ctx->cfg, s->L, pl->L, hybrid);
-            plan_groups(s->ctx->cfg, s->U, pl->U, hybrid);
-        }
-        s->t_analysis_u = now_s() - tu;
-        s->t_analysis = now_s() - t0;
-        pl->maxrow_all = maxrow_all;
-        pl->analysed = true;
-    } while (0);
-    if (rc) {
-        char saved[512];
-        snprintf(saved, sizeof(saved), "%s", cudamat_last_error());
-        ilu0_release(s);
-        set_error("%s", saved);
+    CM_TRY(pl->d_flags.alloc(5));    // [0..1] flags, [2] ticket counter of k_levels_dep, [3] longest row
+    CM_TRY(pl->d_lev.alloc((size_t)n));
+    int *const d_flags = pl->d_flags, *const d_lev = pl->d_lev;
+    int *err_host = nullptr;
+    if (hipHostMalloc((void **)&err_host, sizeof(int), hipHostMallocMapped) != hipSuccess) err_host = nullptr;
+    pl->err_host.adopt(err_host);
+    if (!err_host || hipHostGetDevicePointer((void **)&pl->err_dev, err_host, 0) != hipSuccess) {
+        set_error("pinned status word allocation failed");
+        return CUDAMAT_ERR_HIP;
     }
-    return rc;
+    *err_host = 0;
+    CM_TRY(s->diag_pos.alloc((size_t)n));
+    if (hipMemsetAsync(d_flags, 0, 2 * sizeof(int), st) != hipSuccess) return CUDAMAT_ERR_HIP;
+    if (n) {
+        hipLaunchKernelGGL(k_find_diag, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, n, s->pm_rp, s->pm_ci,
+                           s->diag_pos, d_flags);
+    }
+    int hflags[2] = {0, 0};
+    if (hipMemcpyAsync(hflags, d_flags, sizeof(hflags), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) { set_error("find_diag failed"); return CUDAMAT_ERR_HIP; }
+    if (hflags[1]) {
+        set_error("ILU(0): row %d has no diagonal entry (pbicgstab.h:118 requires A[i,i] != 0)", hflags[1] - 1);
+        return CUDAMAT_ERR_ZERO_PIVOT;
+    }
+    CM_STAMP("find diag");
+    // ---- analysis (pbicgstab.cu:336-347)
+    CM_TRY(build_levels(s, false, d_lev, d_flags, s->L, pl->L, pl->err_host, pl->err_dev));
+    s->t_analysis_l = now_s() - t0;
+    const double tu = now_s();
+    CM_TRY(build_levels(s, true, d_lev, d_flags, s->U, pl->U, pl->err_host, pl->err_dev));
+    int maxrow_all = 0;
+    if (n) {           // the longest row of the pattern (LDS staging of the factorisation, sortable far rows)
+        if (hipMemsetAsync(d_flags + 3, 0, sizeof(int), st) != hipSuccess) return CUDAMAT_ERR_HIP;
+        hipLaunchKernelGGL(k_max_row_len, dim3((unsigned)std::min<long long>(((long long)n + kBlock - 1) / kBlock, 4096)), dim3(kBlock), 0, st,
+                           n, s->pm_rp, d_flags + 3);
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&maxrow_all, d_flags + 3, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) { set_error("row length maximum failed"); return CUDAMAT_ERR_HIP; }
+    }
+    {
+        // the two factors take the hybrid solve TOGETHER: they then share the level-major index spaces (L's output
+        // feeds U's right-hand side, U's output the permuted matrix of the preconditioned loop)
+        const bool hybrid = pl->L.want_hybrid && pl->U.want_hybrid && maxrow_all <= kSortRowMax;
+        plan_groups(s->ctx->cfg, s->L, pl->L, hybrid);
+        plan_groups(s->ctx->cfg, s->U, pl->U, hybrid);
+    }
+    s->t_analysis_u = now_s() - tu;
+    s->t_analysis = now_s() - t0;
+    pl->maxrow_all = maxrow_all;
+    pl->analysed = true;
+    return CUDAMAT_OK;
+}
+
+static int ilu0_analysis(cudamat_solver *s, bool block)
+{
+    ilu0_release(s);
+    const int rc = ilu0_analysis_body(s, block);
+    return rc ? ilu0_fail(s, rc) : CUDAMAT_OK;
 }
 
 int ilu0_analyse_early(cudamat_solver *s)
@@ -1232,7 +1187,7 @@ int ilu0_analyse_early(cudamat_solver *s)
     t_deferred = nullptr;
     (void)pl;
     if (IluPlans *p2 = plans_of(s, false)) p2->deferred.insert(p2->deferred.end(), keep.begin(), keep.end());
-    else for (void *q : keep) CM_DROP(hipFree(q));
+    else flush_deferred(keep);
     return rc;
 }
 
@@ -1247,11 +1202,10 @@ bool ilu0_will_use_level_major(cudamat_solver *s)
 // the temporaries of an analysis that ran beside an upload: free them now (the upload is over)
 void ilu0_flush_deferred(cudamat_solver *s)
 {
-    if (IluPlans *pl = plans_of(s, false)) {
-        for (void *q : pl->deferred) CM_DROP(hipFree(q));
-        pl->deferred.clear();
-    }
+    if (IluPlans *pl = plans_of(s, false)) flush_deferred(pl->deferred);
 }
+
+static int ilu0_setup_body(cudamat_solver *s, IluPlans *pl);
 
 int ilu0_setup(cudamat_solver *s, bool block)
 {
@@ -1264,156 +1218,150 @@ int ilu0_setup(cudamat_solver *s, bool block)
         const bool have = p0 && p0->analysed && !s->has_ilu && s->ilu_block == block;     // the drop-in call ran it beside its upload
         if (!have) CM_TRY(ilu0_analysis(s, block));
     }
-    hipStream_t st = s->ctx->stream;
-    const int n = s->n;
     IluPlans *pl = plans_of(s, true);
     pl->analysed = false;                  // (consumed: a second ilu0_setup on this solver starts over)
-    int *&d_flags = pl->d_flags, *&d_lev = pl->d_lev;
+    const int rc = ilu0_setup_body(s, pl);
+    if (rc) return ilu0_fail(s, rc);
+    pl->d_flags.reset();                   // the scratch of the analysis has served
+    pl->d_lev.reset();
+    return CUDAMAT_OK;
+}
+
+static int ilu0_setup_body(cudamat_solver *s, IluPlans *pl)
+{
+    hipStream_t st = s->ctx->stream;
+    const int n = s->n;
+    int *const d_flags = pl->d_flags;
     const int maxrow_all = pl->maxrow_all;
     int hflags[2] = {0, 0};
-    int rc = CUDAMAT_OK;
-    double t_stamp = now_s();
-    do {
-        // ---- factorisation on a copy of A's values (pbicgstab.cu:316, :356-363)
-        const double t1 = now_s();
-        t_stamp = t1;
-        if ((rc = dalloc(&s->lu, (size_t)s->pm_nnz))) break;
-        if (hipMemcpyAsync(s->lu, s->pm_val, sizeof(double) * (size_t)s->pm_nnz, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-            rc = CUDAMAT_ERR_HIP; set_error("copy of A values failed"); break;
-        }
-        const int maxrow = maxrow_all;
-        const int cap = ((maxrow + 63) / 64) * 64 + 64;
-        const bool one_wave = cap > 2048;
-        const bool fast = cap <= 1024 && !s->ctx->cfg.ilu0_simple;
-        if ((size_t)cap * sizeof(double) > 150 * 1024) {
-            set_error("ILU(0): a row with %d entries exceeds the %d-entry LDS staging limit", maxrow, 150 * 1024 / 8);
-            rc = CUDAMAT_ERR_ARG;
-            break;
-        }
-        if (hipMemsetAsync(d_flags, 0, 2 * sizeof(int), st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
-        if ((rc = set_max_lds((const void *)k_ilu0_level<1>))) break;
-        if ((rc = set_max_lds((const void *)k_ilu0_level<4>))) break;
-        if ((rc = set_max_lds((const void *)k_ilu0_level_fast<4>))) break;
-        for (int l = 0; l < s->L.nlevels; l++) {
-            const int r0 = s->L.level_ptr[(size_t)l], r1 = s->L.level_ptr[(size_t)l + 1];
-            const int rows = r1 - r0;
-            if (fast) {     // 28 bytes of LDS per entry slot and wave: values, pivots, columns, two pivot tables
-                hipLaunchKernelGGL(k_ilu0_level_fast<4>, dim3((rows + 3) / 4), dim3(256), (size_t)28 * 4 * (size_t)cap, st,
-                                   r0, r1, s->L.row_of, s->pm_rp, s->pm_ci, s->diag_pos, s->lu, cap, d_flags);
-            } else if (one_wave) {
-                hipLaunchKernelGGL(k_ilu0_level<1>, dim3(rows), dim3(64), sizeof(double) * (size_t)cap, st, r0, r1,
-                                   s->L.row_of, s->pm_rp, s->pm_ci, s->diag_pos, s->lu, cap, d_flags);
-            } else {
-                hipLaunchKernelGGL(k_ilu0_level<4>, dim3((rows + 3) / 4), dim3(256), sizeof(double) * 4 * (size_t)cap, st,
-                                   r0, r1, s->L.row_of, s->pm_rp, s->pm_ci, s->diag_pos, s->lu, cap, d_flags);
-            }
-        }
-        if (hipGetLastError() != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("ilu0 launch failed"); break; }
-        if (hipMemcpyAsync(hflags, d_flags, sizeof(hflags), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("ilu0 failed"); break; }
-        if (hflags[1]) {
-            set_error("ILU(0): zero pivot in row %d", hflags[1] - 1);
-            rc = CUDAMAT_ERR_ZERO_PIVOT;
-            break;
-        }
-        CM_STAMP("numeric ILU(0)");
-        if ((rc = fill_factor(s, false, s->L))) break;
-        if ((rc = fill_factor(s, true, s->U))) break;
-        if (hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("factor fill failed"); break; }
-        CM_STAMP("factor fill");
-        if (pl->L.hybrid && pl->U.hybrid) {
-            // level-major index spaces: position of every original row in L's and in U's order
-            int *posL = nullptr;
-            const unsigned gp = (unsigned)((n + kBlock - 1) / kBlock);
-            if ((rc = dalloc(&posL, (size_t)n))) break;
-            if ((rc = dalloc(&pl->posU, (size_t)n))) { CM_DROP(hipFree(posL)); break; }
-            hipLaunchKernelGGL(k_invert_perm, dim3(gp), dim3(kBlock), 0, st, n, s->L.row_of, posL);
-            hipLaunchKernelGGL(k_invert_perm, dim3(gp), dim3(kBlock), 0, st, n, s->U.row_of, pl->posU);
-            rc = split_factor(s, s->L, pl->L, posL);
-            if (!rc) rc = split_factor(s, s->U, pl->U, pl->posU);
-            int *mapUL = nullptr;
-            if (!rc && pl->L.hybrid && pl->U.hybrid) rc = dalloc(&mapUL, (size_t)n);
-            if (!rc && mapUL) {
-                hipLaunchKernelGGL(k_compose_perm, dim3(gp), dim3(kBlock), 0, st, n, s->U.row_of, posL, mapUL);
-                if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("permutation maps failed"); }
-            }
-            CM_DROP(hipFree(posL));
-            if (rc) { if (mapUL) CM_DROP(hipFree(mapUL)); break; }
-            if (!(pl->L.hybrid && pl->U.hybrid)) {
-                // (split_factor fell back on one side: out of memory for the blocked copies) -- a half-split pair has no
-                // consistent index space
-                set_error("ILU(0): not enough device memory for the far/near split of the factors");
-                rc = CUDAMAT_ERR_NOMEM;
-                break;
-            }
-            s->L.lm = s->U.lm = true;
-            s->L.rhs_of = s->L.out_of = nullptr;       // L: right-hand side and solution in L's level-major space
-            s->U.rhs_of = mapUL;                       // U: right-hand side in L's space, solution in U's
-            s->U.out_of = nullptr;
-            if ((rc = dalloc(&pl->perm_a, (size_t)n))) break;
-            if ((rc = dalloc(&pl->perm_b, (size_t)n))) break;
-        } else {
-            free_levels(pl->L);
-        }
-        free_levels(pl->U);
-        s->t_factor = now_s() - t1;
-        // solve form: one dependency-driven launch per group (default whenever there is more than one level
-        // to chain), or one launch per level / run of small levels (option TRSV_SYNCFREE = 0)
-        {
-            const Config &cfg = s->ctx->cfg;
-            const bool on = cfg.trsv_syncfree != 0;
-            // narrow levels (mat10000: <= 100 rows each): the whole factor runs as ONE single-workgroup launch with a
-            // barrier per level (0.75 us per level, measured), which beats hand-offs through memory (1.0 us); from a few
-            // hundred rows per level on, the dependency-driven form wins (Poisson 4000x2500: 6x)
-            auto widest = [](const TriFactor &F) {
-                int w = 0;
-                for (int l = 0; l < F.nlevels; l++) w = std::max(w, F.level_ptr[(size_t)l + 1] - F.level_ptr[(size_t)l]);
-                return w;
-            };
-            const bool forced = cfg.trsv_syncfree == 1;
-            pl->L.syncfree = on && s->L.nlevels > 1 && (forced || widest(s->L) > 512);
-            pl->U.syncfree = on && s->U.nlevels > 1 && (forced || widest(s->U) > 512);
-            const bool lds_on = cfg.trsv_lds && n > 0 && n <= kLdsTrsvRows;
-            pl->L.lds = lds_on && !pl->L.hybrid && widest(s->L) <= 512;
-            pl->U.lds = lds_on && !pl->U.hybrid && widest(s->U) <= 512;
-            if (cfg.trsv_spin_limit) pl->L.spin_limit = pl->U.spin_limit = cfg.trsv_spin_limit;
-            int strict = 0;
-            if ((rc = pb_strict_for(s->ctx, &strict))) break;
-            pl->L.pb_strict = pl->U.pb_strict = strict;
-            // Resident workgroups per CU of the dependency-driven launch.  Every waiting row polls memory, and pollers
-            // slow the very hand-offs they wait for: with little work per level the chain of hand-offs is the whole
-            // cost and FEWER resident workgroups are faster (Poisson 4000x2500, 5 K entries per level: 27.6 ms per
-            // application at 8 per CU, 15.0 ms at 1); with much work per level the gathers need the occupancy
-            // (1e6 x 50 random, 190 K entries per level: 1.75 ms at 1, 0.82 ms at 4, 0.89 ms at 8).
-            auto pick_occ = [](const TriFactor &F) {
-                const double per_level = F.nlevels > 0 ? (double)F.nnz / F.nlevels : 0.0;
-                return per_level < 16384.0 ? 1 : per_level < 131072.0 ? 2 : 4;
-            };
-            pl->L.occ = pick_occ(s->L);
-            pl->U.occ = pick_occ(s->U);
-            for (TriHost *h : {&pl->L, &pl->U}) {
-                const size_t k = h->grp_level.size() > 1 ? h->grp_level.size() - 1 : 1;
-                if (!h->tickets && (rc = dalloc(&h->tickets, k))) break;
-            }
-            if (rc) break;
-            // (The early column blocks of a group's far phase 1 on a side stream beside the previous group's near launch were
-            // built and measured in round 3, alternating A/B at C5: 4.95 ms per L^-1 U^-1 with the overlap against 4.78
-            // without -- the streaming phase 1 and the gathering near launch compete for the same fabric requests, and the
-            // near launch loses its one-workgroup-per-CU residency.  Removed in round 4; HISTORY.md.)
-        }
-        s->has_ilu = true;
-    } while (0);
-    if (d_flags) CM_DROP(hipFree(d_flags));
-    if (d_lev) CM_DROP(hipFree(d_lev));
-    d_flags = nullptr;
-    d_lev = nullptr;
-    if (rc) {
-        char saved[512];
-        snprintf(saved, sizeof(saved), "%s", cudamat_last_error());
-        ilu0_release(s);
-        set_error("%s", saved);
+    // ---- factorisation on a copy of A's values (pbicgstab.cu:316, :356-363)
+    const double t1 = now_s();
+    double t_stamp = t1;
+    CM_TRY(s->lu.alloc((size_t)s->pm_nnz));
+    if (hipMemcpyAsync(s->lu, s->pm_val, sizeof(double) * (size_t)s->pm_nnz, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        set_error("copy of A values failed");
+        return CUDAMAT_ERR_HIP;
     }
-    return rc;
+    const int maxrow = maxrow_all;
+    const int cap = ((maxrow + 63) / 64) * 64 + 64;
+    const bool one_wave = cap > 2048;
+    const bool fast = cap <= 1024 && !s->ctx->cfg.ilu0_simple;
+    if ((size_t)cap * sizeof(double) > 150 * 1024) {
+        set_error("ILU(0): a row with %d entries exceeds the %d-entry LDS staging limit", maxrow, 150 * 1024 / 8);
+        return CUDAMAT_ERR_ARG;
+    }
+    if (hipMemsetAsync(d_flags, 0, 2 * sizeof(int), st) != hipSuccess) return CUDAMAT_ERR_HIP;
+    CM_TRY(set_max_lds((const void *)k_ilu0_level<1>));
+    CM_TRY(set_max_lds((const void *)k_ilu0_level<4>));
+    CM_TRY(set_max_lds((const void *)k_ilu0_level_fast<4>));
+    for (int l = 0; l < s->L.nlevels; l++) {
+        const int r0 = s->L.level_ptr[(size_t)l], r1 = s->L.level_ptr[(size_t)l + 1];
+        const int rows = r1 - r0;
+        if (fast) {     // 28 bytes of LDS per entry slot and wave: values, pivots, columns, two pivot tables
+            hipLaunchKernelGGL(k_ilu0_level_fast<4>, dim3((rows + 3) / 4), dim3(256), (size_t)28 * 4 * (size_t)cap, st,
+                               r0, r1, s->L.row_of, s->pm_rp, s->pm_ci, s->diag_pos, s->lu, cap, d_flags);
+        } else if (one_wave) {
+            hipLaunchKernelGGL(k_ilu0_level<1>, dim3(rows), dim3(64), sizeof(double) * (size_t)cap, st, r0, r1,
+                               s->L.row_of, s->pm_rp, s->pm_ci, s->diag_pos, s->lu, cap, d_flags);
+        } else {
+            hipLaunchKernelGGL(k_ilu0_level<4>, dim3((rows + 3) / 4), dim3(256), sizeof(double) * 4 * (size_t)cap, st,
+                               r0, r1, s->L.row_of, s->pm_rp, s->pm_ci, s->diag_pos, s->lu, cap, d_flags);
+        }
+    }
+    if (hipGetLastError() != hipSuccess) { set_error("ilu0 launch failed"); return CUDAMAT_ERR_HIP; }
+    if (hipMemcpyAsync(hflags, d_flags, sizeof(hflags), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) { set_error("ilu0 failed"); return CUDAMAT_ERR_HIP; }
+    if (hflags[1]) {
+        set_error("ILU(0): zero pivot in row %d", hflags[1] - 1);
+        return CUDAMAT_ERR_ZERO_PIVOT;
+    }
+    CM_STAMP("numeric ILU(0)");
+    CM_TRY(fill_factor(s, false, s->L));
+    CM_TRY(fill_factor(s, true, s->U));
+    if (hipStreamSynchronize(st) != hipSuccess) { set_error("factor fill failed"); return CUDAMAT_ERR_HIP; }
+    CM_STAMP("factor fill");
+    if (pl->L.hybrid && pl->U.hybrid) {
+        // level-major index spaces: position of every original row in L's and in U's order
+        DevBuf<int> posL, mapUL;
+        const unsigned gp = (unsigned)((n + kBlock - 1) / kBlock);
+        CM_TRY(posL.alloc((size_t)n));
+        CM_TRY(pl->posU.alloc((size_t)n));
+        hipLaunchKernelGGL(k_invert_perm, dim3(gp), dim3(kBlock), 0, st, n, s->L.row_of, posL);
+        hipLaunchKernelGGL(k_invert_perm, dim3(gp), dim3(kBlock), 0, st, n, s->U.row_of, pl->posU);
+        CM_TRY(split_factor(s, s->L, pl->L, posL));
+        CM_TRY(split_factor(s, s->U, pl->U, pl->posU));
+        if (pl->L.hybrid && pl->U.hybrid) {
+            CM_TRY(mapUL.alloc((size_t)n));
+            hipLaunchKernelGGL(k_compose_perm, dim3(gp), dim3(kBlock), 0, st, n, s->U.row_of, posL, mapUL);
+            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+                set_error("permutation maps failed");
+                return CUDAMAT_ERR_HIP;
+            }
+        }
+        posL.reset();
+        if (!(pl->L.hybrid && pl->U.hybrid)) {
+            // (split_factor fell back on one side: out of memory for the blocked copies) -- a half-split pair has no
+            // consistent index space
+            set_error("ILU(0): not enough device memory for the far/near split of the factors");
+            return CUDAMAT_ERR_NOMEM;
+        }
+        s->L.lm = s->U.lm = true;
+        s->L.rhs_of = s->L.out_of = nullptr;       // L: right-hand side and solution in L's level-major space
+        s->U.rhs_map = std::move(mapUL);           // U: right-hand side in L's space, solution in U's
+        s->U.rhs_of = s->U.rhs_map;
+        s->U.out_of = nullptr;
+        CM_TRY(pl->perm_a.alloc((size_t)n));
+        CM_TRY(pl->perm_b.alloc((size_t)n));
+    } else {
+        pl->L.lev_dev.reset();
+    }
+    pl->U.lev_dev.reset();
+    s->t_factor = now_s() - t1;
+    // solve form: one dependency-driven launch per group (default whenever there is more than one level
+    // to chain), or one launch per level / run of small levels (option TRSV_SYNCFREE = 0)
+    {
+        const Config &cfg = s->ctx->cfg;
+        const bool on = cfg.trsv_syncfree != 0;
+        // narrow levels (mat10000: <= 100 rows each): the whole factor runs as ONE single-workgroup launch with a
+        // barrier per level (0.75 us per level, measured), which beats hand-offs through memory (1.0 us); from a few
+        // hundred rows per level on, the dependency-driven form wins (Poisson 4000x2500: 6x)
+        auto widest = [](const TriFactor &F) {
+            int w = 0;
+            for (int l = 0; l < F.nlevels; l++) w = std::max(w, F.level_ptr[(size_t)l + 1] - F.level_ptr[(size_t)l]);
+            return w;
+        };
+        const bool forced = cfg.trsv_syncfree == 1;
+        pl->L.syncfree = on && s->L.nlevels > 1 && (forced || widest(s->L) > 512);
+        pl->U.syncfree = on && s->U.nlevels > 1 && (forced || widest(s->U) > 512);
+        const bool lds_on = cfg.trsv_lds && n > 0 && n <= kLdsTrsvRows;
+        pl->L.lds = lds_on && !pl->L.hybrid && widest(s->L) <= 512;
+        pl->U.lds = lds_on && !pl->U.hybrid && widest(s->U) <= 512;
+        if (cfg.trsv_spin_limit) pl->L.spin_limit = pl->U.spin_limit = cfg.trsv_spin_limit;
+        int strict = 0;
+        CM_TRY(pb_strict_for(s->ctx, &strict));
+        pl->L.pb_strict = pl->U.pb_strict = strict;
+        // Resident workgroups per CU of the dependency-driven launch.  Every waiting row polls memory, and pollers
+        // slow the very hand-offs they wait for: with little work per level the chain of hand-offs is the whole
+        // cost and FEWER resident workgroups are faster (Poisson 4000x2500, 5 K entries per level: 27.6 ms per
+        // application at 8 per CU, 15.0 ms at 1); with much work per level the gathers need the occupancy
+        // (1e6 x 50 random, 190 K entries per level: 1.75 ms at 1, 0.82 ms at 4, 0.89 ms at 8).
+        auto pick_occ = [](const TriFactor &F) {
+            const double per_level = F.nlevels > 0 ? (double)F.nnz / F.nlevels : 0.0;
+            return per_level < 16384.0 ? 1 : per_level < 131072.0 ? 2 : 4;
+        };
+        pl->L.occ = pick_occ(s->L);
+        pl->U.occ = pick_occ(s->U);
+        for (TriHost *h : {&pl->L, &pl->U}) {
+            const size_t k = h->grp_level.size() > 1 ? h->grp_level.size() - 1 : 1;
+            if (!h->tickets) CM_TRY(h->tickets.alloc(k));
+        }
+        // (The early column blocks of a group's far phase 1 on a side stream beside the previous group's near launch were
+        // built and measured in round 3, alternating A/B at C5: 4.95 ms per L^-1 U^-1 with the overlap against 4.78
+        // without -- the streaming phase 1 and the gathering near launch compete for the same fabric requests, and the
+        // near launch loses its one-workgroup-per-CU residency.  Removed in round 4; HISTORY.md.)
+    }
+    s->has_ilu = true;
+    return CUDAMAT_OK;
 }
 
 __global__ __launch_bounds__(kBlock) void k_perm_row_len(int n, const int *rp, const int *row_of, int *len)
@@ -1438,33 +1386,31 @@ int ilu_perm_matrix(cudamat_solver *s)
     const int64_t nnz = s->pm_nnz;
     const double t0 = now_s();
     double t_stamp = t0;
-    int *d_rp = nullptr, *d_ci = nullptr, *d_len = nullptr;
-    double *d_val = nullptr;
-    int rc = CUDAMAT_OK;
-    do {
-        if ((rc = dalloc(&d_rp, (size_t)n + 1))) break;
-        if ((rc = dalloc(&d_len, (size_t)n))) break;
-        if ((rc = dalloc(&d_ci, (size_t)nnz))) break;
-        if ((rc = dalloc(&d_val, (size_t)nnz))) break;
+    auto build = [&]() -> int {
+        DevBuf<int> d_rp, d_ci, d_len;
+        DevBuf<double> d_val;
+        CM_TRY(d_rp.alloc((size_t)n + 1));
+        CM_TRY(d_len.alloc((size_t)n));
+        CM_TRY(d_ci.alloc((size_t)nnz));
+        CM_TRY(d_val.alloc((size_t)nnz));
         CM_STAMP("perm: allocations");
         // row pointers of the permuted matrix: lengths of the rows in L's order, prefix sums on the device
         hipLaunchKernelGGL(k_perm_row_len, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, n, s->pm_rp, s->L.row_of, d_len);
-        if ((rc = device_exclusive_scan(st, n, d_len, d_rp))) break;
-        if ((rc = launch_sort_rows(st, n, s->pm_rp, s->L.row_of, d_rp, s->pm_ci, s->pm_val, pl->posU, d_ci, d_val))) break;
+        CM_TRY(device_exclusive_scan(st, n, d_len, d_rp));
+        CM_TRY(launch_sort_rows(st, n, s->pm_rp, s->L.row_of, d_rp, s->pm_ci, s->pm_val, pl->posU, d_ci, d_val));
         CM_STAMP("perm: rows permuted and sorted");
         if (nnz >= (1 << 20)) {
-            if ((rc = valdict_build(st, s->ctx->cfg, nnz, d_val, &s->vd_perm))) break;       // (n == 0 afterwards: no dictionary, fp64 values)
+            CM_TRY(valdict_build(st, s->ctx->cfg, nnz, d_val, &s->vd_perm));       // (n == 0 afterwards: no dictionary, fp64 values)
         }
         CM_STAMP("perm: value dictionary");
-        if ((rc = pb_build(st, s->ctx->cfg, n, n, nnz, d_rp, d_ci, d_val, &s->pb_perm, nullptr, &s->vd_perm))) break;
+        CM_TRY(pb_build(st, s->ctx->cfg, n, n, nnz, d_rp, d_ci, d_val, &s->pb_perm, nullptr, &s->vd_perm));
         CM_STAMP("perm: blocked copy");
-        if (!s->x_perm && (rc = dalloc(&s->x_perm, (size_t)(s->n_pad > n ? s->n_pad : n)))) break;
-        if (!s->b_perm && (rc = dalloc(&s->b_perm, (size_t)(s->n_pad > n ? s->n_pad : n)))) break;
-        if (hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("permuted matrix build failed"); break; }
-    } while (0);
-    void *tmp[] = {d_rp, d_ci, d_val, d_len};
-    for (void *q : tmp)
-        if (q) CM_DROP(hipFree(q));
+        if (!s->x_perm) CM_TRY(s->x_perm.alloc((size_t)(s->n_pad > n ? s->n_pad : n)));
+        if (!s->b_perm) CM_TRY(s->b_perm.alloc((size_t)(s->n_pad > n ? s->n_pad : n)));
+        if (hipStreamSynchronize(st) != hipSuccess) { set_error("permuted matrix build failed"); return CUDAMAT_ERR_HIP; }
+        return CUDAMAT_OK;
+    };
+    const int rc = build();                // (its temporaries are released on the way out)
     CM_STAMP("perm: temporaries freed");
     if (rc) {
         pb_free(&s->pb_perm);
@@ -1472,8 +1418,7 @@ int ilu_perm_matrix(cudamat_solver *s)
         return rc;
     }
     s->perm_ready = true;
-    CM_DROP(hipFree(pl->posU));
-    pl->posU = nullptr;
+    pl->posU.reset();
     s->t_perm_matrix = now_s() - t0;
     s->t_factor += s->t_perm_matrix;       // (cudamat_stats.t_factor: everything between the level analysis and the first iteration)
     if (s->ctx->cfg.verbose) fprintf(stderr, "[cudamat] ilu0 permuted matrix (rows in L order, columns in U positions) %8.3f ms\n", s->t_perm_matrix * 1e3);

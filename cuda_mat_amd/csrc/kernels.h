@@ -23,30 +23,30 @@ struct SpmvPlan {
     int rows_per_block;   // contiguous rows owned by a workgroup
     int stream_rows;      // > 0: LDS-staged stream kernel, this many rows per LDS tile (short rows)
     // > 0: nnz-balanced tiles of 2048 entries (skewed row lengths); rows_per_block = tiles per workgroup;
-    // the tables are owned by the plan (plan_spmv_free)
+    // the tables are owned by the plan
     int tiles = 0;
     int tile_nspan = 0, tile_fix_grid = 0;
-    int *tile_S = nullptr, *tile_span = nullptr;
-    double *tile_heads = nullptr, *tile_tails = nullptr;
+    DevBuf<int> tile_S, tile_span;
+    DevBuf<double> tile_heads, tile_tails;
     double lane_cost = 0.0;   // lane-iterations of the lanes-per-row kernel / nnz (1 = perfectly balanced)
     // stream kernel with compressed indices (banded matrices): 16-bit column offsets from the tile's first row,
     // 8-bit row lengths, one entry offset per tile; owned by the plan
-    short *c_off16 = nullptr;
-    unsigned char *c_len8 = nullptr;
-    int *c_tile_base = nullptr;
+    DevBuf<short> c_off16;
+    DevBuf<unsigned char> c_len8;
+    DevBuf<int> c_tile_base;
     // line-aligned copies for the compressed stream kernel (plan_spmv_align, round 3): every tile's entries start on a
     // 64-entry boundary, so each wave's 512-byte value load and 128-byte offset load covers whole 128-byte lines
-    int *a_base = nullptr;              // ntiles + 1: first entry slot of every tile
-    short *a_off16 = nullptr;
-    double *a_val = nullptr;
+    DevBuf<int> a_base;                 // ntiles + 1: first entry slot of every tile
+    DevBuf<short> a_off16;
+    DevBuf<double> a_val;
     // the matrix's value dictionary (valdict.h; 256 doubles on the device, not owned) when the copies below exist
     const double *c_dict = nullptr;
     // dictionary form of the compressed stream kernel (plan_spmv_dict): per tile, the entries' 16-bit offsets and 8-bit
     // value indices padded to a multiple of 8 entries, so that a thread fetches its 8 entries with one 16-byte and one
     // 8-byte load (owned by the plan)
-    int *d_pbase = nullptr;             // ntiles + 1: first padded entry of every tile
-    short *d_off16 = nullptr;
-    unsigned char *d_val8 = nullptr;
+    DevBuf<int> d_pbase;                // ntiles + 1: first padded entry of every tile
+    DevBuf<short> d_off16;
+    DevBuf<unsigned char> d_val8;
 };
 SpmvPlan plan_spmv(const Config &cfg, int n_rows, int64_t nnz);
 // The row partition of the lanes-per-row kernels (k_spmv<L>, k_spmm_csr<L, K>): every workgroup owns rows_per_block
@@ -65,7 +65,6 @@ inline void spmv_partition(int L, int n_rows, int *grid, int *rows_per_block)
     *grid = (int)(((long long)n_rows + per - 1) / per);
     if (*grid < 1) *grid = 1;
 }
-void plan_spmv_free(SpmvPlan *plan);
 // per-workgroup dot partials one launch leaves behind
 inline int plan_spmv_parts(const SpmvPlan &p) { return p.grid + (p.tiles ? p.tile_fix_grid : 0); }
 // short rows (mean <= 12): switch the plan to the LDS-staged stream kernel when every tile of

@@ -195,8 +195,8 @@ int Solve::setup()
     // a restart segment (abs_tol > 0) appends to the history of the segments before it (the kernels check the capacity)
     hist_base = abs_tol > 0.0 ? (s->hist_count < s->hist_cap ? s->hist_count : s->hist_cap) : 0;
     if (hist_base == 0 && need_hist > s->hist_cap) {
-        if (s->hist) { CM_HIP(hipStreamSynchronize(st)); CM_DROP(hipFree(s->hist)); s->hist = nullptr; }
-        CM_TRY(dev_alloc((void **)&s->hist, sizeof(double) * (size_t)need_hist));
+        if (s->hist) { CM_HIP(hipStreamSynchronize(st)); s->hist.reset(); }      // drained first, then released
+        CM_TRY(s->hist.alloc((size_t)need_hist));
         s->hist_cap = need_hist;
     }
     if (s->hist_cap > hist_base)
@@ -243,22 +243,22 @@ int Solve::pipelined_prologue()
     // residual replacement period (Cools & Vanroose): every rr-th iteration r, w, s, z (and their hatted forms, and v)
     // are recomputed from x and p, which discards the rounding errors the recurrences have accumulated
     pipe_rr = cfg->pipe_rr >= 0 ? cfg->pipe_rr : kPipeRR;
-    const size_t nb = sizeof(double) * (size_t)(s->n_pad > 0 ? s->n_pad : 1);
+    const size_t count = (size_t)(s->n_pad > 0 ? s->n_pad : 1), nb = sizeof(double) * count;
     if (!s->pz) {
-        double **vs[] = {&s->pz, &s->pww, &s->pq, &s->py, &s->pxh};
-        for (double **q : vs) {
-            CM_TRY(dev_alloc((void **)q, nb));
-            CM_HIP(hipMemsetAsync(*q, 0, nb, st));
+        DevBuf<double> *vs[] = {&s->pz, &s->pww, &s->pq, &s->py, &s->pxh};
+        for (DevBuf<double> *q : vs) {
+            CM_TRY(q->alloc(count));
+            CM_HIP(hipMemsetAsync(q->get(), 0, nb, st));
         }
-        CM_TRY(dev_alloc((void **)&s->pipeA, sizeof(double) * 3 * kVecGridMax));
-        CM_TRY(dev_alloc((void **)&s->pipeB, sizeof(double) * 5 * kVecGridMax));
-        CM_TRY(dev_alloc((void **)&s->red_pipe, sizeof(double) * 16));
+        CM_TRY(s->pipeA.alloc(3 * kVecGridMax));
+        CM_TRY(s->pipeB.alloc(5 * kVecGridMax));
+        CM_TRY(s->red_pipe.alloc(16));
     }
     if (pipe_pc && !s->prh) {
-        double **vs[] = {&s->prh, &s->pwh, &s->psh, &s->pzh, &s->pqh, &s->ptmp};
-        for (double **q : vs) {
-            CM_TRY(dev_alloc((void **)q, nb));
-            CM_HIP(hipMemsetAsync(*q, 0, nb, st));
+        DevBuf<double> *vs[] = {&s->prh, &s->pwh, &s->psh, &s->pzh, &s->pqh, &s->ptmp};
+        for (DevBuf<double> *q : vs) {
+            CM_TRY(q->alloc(count));
+            CM_HIP(hipMemsetAsync(q->get(), 0, nb, st));
         }
     }
     if (sharded && s->comm.allreduce_side && s->comm.reduce_stream) {
@@ -396,7 +396,7 @@ bool Solve::wants_resident()
 int Solve::run_resident(bool *gave_up)
 {
     loop_form = 2;
-    if (!s->bar) CM_TRY(dev_alloc((void **)&s->bar, 2 * sizeof(unsigned)));
+    if (!s->bar) CM_TRY(s->bar.alloc(2));
     SpmvArgs a{};
     a.n = n; a.rp = s->rp; a.ci = s->ci; a.val = s->val; a.x = nullptr; a.d = s->d; a.xd = nullptr;
     a.alpha = 1.0; a.beta = 0.0; a.check = CHECK_NONE; a.half = nosrc;
@@ -693,8 +693,8 @@ int solve_once(cudamat_solver *s, const double *b, double *x, int precond, int l
     if (q.pipelined) CM_TRY(q.pipelined_prologue());
     q.loop_form = !q.guard && q.wants_fused() ? 1 : 0;       // (a guarded solve: five launches, whatever the system's size)
     if (q.loop_form == 1 && !s->v2) {
-        const size_t nb = sizeof(double) * (size_t)(s->n_pad > 0 ? s->n_pad : 1);
-        CM_TRY(dev_alloc((void **)&s->v2, nb));
+        const size_t count = (size_t)(s->n_pad > 0 ? s->n_pad : 1), nb = sizeof(double) * count;
+        CM_TRY(s->v2.alloc(count));
         CM_HIP(hipMemsetAsync(s->v2, 0, nb, q.st));
     }
     q.p_a = s->p; q.p_b = s->pw; q.v_a = s->v; q.v_b = s->v2;
@@ -718,7 +718,7 @@ int solve_guarded(cudamat_solver *s, const double *b, double *x, int precond, in
                          !(flags & CUDAMAT_FLAG_X0_ONES);
     if (keep_x0) {
         CM_HIP(hipSetDevice(s->ctx->device));
-        if (!s->x0_save) CM_TRY(dev_alloc((void **)&s->x0_save, sizeof(double) * (size_t)(s->n > 0 ? s->n : 1)));
+        if (!s->x0_save) CM_TRY(s->x0_save.alloc((size_t)(s->n > 0 ? s->n : 1)));
         CM_HIP(hipMemcpyAsync(s->x0_save, x, sizeof(double) * (size_t)s->n, hipMemcpyDeviceToDevice, s->ctx->stream));
     }
     bool gave_up = false, resident_gave_up = false;

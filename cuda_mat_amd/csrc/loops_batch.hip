@@ -47,38 +47,36 @@ int64_t many_rows(const cudamat_solver *s)
     return rows > 0 ? rows : 1;
 }
 
-// The interleaved buffers come in three groups, each a list of (pointer, bytes for K columns, zeroed at allocation?): the plain
-// loop's -- seven vectors (r, rw, p, v, t, b, x), the partial sums, the K loop states --, the three further blocks of the
-// preconditioned loop: ph = M^-1 p, sh = M^-1 r and the scratch of L^-1; and the per-column shifts' one block.
+// The interleaved buffers come in three groups, each a list of (owner, doubles for K columns, zeroed at allocation?): the plain
+// loop's -- seven vectors (r, rw, p, v, t, b, x), the partial sums; the K loop states go with them --, the
+// three further blocks of the preconditioned loop: ph = M^-1 p, sh = M^-1 r and the scratch of L^-1; and the per-column
+// shifts' one block.
 enum Group { G_PLAIN = 0, G_PRECOND = 1, G_SHIFTS = 2 };
 
 int &group_cap(cudamat_solver *s, Group g) { return g == G_PRECOND ? s->many.pcap : g == G_SHIFTS ? s->many.dcap : s->many.cap; }
 
 struct Buf {
-    void **p;
-    size_t bytes;
+    DevBuf<double> *p;
+    size_t count;
     bool zero;
 };
 
 std::vector<Buf> many_group(cudamat_solver *s, Group g, int K)
 {
     ManyWork &m = s->many;
-    const size_t nb = sizeof(double) * (size_t)K * (size_t)many_rows(s);
-    if (g == G_SHIFTS) return {{(void **)&m.dk, nb, true}};
-    if (g == G_PRECOND) return {{(void **)&m.pw, nb, true}, {(void **)&m.s, nb, true}, {(void **)&m.lt, nb, true}};
-    const size_t pv = sizeof(double) * 2 * (size_t)K * kVecGridMax, ps = sizeof(double) * 2 * (size_t)K * kSpmvGridMax;
-    return {{(void **)&m.r, nb, true}, {(void **)&m.rw, nb, true}, {(void **)&m.p, nb, true}, {(void **)&m.v, nb, true},
-            {(void **)&m.t, nb, true}, {(void **)&m.b, nb, true}, {(void **)&m.x, nb, true},
-            {(void **)&m.parts_full, pv, false}, {(void **)&m.parts_half, pv, false}, {(void **)&m.parts_rv, ps, false},
-            {(void **)&m.parts_tt, ps, false}, {(void **)&m.st, sizeof(LoopState) * (size_t)K, false}};
+    const size_t nv = (size_t)K * (size_t)many_rows(s);
+    if (g == G_SHIFTS) return {{&m.dk, nv, true}};
+    if (g == G_PRECOND) return {{&m.pw, nv, true}, {&m.s, nv, true}, {&m.lt, nv, true}};
+    const size_t pv = 2 * (size_t)K * kVecGridMax, ps = 2 * (size_t)K * kSpmvGridMax;
+    return {{&m.r, nv, true}, {&m.rw, nv, true}, {&m.p, nv, true}, {&m.v, nv, true}, {&m.t, nv, true}, {&m.b, nv, true},
+            {&m.x, nv, true}, {&m.parts_full, pv, false}, {&m.parts_half, pv, false}, {&m.parts_rv, ps, false},
+            {&m.parts_tt, ps, false}};
 }
 
 void free_group(cudamat_solver *s, Group g)
 {
-    for (const Buf &b : many_group(s, g, 0)) {
-        if (*b.p) CM_DROP(hipFree(*b.p));
-        *b.p = nullptr;
-    }
+    for (const Buf &b : many_group(s, g, 0)) b.p->reset();
+    if (g == G_PLAIN) s->many.st.reset();
     group_cap(s, g) = 0;
 }
 
@@ -92,8 +90,7 @@ void many_release(cudamat_solver *s)
     free_group(s, G_PLAIN);
     free_group(s, G_PRECOND);
     free_group(s, G_SHIFTS);
-    if (m.hist) CM_DROP(hipFree(m.hist));
-    m.hist = nullptr;
+    m.hist.reset();
     m.hist_bytes = 0;
 }
 
@@ -113,9 +110,10 @@ int ensure_many(cudamat_solver *s, Group g, int K)
     else many_release(s);
     int rc = CUDAMAT_OK;
     for (const Buf &b : many_group(s, g, K)) {
-        if ((rc = dev_alloc(b.p, b.bytes))) break;
-        if (b.zero && (rc = CM_RC(hipMemsetAsync(*b.p, 0, b.bytes, st)))) break;
+        if ((rc = b.p->alloc(b.count))) break;
+        if (b.zero && (rc = CM_RC(hipMemsetAsync(b.p->get(), 0, sizeof(double) * b.count, st)))) break;
     }
+    if (!rc && g == G_PLAIN) rc = s->many.st.alloc((size_t)K);       // the K loop states
     if (rc) {
         CM_DROP(hipStreamSynchronize(st));
         free_group(s, g);
@@ -195,8 +193,8 @@ int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, do
     if (hist_out) {
         const size_t bytes = sizeof(double) * (size_t)K * (size_t)need;
         if (bytes > m.hist_bytes) {
-            if (m.hist) { CM_HIP(hipStreamSynchronize(st)); CM_DROP(hipFree(m.hist)); m.hist = nullptr; m.hist_bytes = 0; }
-            CM_TRY(dev_alloc((void **)&m.hist, bytes));
+            if (m.hist) { CM_HIP(hipStreamSynchronize(st)); m.hist.reset(); m.hist_bytes = 0; }      // drained first, then released
+            CM_TRY(m.hist.alloc((size_t)K * (size_t)need));
             m.hist_bytes = bytes;
         }
         hist = m.hist;

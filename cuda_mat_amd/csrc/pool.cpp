@@ -47,6 +47,8 @@ struct DevicePool {
 std::mutex g_mu;
 std::map<int, DevicePool> g_pools;
 std::atomic<unsigned> g_generation{0};
+// allocations handed out and not yet freed, pooled or not (pool_live): every owner that forgets a buffer shows here
+std::atomic<long long> g_live{0};
 int g_enabled = -1;
 
 bool enabled()
@@ -88,11 +90,7 @@ void trim_locked(DevicePool &dp, size_t keep)
     }
 }
 
-}  // namespace
-
-bool pool_enabled() { return enabled(); }
-
-hipError_t pool_malloc(void **out, size_t bytes)
+hipError_t malloc_uncounted(void **out, size_t bytes)
 {
     if (!out) return hipErrorInvalidValue;
     *out = nullptr;
@@ -131,9 +129,8 @@ hipError_t pool_malloc(void **out, size_t bytes)
     return hipSuccess;
 }
 
-hipError_t pool_free(void *p)
+hipError_t free_uncounted(void *p)
 {
-    if (!p) return hipSuccess;
     if (!enabled()) return hipFree(p);
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -178,6 +175,31 @@ hipError_t pool_free(void *p)
     list_free(dp, it->first, it->second.size);
     if (dp.free_bytes > kKeepFree) trim_locked(dp, kKeepFree);
     return es;
+}
+
+}  // namespace
+
+bool pool_enabled() { return enabled(); }
+
+hipError_t pool_malloc(void **out, size_t bytes)
+{
+    const hipError_t e = malloc_uncounted(out, bytes);
+    if (e == hipSuccess) g_live.fetch_add(1);
+    return e;
+}
+
+hipError_t pool_free(void *p)
+{
+    if (!p) return hipSuccess;
+    const hipError_t e = free_uncounted(p);
+    if (e == hipSuccess) g_live.fetch_sub(1);
+    return e;
+}
+
+size_t pool_live()
+{
+    const long long v = g_live.load();
+    return v > 0 ? (size_t)v : 0;
 }
 
 // keep the first `bytes` of a pooled block, hand the rest back to the free list (a caller that asked for more than it keeps:
@@ -237,6 +259,7 @@ bool pool_split(void *p, size_t offset)
         if (b.free || offset >= b.size) return false;
         dp.blocks[(char *)p + offset] = Block{b.size - offset, false, b.seg};
         b.size = offset;
+        g_live.fetch_add(1);               // (two allocations now, each freed on its own)
         return true;
     }
     return false;

@@ -170,8 +170,8 @@ void rank_main(Job *j)
 
     cudamat_ctx *ctx = nullptr;
     cudamat_solver *s = nullptr;
-    int *d_rp = nullptr, *d_ci = nullptr;
-    double *d_val = nullptr, *d_b = nullptr, *d_x = nullptr, *d_d = nullptr;
+    cm::DevBuf<int> d_rp, d_ci;                    // on the device cudamat_ctx_create made current for this thread
+    cm::DevBuf<double> d_val, d_b, d_x, d_d;
     cudamat_comm comm;
     memset(&comm, 0, sizeof(comm));
     EmuComm emu{sh, rank, nullptr};
@@ -184,18 +184,18 @@ void rank_main(Job *j)
             std::vector<int> rp((size_t)nloc + 1);
             for (int i = 0; i <= nloc; i++) rp[(size_t)i] = j->iA[row0 + i] - j->iA[row0] + j->base;
             const size_t nn = (size_t)(nnz_loc > 0 ? nnz_loc : 1), nv = (size_t)(nloc > 0 ? nloc : 1);
-            if (!rc) rc = cudamat_malloc(ctx, sizeof(int) * ((size_t)nloc + 1), (void **)&d_rp);
-            if (!rc) rc = cudamat_malloc(ctx, sizeof(int) * nn, (void **)&d_ci);
-            if (!rc) rc = cudamat_malloc(ctx, sizeof(double) * nn, (void **)&d_val);
-            if (!rc) rc = cudamat_malloc(ctx, sizeof(double) * nv, (void **)&d_b);
-            if (!rc) rc = cudamat_malloc(ctx, sizeof(double) * nv, (void **)&d_x);
+            if (!rc) rc = d_rp.alloc((size_t)nloc + 1);
+            if (!rc) rc = d_ci.alloc(nn);
+            if (!rc) rc = d_val.alloc(nn);
+            if (!rc) rc = d_b.alloc(nv);
+            if (!rc) rc = d_x.alloc(nv);
             if (!rc) rc = cudamat_h2d(ctx, d_rp, rp.data(), sizeof(int) * ((size_t)nloc + 1));
             if (!rc && nnz_loc > 0) rc = cudamat_h2d(ctx, d_ci, j->jA + k0, sizeof(int) * (size_t)nnz_loc);
             if (!rc && nnz_loc > 0) rc = cudamat_h2d(ctx, d_val, j->A + k0, sizeof(double) * (size_t)nnz_loc);
             if (!rc && nloc > 0) rc = cudamat_h2d(ctx, d_b, j->b + row0, sizeof(double) * (size_t)nloc);
             if (!rc && nloc > 0 && j->x0) rc = cudamat_h2d(ctx, d_x, j->x0 + row0, sizeof(double) * (size_t)nloc);
             if (!rc && j->d) {
-                rc = cudamat_malloc(ctx, sizeof(double) * nv, (void **)&d_d);
+                rc = d_d.alloc(nv);
                 if (!rc && nloc > 0) rc = cudamat_h2d(ctx, d_d, j->d + row0, sizeof(double) * (size_t)nloc);
             }
             if (!rc) rc = cudamat_solver_create(ctx, nloc, j->n, nnz_loc, d_rp, d_ci, d_val, j->base, &s);
@@ -245,10 +245,12 @@ void rank_main(Job *j)
     if (sh->failed.load() && native) cudamat_rccl_comm_abort(&comm);
     if (s) cudamat_solver_destroy(s);
     if (native) cudamat_rccl_comm_destroy(&comm);
-    void *ptrs[] = {d_rp, d_ci, d_val, d_b, d_x, d_d};
-    for (void *p : ptrs)
-        if (p) cudamat_free(ctx, p);
-    if (ctx) cudamat_ctx_destroy(ctx);
+    if (ctx) {
+        cudamat_ctx_sync(ctx);
+        for (cm::DevBuf<int> *p : {&d_rp, &d_ci}) p->reset();
+        for (cm::DevBuf<double> *p : {&d_val, &d_b, &d_x, &d_d}) p->reset();
+        cudamat_ctx_destroy(ctx);
+    }
 }
 
 }  // namespace

@@ -1,5 +1,6 @@
 // solver.h -- the HBM-resident system behind cudamat_solver_* (internal).
 #pragma once
+#include <memory>
 #include <vector>
 
 #include "kernels.h"
@@ -17,16 +18,17 @@ constexpr int kPipeRR = 32;         // residual replacement period of the pipeli
 struct TriFactor {                 // one triangular factor in level-major storage
     int nlevels = 0;
     std::vector<int> level_ptr;    // host: rows of level l are [level_ptr[l], level_ptr[l+1])
-    int *rp = nullptr;             // device, n+1, rows in level order, 0-based
-    int *ci = nullptr;             // device, column ids (original numbering)
-    double *val = nullptr;         // device
-    int *row_of = nullptr;         // device: original row id of permuted row
-    double *dinv = nullptr;        // device: 1/diag in permuted order (upper only)
+    DevBuf<int> rp;                // device, n+1, rows in level order, 0-based
+    DevBuf<int> ci;                // device, column ids (original numbering)
+    DevBuf<double> val;            // device
+    DevBuf<int> row_of;            // device: original row id of permuted row
+    DevBuf<double> dinv;           // device: 1/diag in permuted order (upper only)
     int64_t nnz = 0;
     // index spaces of a solve (trsv.hip tri_rows): permuted row pr reads rhs[rhs_of[pr]], writes out[out_of[pr]]
     // (nullptr = pr itself); `ci` holds indices into out.  Original space: both = row_of.  Level-major space (lm,
-    // hybrid factors): out_of = nullptr; rhs_of = nullptr for L, the U-position -> L-position map (owned) for U.
-    int *rhs_of = nullptr, *out_of = nullptr;
+    // hybrid factors): out_of = nullptr; rhs_of = nullptr for L, the U-position -> L-position map (rhs_map) for U.
+    int *rhs_of = nullptr, *out_of = nullptr;   // views, not owned
+    DevBuf<int> rhs_map;
     bool lm = false;
 };
 
@@ -35,16 +37,16 @@ struct TriFactor {                 // one triangular factor in level-major stora
 struct ManyWork {
     // the plain loop: seven vectors of `cap` columns, the partial sums, `cap` loop states (device)
     int cap = 0;                // columns the group holds (0: not allocated)
-    double *r = nullptr, *rw = nullptr, *p = nullptr, *v = nullptr, *t = nullptr, *b = nullptr, *x = nullptr;
-    double *parts_full = nullptr, *parts_rv = nullptr, *parts_half = nullptr, *parts_tt = nullptr;
-    LoopState *st = nullptr;
+    DevBuf<double> r, rw, p, v, t, b, x;
+    DevBuf<double> parts_full, parts_rv, parts_half, parts_tt;
+    DevBuf<LoopState> st;
     // the preconditioned loop: M^-1 p, M^-1 r and the scratch of L^-1 (`pcap` columns; allocated at its first use)
     int pcap = 0;
-    double *pw = nullptr, *s = nullptr, *lt = nullptr;
+    DevBuf<double> pw, s, lt;
     // per-column shifts (cudamat_solver_spmm_shifts / _solve_shifts): one block of `dcap` columns, allocated at its first use
     int dcap = 0;
-    double *dk = nullptr;
-    double *hist = nullptr;     // device: per column a history of the batch's length (hist_bytes in all)
+    DevBuf<double> dk;
+    DevBuf<double> hist;        // device: per column a history of the batch's length (hist_bytes in all)
     size_t hist_bytes = 0;
     std::vector<std::vector<double>> hist_host;   // per column: the residual history of the last cudamat_solver_solve_many
     // form choice (MANY_FORM / MANY_PRECOND = auto): seconds of tune_iters iterations, single loop (< 0: not timed) and batched by log2 K
@@ -54,14 +56,16 @@ struct ManyWork {
 
 }  // namespace cm
 
+struct IluPlans;
+
 struct cudamat_solver {
     cudamat_ctx *ctx = nullptr;
     int n = 0;                 // local rows
     int n_pad = 0;             // rows per rank in a sharded run (== n when single)
     int64_t n_cols = 0;
     int64_t nnz = 0;
-    int *rp = nullptr, *ci = nullptr;
-    double *val = nullptr;
+    cm::DevBuf<int> rp, ci;
+    cm::DevBuf<double> val;
     const double *d = nullptr;
     cm::SpmvPlan plan{};
     int spmv_mode = -1;        // -1 undecided, 0 CSR forms, 1 blocked two-phase kernels, 2 SELL-C-sigma, 3 row-pattern dictionary
@@ -77,27 +81,26 @@ struct cudamat_solver {
     double col_span_bytes = -1.0; // mean (last - first column) * 8 over sampled rows (-1: not sampled)
 
     // work vectors (n_pad doubles each, pad kept zero)
-    double *r = nullptr, *rw = nullptr, *p = nullptr, *pw = nullptr, *s = nullptr, *t = nullptr,
-           *v = nullptr;
-    double *gather = nullptr;  // world * n_pad doubles (sharded runs)
-    double *x0_save = nullptr; // the caller's x0, kept while a dependency-driven preconditioner may have to be redone
-    double *v2 = nullptr;      // second v buffer of the fused small-system loop (p and r double-buffer in pw and s)
+    cm::DevBuf<double> r, rw, p, pw, s, t, v;
+    cm::DevBuf<double> gather; // world * n_pad doubles (sharded runs)
+    cm::DevBuf<double> x0_save; // the caller's x0, kept while a dependency-driven preconditioner may have to be redone
+    cm::DevBuf<double> v2;     // second v buffer of the fused small-system loop (p and r double-buffer in pw and s)
     // CUDAMAT_LOOP_PIPELINED: z = A s, w = A r, q, y = A q, xh = x + alpha p (n_pad each), partials of k_pipe_a / k_pipe_b,
     // reduced scalars ([0..2] phase A, [8..12] phase B), events ordering the side-stream reductions
-    double *pz = nullptr, *pww = nullptr, *pq = nullptr, *py = nullptr, *pxh = nullptr;
-    double *prh = nullptr, *pwh = nullptr, *psh = nullptr, *pzh = nullptr, *pqh = nullptr, *ptmp = nullptr;   // preconditioned pipelined loop: M^-1 r, w, s, z, q; scratch
-    double *pipeA = nullptr, *pipeB = nullptr, *red_pipe = nullptr;
+    cm::DevBuf<double> pz, pww, pq, py, pxh;
+    cm::DevBuf<double> prh, pwh, psh, pzh, pqh, ptmp;   // preconditioned pipelined loop: M^-1 r, w, s, z, q; scratch
+    cm::DevBuf<double> pipeA, pipeB, red_pipe;
     hipEvent_t ev_red[2] = {}, ev_red_done[2] = {};
 
     // reduction workspace: four stages of per-workgroup partials + reduced scalars
-    double *parts_full = nullptr, *parts_rv = nullptr, *parts_half = nullptr, *parts_tt = nullptr;
-    double *red = nullptr;     // 8 doubles
-    cm::LoopState *st = nullptr;       // device
-    cm::LoopState *st_ring = nullptr;  // pinned host, kRing slots
+    cm::DevBuf<double> parts_full, parts_rv, parts_half, parts_tt;
+    cm::DevBuf<double> red;    // 8 doubles
+    cm::DevBuf<cm::LoopState> st;             // device
+    cm::PinnedBuf<cm::LoopState> st_ring;     // pinned host, kRing slots
     hipEvent_t ev[cm::kRing] = {};
-    unsigned long long *snap_host = nullptr;   // pinned: per-iteration progress words written by k_full
+    cm::PinnedBuf<unsigned long long> snap_host;   // pinned: per-iteration progress words written by k_full
     unsigned long long *snap_dev = nullptr;    // the same memory as the device sees it
-    double *hist = nullptr;    // device
+    cm::DevBuf<double> hist;   // device
     int hist_cap = 0;
     int hist_count = 0;
     int last_loop = 0;
@@ -134,26 +137,28 @@ struct cudamat_solver {
     bool windows_known = false;
     std::vector<int64_t> w_send_off, w_send_cnt, w_recv_off, w_recv_cnt;
     double gather_fraction = 1.0;
-    double *need_dev = nullptr;   // 2 * world (mine) + 2 * world^2 (everybody's) doubles
+    cm::DevBuf<double> need_dev;  // 2 * world (mine) + 2 * world^2 (everybody's) doubles
 
     // ILU(0)
     bool has_ilu = false;
     // the matrix the preconditioner is built from: the solver's own CSR, or -- block-Jacobi in a sharded
     // run -- a copy of the rank's diagonal block with local column ids
-    int *pm_rp = nullptr, *pm_ci = nullptr;
+    int *pm_rp = nullptr, *pm_ci = nullptr;      // what the kernels read: the solver's arrays or the copy below
     double *pm_val = nullptr;
     int64_t pm_nnz = 0;
     bool pm_owned = false;
+    cm::DevBuf<int> pm_own_rp, pm_own_ci;        // the diagonal block's copy (pm_owned)
+    cm::DevBuf<double> pm_own_val;
     bool ilu_block = false;    // factors belong to CUDAMAT_PRECOND_BLOCK_ILU0
-    double *lu = nullptr;      // pm_nnz doubles on that matrix's pattern
-    int *diag_pos = nullptr;   // position of the diagonal in each row
+    cm::DevBuf<double> lu;     // pm_nnz doubles on that matrix's pattern
+    cm::DevBuf<int> diag_pos;  // position of the diagonal in each row
     cm::TriFactor L, U;
-    void *ilu_plans = nullptr;  // launch plans (ilu.h) owned by ilu.hip
+    std::unique_ptr<IluPlans> ilu_plans;  // launch plans (ilu.h); complete where a solver is destroyed (solver.hip)
     // the loop in level-major spaces (hybrid factors, one GPU): the matrix with rows in L's order and columns in U's
     // positions as a blocked copy, b in L's space, x in U's
     cm::PbPlan pb_perm{};
     cm::ValDict vd_perm;
-    double *x_perm = nullptr, *b_perm = nullptr;
+    cm::DevBuf<double> x_perm, b_perm;
     bool perm_ready = false;    // pb_perm is built
     bool perm_failed = false;   // ... could not be (out of memory): the loop permutes around every M^-1 instead
     bool perm_active = false;   // the solve in progress runs in the level-major spaces (spmv_local uses pb_perm)
@@ -162,7 +167,7 @@ struct cudamat_solver {
     int trsv_fallbacks = 0;     // solves redone level by level after a dependency-driven wait timed out
     cm::ValDict vd;             // value dictionary of the matrix (n == 0: more than 256 distinct values, or not looked yet)
     bool vd_tried = false;
-    unsigned *bar = nullptr;    // grid barrier words of the single-launch loop (device)
+    cm::DevBuf<unsigned> bar;   // grid barrier words of the single-launch loop (device)
     int test_allreduces = 0;    // fault injection (CUDAMAT_TEST_COMM_FAIL)
     bool resident_off = false;  // a barrier wait ran into its bound once: keep to the three-launch loop
     int device_cus = 0;         // compute units of the device (0: not asked yet)
@@ -173,7 +178,6 @@ struct cudamat_solver {
 
 namespace cm {
 // ---- solver.hip: what the loops (loops.hip) and the drop-in entry point (dropin.hip) use of the resident system
-int dev_alloc(void **p, size_t bytes);
 // creation in stages (cudamat_solver_create = all three on device arrays; dropin.hip runs them beside the upload)
 int solver_alloc(cudamat_ctx *ctx, int n_local, int64_t n_cols, int64_t nnz, cudamat_solver **out);   // rp / ci / val allocated, EMPTY
 int solver_setup_pattern(cudamat_solver *s);         // rp, ci in place (0-based): validation, CSR plan, compressed indices

@@ -26,49 +26,37 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "ilu.h"      // IluPlans complete: a solver is created and destroyed here
 #include "solver.h"
 
 using namespace cm;
 
 namespace cm {
 
-int dev_alloc(void **p, size_t bytes)
-{
-    *p = nullptr;
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? CUDAMAT_ERR_NOMEM : CUDAMAT_ERR_HIP;
-    }
-    return CUDAMAT_OK;
-}
-
+// everything sized by the partition (n_pad): released when the partition changes (cudamat_solver_set_comm)
 static void free_work(cudamat_solver *s)
 {
-    double **vs[] = {&s->r, &s->rw, &s->p, &s->pw, &s->s, &s->t, &s->v, &s->gather, &s->x0_save, &s->v2,
-                     &s->pz, &s->pww, &s->pq, &s->py, &s->pxh, &s->pipeA, &s->pipeB, &s->red_pipe,
-                     &s->prh, &s->pwh, &s->psh, &s->pzh, &s->pqh, &s->ptmp};
-    for (double **q : vs) {
-        if (*q) CM_DROP(hipFree(*q));
-        *q = nullptr;
-    }
+    DevBuf<double> *vs[] = {&s->r, &s->rw, &s->p, &s->pw, &s->s, &s->t, &s->v, &s->gather, &s->x0_save, &s->v2,
+                            &s->pz, &s->pww, &s->pq, &s->py, &s->pxh, &s->pipeA, &s->pipeB, &s->red_pipe,
+                            &s->prh, &s->pwh, &s->psh, &s->pzh, &s->pqh, &s->ptmp};
+    for (DevBuf<double> *q : vs) q->reset();
 }
 
 int ensure_work(cudamat_solver *s)
 {
     if (s->r) return CUDAMAT_OK;
     hipStream_t st = s->ctx->stream;
-    const size_t nb = sizeof(double) * (size_t)(s->n_pad > 0 ? s->n_pad : 1);
-    double **vs[] = {&s->r, &s->rw, &s->p, &s->pw, &s->s, &s->t, &s->v};
-    for (double **q : vs) {
-        CM_TRY(dev_alloc((void **)q, nb));
-        CM_HIP(hipMemsetAsync(*q, 0, nb, st));
+    const size_t count = (size_t)(s->n_pad > 0 ? s->n_pad : 1), nb = sizeof(double) * count;
+    DevBuf<double> *vs[] = {&s->r, &s->rw, &s->p, &s->pw, &s->s, &s->t, &s->v};
+    for (DevBuf<double> *q : vs) {
+        CM_TRY(q->alloc(count));
+        CM_HIP(hipMemsetAsync(q->get(), 0, nb, st));
     }
     if (s->ctx->cfg.verbose)
         fprintf(stderr, "[cudamat] work vectors: r %p rw %p p %p pw %p s %p t %p v %p (%zu bytes each)\n", (void *)s->r, (void *)s->rw, (void *)s->p,
                 (void *)s->pw, (void *)s->s, (void *)s->t, (void *)s->v, nb);
     if (s->sharded) {
-        CM_TRY(dev_alloc((void **)&s->gather, nb * (size_t)s->comm.world));
+        CM_TRY(s->gather.alloc(count * (size_t)s->comm.world));
         CM_HIP(hipMemsetAsync(s->gather, 0, nb * (size_t)s->comm.world, st));
     }
     return CUDAMAT_OK;
@@ -111,7 +99,7 @@ __global__ __launch_bounds__(kBlock) void k_check_columns(int n, long long n_col
 static int validate_csr(cudamat_solver *s)
 {
     hipStream_t st = s->ctx->stream;
-    int *d = (int *)s->ctx->scratch, h[3] = {0, 0, 0};
+    int *d = (int *)s->ctx->scratch.get(), h[3] = {0, 0, 0};
     hipError_t e = hipMemsetAsync(d, 0, sizeof(h), st);
     hipLaunchKernelGGL(k_check_rowptr, dim3((unsigned)(((long long)s->n + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, s->n,
                        (long long)s->nnz, s->rp, d);
@@ -144,7 +132,7 @@ int solver_alloc(cudamat_ctx *ctx, int n_local, int64_t n_cols, int64_t nnz, cud
     CM_ARG(n_local >= 0 && n_cols >= n_local && nnz >= 0, "sizes");
     CM_ARG(nnz < (1LL << 31) && n_cols < (1LL << 31), "local nnz and dimension must fit int32");
     CM_HIP(hipSetDevice(ctx->device));
-    cudamat_solver *s = new cudamat_solver();
+    std::unique_ptr<cudamat_solver> s(new cudamat_solver());
     s->ctx = ctx;
     s->n = n_local;
     s->n_pad = n_local;
@@ -152,31 +140,31 @@ int solver_alloc(cudamat_ctx *ctx, int n_local, int64_t n_cols, int64_t nnz, cud
     s->nnz = nnz;
     s->t_create0 = now_s();
     hipStream_t st = ctx->stream;
-    int rc = CUDAMAT_OK;
-    do {
-        if ((rc = dev_alloc((void **)&s->rp, sizeof(int) * ((size_t)n_local + 1)))) break;
-        if ((rc = dev_alloc((void **)&s->ci, sizeof(int) * (size_t)nnz))) break;
-        if ((rc = dev_alloc((void **)&s->val, sizeof(double) * (size_t)nnz))) break;
-        if ((rc = dev_alloc((void **)&s->parts_full, sizeof(double) * 2 * kMaxParts))) break;
-        if ((rc = dev_alloc((void **)&s->parts_rv, sizeof(double) * 2 * kMaxParts))) break;
-        if ((rc = dev_alloc((void **)&s->parts_half, sizeof(double) * 2 * kMaxParts))) break;
-        if ((rc = dev_alloc((void **)&s->parts_tt, sizeof(double) * 2 * kMaxParts))) break;
-        if ((rc = dev_alloc((void **)&s->red, sizeof(double) * 16))) break;
-        if ((rc = dev_alloc((void **)&s->st, sizeof(LoopState)))) break;
-        if (hipHostMalloc((void **)&s->st_ring, sizeof(LoopState) * kRing, hipHostMallocDefault) != hipSuccess) {
-            rc = CUDAMAT_ERR_HIP; set_error("hipHostMalloc failed"); break;
-        }
-        if (hipHostMalloc((void **)&s->snap_host, sizeof(unsigned long long) * kRing, hipHostMallocDefault) != hipSuccess ||
-            hipHostGetDevicePointer((void **)&s->snap_dev, s->snap_host, 0) != hipSuccess) {
-            rc = CUDAMAT_ERR_HIP; set_error("pinned progress words unavailable"); break;
-        }
-        if (hipMemsetAsync(s->st, 0, sizeof(LoopState), st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
-    } while (0);
-    if (rc) {
-        cudamat_solver_destroy(s);
-        return rc;
+    // (a failure below leaves through the solver's own destructor: nothing but memory is held yet)
+    CM_TRY(s->rp.alloc((size_t)n_local + 1));
+    CM_TRY(s->ci.alloc((size_t)nnz));
+    CM_TRY(s->val.alloc((size_t)nnz));
+    CM_TRY(s->parts_full.alloc(2 * kMaxParts));
+    CM_TRY(s->parts_rv.alloc(2 * kMaxParts));
+    CM_TRY(s->parts_half.alloc(2 * kMaxParts));
+    CM_TRY(s->parts_tt.alloc(2 * kMaxParts));
+    CM_TRY(s->red.alloc(16));
+    CM_TRY(s->st.alloc(1));
+    LoopState *ring = nullptr;
+    unsigned long long *snap = nullptr;
+    if (hipHostMalloc((void **)&ring, sizeof(LoopState) * kRing, hipHostMallocDefault) != hipSuccess) {
+        set_error("hipHostMalloc failed");
+        return CUDAMAT_ERR_HIP;
     }
-    *out = s;
+    s->st_ring.adopt(ring);
+    if (hipHostMalloc((void **)&snap, sizeof(unsigned long long) * kRing, hipHostMallocDefault) != hipSuccess) snap = nullptr;
+    s->snap_host.adopt(snap);
+    if (!snap || hipHostGetDevicePointer((void **)&s->snap_dev, snap, 0) != hipSuccess) {
+        set_error("pinned progress words unavailable");
+        return CUDAMAT_ERR_HIP;
+    }
+    if (hipMemsetAsync(s->st, 0, sizeof(LoopState), st) != hipSuccess) return CUDAMAT_ERR_HIP;
+    *out = s.release();
     return CUDAMAT_OK;
 }
 
@@ -256,26 +244,12 @@ extern "C" int cudamat_solver_destroy(cudamat_solver *s)
     if (!s) return CUDAMAT_OK;
     CM_DROP(hipSetDevice(s->ctx->device));
     CM_DROP(hipStreamSynchronize(s->ctx->stream));
-    ilu0_release(s);
+    ilu0_release(s);           // (the blocked copies it holds are PbPlans: freed by hand, like s->pb)
     pb_free(&s->pb);
-    sell_free(&s->sell);
-    pat_free(&s->pat);
-    free_work(s);
-    many_release(s);
-    plan_spmv_free(&s->plan);
-    void *ptrs[] = {s->rp, s->ci, s->val, s->parts_full, s->parts_rv, s->parts_half, s->parts_tt,
-                    s->red, s->st, s->hist};
-    for (void *p : ptrs)
-        if (p) CM_DROP(hipFree(p));
-    if (s->st_ring) CM_DROP(hipHostFree(s->st_ring));
-    if (s->snap_host) CM_DROP(hipHostFree(s->snap_host));
     for (int i = 0; i < kRing; i++)
         if (s->ev[i]) CM_DROP(hipEventDestroy(s->ev[i]));
     for (hipEvent_t e : s->prof_ev) CM_DROP(hipEventDestroy(e));
     for (hipEvent_t e : s->comm_ev) CM_DROP(hipEventDestroy(e));
-    if (s->need_dev) CM_DROP(hipFree(s->need_dev));
-    if (s->bar) CM_DROP(hipFree(s->bar));
-    valdict_free(&s->vd);
     for (int e = 0; e < 2; e++) {
         if (s->ev_red[e]) CM_DROP(hipEventDestroy(s->ev_red[e]));
         if (s->ev_red_done[e]) CM_DROP(hipEventDestroy(s->ev_red_done[e]));
@@ -287,7 +261,7 @@ extern "C" int cudamat_solver_destroy(cudamat_solver *s)
         if (e) CM_DROP(hipEventDestroy(e));
     for (hipStream_t q : s->part_stream)
         if (q) { CM_DROP(hipStreamSynchronize(q)); CM_DROP(hipStreamDestroy(q)); }
-    delete s;
+    delete s;                  // every buffer is released by its owner
     return CUDAMAT_OK;
 }
 
@@ -312,7 +286,7 @@ extern "C" int cudamat_solver_set_comm(cudamat_solver *s, const cudamat_comm *co
     s->agreed = false;
     s->windowed = false;
     s->windows_known = false;
-    if (s->need_dev) { CM_DROP(hipFree(s->need_dev)); s->need_dev = nullptr; }
+    s->need_dev.reset();
     const bool forced = comm && comm->world == 1 && s->ctx->cfg.force_sharded;
     if (!comm || (comm->world <= 1 && !forced)) {
         s->sharded = false;
@@ -334,7 +308,7 @@ extern "C" int cudamat_solver_set_comm(cudamat_solver *s, const cudamat_comm *co
     s->sharded = true;
     s->n_pad = (int)per;
     if (comm->gather_window && comm->world > 1 && comm->world <= 4096)      // compute_windows' exchange buffer: allocated
-        CM_TRY(dev_alloc((void **)&s->need_dev, sizeof(double) * ((size_t)2 * comm->world + (size_t)2 * comm->world * comm->world)));  // here, where a failure is still rank-local
+        CM_TRY(s->need_dev.alloc((size_t)2 * comm->world + (size_t)2 * comm->world * comm->world));  // here, where a failure is still rank-local
     if (comm->gather_part && comm->comm_stream && !s->ev_x) {
         CM_HIP(hipEventCreateWithFlags(&s->ev_x, hipEventDisableTiming));
         for (int c = 0; c < kPbMaxChunks; c++) {
@@ -502,7 +476,7 @@ static int col_span_bytes(cudamat_solver *s, double *out)
 {
     *out = 0.0;
     hipStream_t st = s->ctx->stream;
-    unsigned long long *d = (unsigned long long *)s->ctx->scratch, h[2] = {0ULL, 0ULL};
+    unsigned long long *d = (unsigned long long *)s->ctx->scratch.get(), h[2] = {0ULL, 0ULL};
     CM_HIP(hipMemsetAsync(d, 0, sizeof(h), st));
     const int samples = s->n < 4096 ? s->n : 4096;
     hipLaunchKernelGGL(k_col_span, dim3((samples + kBlock - 1) / kBlock), dim3(kBlock), 0, st, s->n, s->rp, s->ci, samples, d, (int *)(d + 1));
@@ -764,8 +738,8 @@ static int compute_windows(cudamat_solver *s)
     std::vector<double> mine((size_t)2 * W, 0.0), all((size_t)2 * W * W, 0.0);
     char saved[512] = "";
     auto local = [&]() -> int {
-        int *d_lohi = nullptr;
-        CM_HIP(hipMalloc((void **)&d_lohi, sizeof(int) * 2 * (size_t)W));
+        DevBuf<int> d_lohi;
+        CM_TRY(d_lohi.alloc(2 * (size_t)W));
         for (int q = 0; q < W; q++) { h[(size_t)q] = per; h[(size_t)W + q] = 0; }
         hipError_t e = hipMemcpyAsync(d_lohi, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st);
         if (e == hipSuccess && s->nnz > 0) {
@@ -774,7 +748,6 @@ static int compute_windows(cudamat_solver *s)
         }
         if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_lohi, sizeof(int) * h.size(), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        CM_DROP(hipFree(d_lohi));
         CM_HIP(e);
         for (int q = 0; q < W; q++)
             if (q != me && h[(size_t)W + q] > h[(size_t)q]) { mine[(size_t)2 * q] = h[(size_t)q]; mine[(size_t)2 * q + 1] = h[(size_t)W + q]; }

@@ -243,31 +243,24 @@ int plan_spmv_compress(hipStream_t s, const Config &cfg, int n_rows, int64_t nnz
     if (!plan->stream_rows || nnz <= 0 || !cfg.spmv_compress) return CUDAMAT_OK;
     const int R = plan->stream_rows;
     const size_t ntiles = ((size_t)n_rows + R - 1) / R;
-    int *flags = nullptr, h = 0;
-    int rc = CUDAMAT_OK;
+    DevBuf<int> flags;
+    int h = 0, rc = CUDAMAT_OK;
     do {
-        if (hipMalloc((void **)&plan->c_off16, sizeof(short) * (size_t)nnz) != hipSuccess ||
-            hipMalloc((void **)&plan->c_len8, (size_t)n_rows) != hipSuccess ||
-            hipMalloc((void **)&plan->c_tile_base, sizeof(int) * (ntiles + 1)) != hipSuccess ||
-            hipMalloc((void **)&flags, sizeof(int)) != hipSuccess) { rc = CUDAMAT_ERR_NOMEM; break; }
+        if ((rc = plan->c_off16.alloc((size_t)nnz)) || (rc = plan->c_len8.alloc((size_t)n_rows)) ||
+            (rc = plan->c_tile_base.alloc(ntiles + 1)) || (rc = flags.alloc(1))) break;
         if ((rc = CM_RC(hipMemsetAsync(flags, 0, sizeof(int), s)))) break;
         const long long threads = ((long long)n_rows + 1) * 8;
         hipLaunchKernelGGL(k_stream_compress, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, n_rows, R,
                            rp, ci, plan->c_off16, plan->c_len8, plan->c_tile_base, flags);
         if (hipMemcpyAsync(&h, flags, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
+            hipStreamSynchronize(s) != hipSuccess) rc = fail_hip(hipGetLastError(), "index compression", __FILE__, __LINE__);
     } while (0);
-    if (flags) CM_DROP(hipFree(flags));
     if (rc || h) {                                    // does not fit (or no memory): the plain stream kernel stays
-        void *ptrs[] = {plan->c_off16, plan->c_len8, plan->c_tile_base};
-        for (void *q : ptrs)
-            if (q) CM_DROP(hipFree(q));
-        plan->c_off16 = nullptr;
-        plan->c_len8 = nullptr;
-        plan->c_tile_base = nullptr;
-        if (rc == CUDAMAT_ERR_HIP) return fail_hip(hipGetLastError(), "index compression", __FILE__, __LINE__);
+        plan->c_off16.reset();
+        plan->c_len8.reset();
+        plan->c_tile_base.reset();
     }
-    return CUDAMAT_OK;
+    return rc == CUDAMAT_ERR_NOMEM ? CUDAMAT_OK : rc;
 }
 
 // ---- padded per-tile copies for the dictionary form
@@ -339,30 +332,26 @@ int plan_spmv_align(hipStream_t s, const Config &cfg, int n_rows, int64_t nnz, c
     if (nnz + 63LL * ntiles > 0x7fffffffLL) return CUDAMAT_OK;
     int total = 0, rc = CUDAMAT_OK;
     do {
-        if (hipMalloc((void **)&plan->a_base, sizeof(int) * ((size_t)ntiles + 1)) != hipSuccess) { rc = CUDAMAT_ERR_NOMEM; break; }
+        if ((rc = plan->a_base.alloc((size_t)ntiles + 1))) break;
         hipLaunchKernelGGL(k_tile_pad_scan, dim3(1), dim3(kBlock), 0, s, n_rows, R, ntiles, rp, plan->a_base, 64);
         if (hipMemcpyAsync(&total, plan->a_base + ntiles, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
-        if (total < nnz || (int64_t)total > nnz + 64LL * ntiles) { rc = CUDAMAT_ERR_HIP; break; }
-        if (hipMalloc((void **)&plan->a_off16, sizeof(short) * (size_t)total + 256) != hipSuccess ||
-            hipMalloc((void **)&plan->a_val, sizeof(double) * (size_t)total + 256) != hipSuccess) { rc = CUDAMAT_ERR_NOMEM; break; }
+            hipStreamSynchronize(s) != hipSuccess) { rc = fail_hip(hipGetLastError(), "aligned stream copies", __FILE__, __LINE__); break; }
+        if (total < nnz || (int64_t)total > nnz + 64LL * ntiles) { rc = fail_hip(hipGetLastError(), "aligned stream copies", __FILE__, __LINE__); break; }
+        // (256 bytes past the last tile each)
+        if ((rc = plan->a_off16.alloc((size_t)total + 128)) || (rc = plan->a_val.alloc((size_t)total + 32))) break;
         if ((rc = CM_RC(hipMemsetAsync(plan->a_off16, 0, sizeof(short) * (size_t)total + 256, s)))) break;      // idle slots: offset 0, value 0
         if ((rc = CM_RC(hipMemsetAsync(plan->a_val, 0, sizeof(double) * (size_t)total + 256, s)))) break;
         const long long threads = (long long)n_rows * 8;
         hipLaunchKernelGGL(k_tile_align_fill, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, n_rows, R, rp,
                            plan->c_off16, val, plan->a_base, plan->a_off16, plan->a_val);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = fail_hip(hipGetLastError(), "aligned stream copies", __FILE__, __LINE__); break; }
     } while (0);
     if (rc) {                                         // no memory / failure: the packed arrays stay
-        void *ptrs[] = {plan->a_base, plan->a_off16, plan->a_val};
-        for (void *q : ptrs)
-            if (q) CM_DROP(hipFree(q));
-        plan->a_base = nullptr;
-        plan->a_off16 = nullptr;
-        plan->a_val = nullptr;
-        if (rc == CUDAMAT_ERR_HIP) return fail_hip(hipGetLastError(), "aligned stream copies", __FILE__, __LINE__);
+        plan->a_base.reset();
+        plan->a_off16.reset();
+        plan->a_val.reset();
     }
-    return CUDAMAT_OK;
+    return rc == CUDAMAT_ERR_NOMEM ? CUDAMAT_OK : rc;
 }
 
 int plan_spmv_dict(hipStream_t s, int n_rows, int64_t nnz, const int *rp, const unsigned char *vidx, const double *dict,
@@ -373,32 +362,28 @@ int plan_spmv_dict(hipStream_t s, int n_rows, int64_t nnz, const int *rp, const 
     const int ntiles = (int)(((long long)n_rows + R - 1) / R);
     int total = 0, rc = CUDAMAT_OK;
     do {
-        if (hipMalloc((void **)&plan->d_pbase, sizeof(int) * ((size_t)ntiles + 1)) != hipSuccess) { rc = CUDAMAT_ERR_NOMEM; break; }
+        if ((rc = plan->d_pbase.alloc((size_t)ntiles + 1))) break;
         hipLaunchKernelGGL(k_tile_pad_scan, dim3(1), dim3(kBlock), 0, s, n_rows, R, ntiles, rp, plan->d_pbase, 8);
         if (hipMemcpyAsync(&total, plan->d_pbase + ntiles, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
-        if (total < nnz || (int64_t)total > nnz + 8LL * ntiles) { rc = CUDAMAT_ERR_HIP; break; }
-        if (hipMalloc((void **)&plan->d_off16, sizeof(short) * (size_t)total + 16) != hipSuccess ||
-            hipMalloc((void **)&plan->d_val8, (size_t)total + 16) != hipSuccess) { rc = CUDAMAT_ERR_NOMEM; break; }
+            hipStreamSynchronize(s) != hipSuccess) { rc = fail_hip(hipGetLastError(), "dictionary tiles", __FILE__, __LINE__); break; }
+        if (total < nnz || (int64_t)total > nnz + 8LL * ntiles) { rc = fail_hip(hipGetLastError(), "dictionary tiles", __FILE__, __LINE__); break; }
+        // (16 bytes past the last tile each)
+        if ((rc = plan->d_off16.alloc((size_t)total + 8)) || (rc = plan->d_val8.alloc((size_t)total + 16))) break;
         if ((rc = CM_RC(hipMemsetAsync(plan->d_off16, 0, sizeof(short) * (size_t)total + 16, s)))) break;      // padding: offset 0, value index 0
         if ((rc = CM_RC(hipMemsetAsync(plan->d_val8, 0, (size_t)total + 16, s)))) break;
         const long long threads = (long long)n_rows * 8;
         hipLaunchKernelGGL(k_tile_pad_fill, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, n_rows, R, rp,
                            plan->c_off16, vidx, plan->d_pbase, plan->d_off16, plan->d_val8);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = fail_hip(hipGetLastError(), "dictionary tiles", __FILE__, __LINE__); break; }
         plan->c_dict = dict;
     } while (0);
     if (rc) {                                         // no memory / failure: the plain compressed kernel stays
-        void *ptrs[] = {plan->d_pbase, plan->d_off16, plan->d_val8};
-        for (void *q : ptrs)
-            if (q) CM_DROP(hipFree(q));
-        plan->d_pbase = nullptr;
-        plan->d_off16 = nullptr;
-        plan->d_val8 = nullptr;
+        plan->d_pbase.reset();
+        plan->d_off16.reset();
+        plan->d_val8.reset();
         plan->c_dict = nullptr;
-        if (rc == CUDAMAT_ERR_HIP) return fail_hip(hipGetLastError(), "dictionary tiles", __FILE__, __LINE__);
     }
-    return CUDAMAT_OK;
+    return rc == CUDAMAT_ERR_NOMEM ? CUDAMAT_OK : rc;
 }
 
 // ------------------------------------------------------------ SpMV, skewed row lengths
@@ -592,38 +577,16 @@ __global__ __launch_bounds__(kBlock) void k_lane_cost(int n, const int *rp, int 
     if ((threadIdx.x & 63) == 0 && it) atomicAdd(out, it);
 }
 
-void plan_spmv_free(SpmvPlan *plan)
-{
-    void *ptrs[] = {plan->tile_S, plan->tile_span, plan->tile_heads, plan->tile_tails, plan->c_off16, plan->c_len8,
-                    plan->c_tile_base, plan->d_pbase, plan->d_off16, plan->d_val8, plan->a_base, plan->a_off16, plan->a_val};
-    plan->a_base = nullptr;
-    plan->a_off16 = nullptr;
-    plan->a_val = nullptr;
-    plan->d_pbase = nullptr;
-    plan->d_off16 = nullptr;
-    plan->d_val8 = nullptr;
-    for (void *q : ptrs)
-        if (q) CM_DROP(hipFree(q));
-    plan->c_off16 = nullptr;
-    plan->c_len8 = nullptr;
-    plan->c_tile_base = nullptr;
-    plan->tile_S = plan->tile_span = nullptr;
-    plan->tile_heads = plan->tile_tails = nullptr;
-    plan->tiles = 0;
-}
-
 static int plan_spmv_tiles(hipStream_t s, int n_rows, int64_t nnz, const int *rp, SpmvPlan *plan)
 {
     const int64_t nt64 = (nnz + kTileNnz - 1) / kTileNnz;
     if (nt64 < 1 || nt64 > (1 << 24)) return CUDAMAT_OK;                 // keep the lanes-per-row plan
     const int ntiles = (int)nt64;
-    int *flag = nullptr;
+    DevBuf<int> flag;
     int rc = CUDAMAT_OK;
     do {
-        if (hipMalloc((void **)&plan->tile_S, sizeof(int) * ((size_t)ntiles + 1)) != hipSuccess ||
-            hipMalloc((void **)&plan->tile_heads, sizeof(double) * (size_t)ntiles) != hipSuccess ||
-            hipMalloc((void **)&plan->tile_tails, sizeof(double) * (size_t)ntiles) != hipSuccess ||
-            hipMalloc((void **)&flag, sizeof(int) * (size_t)ntiles) != hipSuccess) { rc = CUDAMAT_ERR_NOMEM; break; }
+        if ((rc = plan->tile_S.alloc((size_t)ntiles + 1)) || (rc = plan->tile_heads.alloc((size_t)ntiles)) ||
+            (rc = plan->tile_tails.alloc((size_t)ntiles)) || (rc = flag.alloc((size_t)ntiles))) break;
         if ((rc = CM_RC(hipMemsetAsync(plan->tile_heads, 0, sizeof(double) * (size_t)ntiles, s)))) break;
         if ((rc = CM_RC(hipMemsetAsync(plan->tile_tails, 0, sizeof(double) * (size_t)ntiles, s)))) break;
         hipLaunchKernelGGL(k_tiles_rows, dim3((unsigned)((ntiles + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, n_rows, rp,
@@ -632,15 +595,13 @@ static int plan_spmv_tiles(hipStream_t s, int n_rows, int64_t nnz, const int *rp
                            ntiles, plan->tile_S, flag);
         std::vector<int> h((size_t)ntiles), span;
         if (hipMemcpyAsync(h.data(), flag, sizeof(int) * (size_t)ntiles, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
+            hipStreamSynchronize(s) != hipSuccess) { rc = fail_hip(hipGetLastError(), "tile plan", __FILE__, __LINE__); break; }
         for (int t = 0; t < ntiles; t++)
             if (h[(size_t)t]) span.push_back(t);
         plan->tile_nspan = (int)span.size();
         if (!span.empty()) {
-            if (hipMalloc((void **)&plan->tile_span, sizeof(int) * span.size()) != hipSuccess) { rc = CUDAMAT_ERR_NOMEM; break; }
-            if (hipMemcpy(plan->tile_span, span.data(), sizeof(int) * span.size(), hipMemcpyHostToDevice) != hipSuccess) {
-                rc = CUDAMAT_ERR_HIP; break;
-            }
+            if ((rc = plan->tile_span.alloc(span.size()))) break;
+            if ((rc = CM_RC(hipMemcpy(plan->tile_span, span.data(), sizeof(int) * span.size(), hipMemcpyHostToDevice)))) break;
         }
         const int fix_grid = span.empty() ? 0 : (int)std::min<size_t>(64, (span.size() + 3) / 4);
         const int main_max = kSpmvGridMax - 64;
@@ -652,13 +613,13 @@ static int plan_spmv_tiles(hipStream_t s, int n_rows, int64_t nnz, const int *rp
         plan->grid = grid;
         plan->tile_fix_grid = fix_grid;
     } while (0);
-    if (flag) CM_DROP(hipFree(flag));
     if (rc) {
-        plan_spmv_free(plan);
-        if (rc == CUDAMAT_ERR_NOMEM) return CUDAMAT_OK;                  // no room for the tables: lanes-per-row plan stays
-        return fail_hip(hipGetLastError(), "tile plan", __FILE__, __LINE__);
+        plan->tile_S.reset();
+        plan->tile_span.reset();
+        plan->tile_heads.reset();
+        plan->tile_tails.reset();
     }
-    return CUDAMAT_OK;
+    return rc == CUDAMAT_ERR_NOMEM ? CUDAMAT_OK : rc;                    // no room for the tables: lanes-per-row plan stays
 }
 
 // max over tiles of R rows of the number of entries in the tile, for R = 64, 128, 256
@@ -682,8 +643,9 @@ static int plan_spmv_balance(hipStream_t s, const Config &cfg, int n_rows, int64
     if (nnz <= 0 || n_rows <= 0) return CUDAMAT_OK;
     if (!force) {
         if (nnz < 65536) return CUDAMAT_OK;
-        unsigned long long *d = (unsigned long long *)scratch, h = 0;
-        if (!scratch) CM_HIP(hipMalloc((void **)&d, sizeof(h)));
+        DevBuf<unsigned long long> own;
+        if (!scratch) CM_TRY(own.alloc(1));
+        unsigned long long *d = scratch ? (unsigned long long *)scratch : own.get(), h = 0;
         hipError_t e = hipMemsetAsync(d, 0, sizeof(h), s);
         const long long groups = ((long long)n_rows + (64 / plan->lanes) - 1) / (64 / plan->lanes);
         hipLaunchKernelGGL(k_lane_cost, dim3((unsigned)((groups + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, n_rows, rp,
@@ -691,7 +653,6 @@ static int plan_spmv_balance(hipStream_t s, const Config &cfg, int n_rows, int64
         if (e == hipSuccess) e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (!scratch) CM_DROP(hipFree(d));
         if (e != hipSuccess) return fail_hip(e, "lane cost", __FILE__, __LINE__);
         plan->lane_cost = (double)h * 64.0 / (double)nnz;
         // measured (scripts/skew_probe.py): at 2.0 (rows of 2 and 62 alternating) the lanes kernel is still memory-bound
@@ -709,15 +670,15 @@ int plan_spmv_refine(hipStream_t s, const Config &cfg, int n_rows, int64_t nnz, 
     const double mean = n_rows > 0 ? (double)nnz / n_rows : 0.0;
     if (n_rows < 64) return CUDAMAT_OK;
     if (mean > 12.0) return plan_spmv_balance(s, cfg, n_rows, nnz, rp, plan, scratch);
-    int *d = (int *)scratch, h[3] = {0, 0, 0};
-    if (!scratch) CM_HIP(hipMalloc((void **)&d, 3 * sizeof(int)));
+    DevBuf<int> own;
+    if (!scratch) CM_TRY(own.alloc(3));
+    int *d = scratch ? (int *)scratch : own.get(), h[3] = {0, 0, 0};
     hipError_t e = hipMemsetAsync(d, 0, 3 * sizeof(int), s);
     const long long tiles = ((long long)n_rows + 63) / 64;
     hipLaunchKernelGGL(k_tile_nnz_max, dim3((unsigned)((tiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, n_rows, rp, d);
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (!scratch) CM_DROP(hipFree(d));
     if (e != hipSuccess) return fail_hip(e, "tile scan", __FILE__, __LINE__);
     int R = 0;
     if (h[2] <= kStreamNnz) R = 256;

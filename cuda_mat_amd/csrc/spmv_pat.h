@@ -16,15 +16,15 @@ struct PatPlan {
     int nchunks = 0;                 // chunks of 64 rows (the last one padded with empty rows)
     double fill = 1.0;               // stored value slots / nnz
     int grid = 0, tiles_per_block = 0;
-    double *val = nullptr;           // [nchunks][W][64]: slot-major inside a chunk (NULL when the copy holds dictionary indices)
+    DevBuf<double> val;              // [nchunks][W][64]: slot-major inside a chunk (NULL when the copy holds dictionary indices)
     // value-dictionary form (the matrix has <= 256 distinct values, valdict.h): per row ONE word of 8 (W <= 8) or 16 bytes
     // holding the 8-bit dictionary indices of its entries in column order -- 8 or 16 B per row instead of 8 B per entry
-    unsigned char *vidx = nullptr;   // [nchunks * 64][vword]
+    DevBuf<unsigned char> vidx;      // [nchunks * 64][vword]
     int vword = 0;                   // 8 or 16
     const double *dict = nullptr;    // the dictionary (owned by the ValDict it came from)
     int ndict = 0;
-    unsigned char *pid = nullptr;    // [nchunks * 64]: pattern of every row
-    int *tab = nullptr;              // [kPatMax][16]: length, then the column offsets (column - row) in column order
+    DevBuf<unsigned char> pid;       // [nchunks * 64]: pattern of every row
+    DevBuf<int> tab;                 // [kPatMax][16]: length, then the column offsets (column - row) in column order
     double build_seconds = 0.0;
 };
 

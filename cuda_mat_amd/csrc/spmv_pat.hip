@@ -24,6 +24,7 @@
 // row with its table entry -- a hash collision or a row the table cannot describe makes the builder give up, it never
 // produces a wrong copy.  Chosen per matrix by timing it against the other forms (solver.hip, ensure_spmv_mode).
 #include <algorithm>
+#include <utility>
 #include <vector>
 
 #include "device.h"
@@ -36,25 +37,7 @@ constexpr int kPatSlots = 4096;                                  // hash table s
 constexpr unsigned long long kPatEmpty = 0xFFFFFFFFFFFFFFFFull;
 constexpr int kPatRow = kPatMaxLen + 1;                          // ints per table row
 
-template <typename T>
-static int dalloc(T **p, size_t count)
-{
-    *p = nullptr;
-    hipError_t e = hipMalloc((void **)p, sizeof(T) * (count ? count : 1));
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%zu bytes) failed: %s", sizeof(T) * count, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? CUDAMAT_ERR_NOMEM : CUDAMAT_ERR_HIP;
-    }
-    return CUDAMAT_OK;
-}
-
-void pat_free(PatPlan *p)
-{
-    void *ptrs[] = {p->val, p->vidx, p->pid, p->tab};
-    for (void *q : ptrs)
-        if (q) CM_DROP(hipFree(q));
-    *p = PatPlan();
-}
+void pat_free(PatPlan *p) { *p = PatPlan(); }
 
 __device__ __forceinline__ unsigned long long pat_mix(unsigned long long h, unsigned long long v)
 {
@@ -183,93 +166,81 @@ int pat_build(hipStream_t st, int n, int64_t nnz, const int *rp, const int *ci, 
     p.nnz = nnz;
     p.nchunks = (n + kPatChunk - 1) / kPatChunk;
     const long long padded = (long long)p.nchunks * kPatChunk;
-    unsigned long long *table = nullptr, *keys_dev = nullptr;
-    int *rep = nullptr, *flags = nullptr, *reps_dev = nullptr;
-    int rc = CUDAMAT_OK;
-    do {
-        if (n <= 0 || nnz <= 0) { rc = CUDAMAT_ERR_ARG; set_error("pat_build: empty matrix"); break; }
-        if ((rc = dalloc(&table, (size_t)kPatSlots))) break;
-        if ((rc = dalloc(&rep, (size_t)kPatSlots))) break;
-        if ((rc = dalloc(&flags, 2))) break;
-        if ((rc = CM_RC(hipMemsetAsync(table, 0xFF, sizeof(unsigned long long) * kPatSlots, st)))) break;
-        if ((rc = CM_RC(hipMemsetAsync(rep, 0x7F, sizeof(int) * kPatSlots, st)))) break;
-        if ((rc = CM_RC(hipMemsetAsync(flags, 0, 2 * sizeof(int), st)))) break;
-        int grid = (int)(((long long)n + kBlock - 1) / kBlock);
-        if (grid > 8192) grid = 8192;
-        hipLaunchKernelGGL(k_pat_probe, dim3(grid), dim3(kBlock), 0, st, n, rp, ci, table, rep, flags);
-        int h[2] = {0, 0};
-        std::vector<unsigned long long> hk((size_t)kPatSlots);
-        std::vector<int> hr((size_t)kPatSlots);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipMemcpyAsync(hk.data(), table, sizeof(unsigned long long) * kPatSlots, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipMemcpyAsync(hr.data(), rep, sizeof(int) * kPatSlots, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("pattern probe failed"); break; }
-        if (h[1] || h[0] < 1 || h[0] > kPatMax - 1) {
-            rc = CUDAMAT_ERR_ARG;
-            set_error("pat_build: rows longer than %d entries or more than %d distinct row patterns", kPatMaxLen, kPatMax - 1);
-            break;
-        }
-        // distinct patterns sorted by key (deterministic ids) + the empty pattern for the padding rows of the last chunk
-        std::vector<std::pair<unsigned long long, int>> pats;
-        for (int i = 0; i < kPatSlots; i++)
-            if (hk[(size_t)i] != kPatEmpty) pats.push_back({hk[(size_t)i], hr[(size_t)i]});
-        if ((int)pats.size() != h[0]) { rc = CUDAMAT_ERR_HIP; set_error("pat_build: table count mismatch"); break; }
-        std::sort(pats.begin(), pats.end());
-        std::vector<unsigned long long> keys;
-        std::vector<int> reps;
-        for (auto &q : pats) { keys.push_back(q.first); reps.push_back(q.second); }
-        p.npat = (int)keys.size();
-        if ((rc = dalloc(&keys_dev, (size_t)kPatMax))) break;
-        if ((rc = dalloc(&reps_dev, (size_t)kPatMax))) break;
-        if ((rc = dalloc(&p.tab, (size_t)kPatMax * kPatRow))) break;
-        if (hipMemcpyAsync(keys_dev, keys.data(), sizeof(unsigned long long) * keys.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(reps_dev, reps.data(), sizeof(int) * reps.size(), hipMemcpyHostToDevice, st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
-        hipLaunchKernelGGL(k_pat_extract, dim3(1), dim3(kBlock), 0, st, p.npat, reps_dev, rp, ci, p.tab);
-        std::vector<int> htab((size_t)kPatMax * kPatRow);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(htab.data(), p.tab, sizeof(int) * htab.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("pattern table failed"); break; }
-        // the id the padding rows take: a pattern of length 0 (present already when the matrix has empty rows, else the
-        // first unused table row, which k_pat_extract left all zero)
-        int empty_id = -1;
-        for (int i = 0; i < p.npat; i++) {
-            if (htab[(size_t)i * kPatRow] == 0) empty_id = i;
-            p.W = std::max(p.W, htab[(size_t)i * kPatRow]);
-        }
-        if (empty_id < 0) empty_id = p.npat;             // (< kPatMax: at most kPatMax - 1 patterns came from the matrix)
-        p.fill = (double)padded * p.W / (double)nnz;
-        if (p.W < 1 || (max_fill > 0.0 && p.fill > max_fill)) {
-            rc = CUDAMAT_ERR_ARG;
-            set_error("pat_build: padded copy would hold %.2f x the entries", p.fill);
-            break;
-        }
-        if ((rc = dalloc(&p.pid, (size_t)padded))) break;
-        if ((rc = CM_RC(hipMemsetAsync(flags, 0, 2 * sizeof(int), st)))) break;
-        hipLaunchKernelGGL(k_pat_assign, dim3(grid), dim3(kBlock), 0, st, n, (int)padded, p.npat, empty_id, rp, ci, keys_dev, p.tab, p.pid, flags);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("pattern assignment failed"); break; }
-        if (h[0]) { rc = CUDAMAT_ERR_ARG; set_error("pat_build: two row patterns share a hash key; this matrix keeps its indices"); break; }
-        if (vd && vd->n > 0) {
-            p.vword = p.W <= 8 ? 8 : 16;
-            p.dict = vd->dict;
-            p.ndict = vd->n;
-            if ((rc = dalloc(&p.vidx, (size_t)padded * p.vword))) break;
-            hipLaunchKernelGGL(k_pat_fill_idx, dim3((unsigned)((padded + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, n, padded, p.vword, rp, vd->idx, p.vidx);
-        } else {
-            if ((rc = dalloc(&p.val, (size_t)padded * p.W))) break;
-            hipLaunchKernelGGL(k_pat_fill, dim3((unsigned)((padded + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, n, p.nchunks, p.W, rp, val, p.val);
-        }
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("pattern fill failed"); break; }
-    } while (0);
-    void *tmp[] = {table, rep, flags, keys_dev, reps_dev};
-    for (void *q : tmp)
-        if (q) CM_DROP(hipFree(q));
-    if (rc) {
-        pat_free(&p);
-        return rc;
+    DevBuf<unsigned long long> table, keys_dev;
+    DevBuf<int> rep, flags, reps_dev;
+    if (n <= 0 || nnz <= 0) { set_error("pat_build: empty matrix"); return CUDAMAT_ERR_ARG; }
+    CM_TRY(table.alloc((size_t)kPatSlots));
+    CM_TRY(rep.alloc((size_t)kPatSlots));
+    CM_TRY(flags.alloc(2));
+    CM_HIP(hipMemsetAsync(table, 0xFF, sizeof(unsigned long long) * kPatSlots, st));
+    CM_HIP(hipMemsetAsync(rep, 0x7F, sizeof(int) * kPatSlots, st));
+    CM_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int), st));
+    int grid = (int)(((long long)n + kBlock - 1) / kBlock);
+    if (grid > 8192) grid = 8192;
+    hipLaunchKernelGGL(k_pat_probe, dim3(grid), dim3(kBlock), 0, st, n, rp, ci, table, rep, flags);
+    int h[2] = {0, 0};
+    std::vector<unsigned long long> hk((size_t)kPatSlots);
+    std::vector<int> hr((size_t)kPatSlots);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(hk.data(), table, sizeof(unsigned long long) * kPatSlots, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(hr.data(), rep, sizeof(int) * kPatSlots, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) { set_error("pattern probe failed"); return CUDAMAT_ERR_HIP; }
+    if (h[1] || h[0] < 1 || h[0] > kPatMax - 1) {
+        set_error("pat_build: rows longer than %d entries or more than %d distinct row patterns", kPatMaxLen, kPatMax - 1);
+        return CUDAMAT_ERR_ARG;
     }
+    // distinct patterns sorted by key (deterministic ids) + the empty pattern for the padding rows of the last chunk
+    std::vector<std::pair<unsigned long long, int>> pats;
+    for (int i = 0; i < kPatSlots; i++)
+        if (hk[(size_t)i] != kPatEmpty) pats.push_back({hk[(size_t)i], hr[(size_t)i]});
+    if ((int)pats.size() != h[0]) { set_error("pat_build: table count mismatch"); return CUDAMAT_ERR_HIP; }
+    std::sort(pats.begin(), pats.end());
+    std::vector<unsigned long long> keys;
+    std::vector<int> reps;
+    for (auto &q : pats) { keys.push_back(q.first); reps.push_back(q.second); }
+    p.npat = (int)keys.size();
+    CM_TRY(keys_dev.alloc((size_t)kPatMax));
+    CM_TRY(reps_dev.alloc((size_t)kPatMax));
+    CM_TRY(p.tab.alloc((size_t)kPatMax * kPatRow));
+    if (hipMemcpyAsync(keys_dev, keys.data(), sizeof(unsigned long long) * keys.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(reps_dev, reps.data(), sizeof(int) * reps.size(), hipMemcpyHostToDevice, st) != hipSuccess) return CUDAMAT_ERR_HIP;
+    hipLaunchKernelGGL(k_pat_extract, dim3(1), dim3(kBlock), 0, st, p.npat, reps_dev, rp, ci, p.tab);
+    std::vector<int> htab((size_t)kPatMax * kPatRow);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(htab.data(), p.tab, sizeof(int) * htab.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) { set_error("pattern table failed"); return CUDAMAT_ERR_HIP; }
+    // the id the padding rows take: a pattern of length 0 (present already when the matrix has empty rows, else the
+    // first unused table row, which k_pat_extract left all zero)
+    int empty_id = -1;
+    for (int i = 0; i < p.npat; i++) {
+        if (htab[(size_t)i * kPatRow] == 0) empty_id = i;
+        p.W = std::max(p.W, htab[(size_t)i * kPatRow]);
+    }
+    if (empty_id < 0) empty_id = p.npat;             // (< kPatMax: at most kPatMax - 1 patterns came from the matrix)
+    p.fill = (double)padded * p.W / (double)nnz;
+    if (p.W < 1 || (max_fill > 0.0 && p.fill > max_fill)) {
+        set_error("pat_build: padded copy would hold %.2f x the entries", p.fill);
+        return CUDAMAT_ERR_ARG;
+    }
+    CM_TRY(p.pid.alloc((size_t)padded));
+    CM_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int), st));
+    hipLaunchKernelGGL(k_pat_assign, dim3(grid), dim3(kBlock), 0, st, n, (int)padded, p.npat, empty_id, rp, ci, keys_dev, p.tab, p.pid, flags);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) { set_error("pattern assignment failed"); return CUDAMAT_ERR_HIP; }
+    if (h[0]) { set_error("pat_build: two row patterns share a hash key; this matrix keeps its indices"); return CUDAMAT_ERR_ARG; }
+    if (vd && vd->n > 0) {
+        p.vword = p.W <= 8 ? 8 : 16;
+        p.dict = vd->dict;
+        p.ndict = vd->n;
+        CM_TRY(p.vidx.alloc((size_t)padded * p.vword));
+        hipLaunchKernelGGL(k_pat_fill_idx, dim3((unsigned)((padded + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, n, padded, p.vword, rp, vd->idx, p.vidx);
+    } else {
+        CM_TRY(p.val.alloc((size_t)padded * p.W));
+        hipLaunchKernelGGL(k_pat_fill, dim3((unsigned)((padded + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, n, p.nchunks, p.W, rp, val, p.val);
+    }
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { set_error("pattern fill failed"); return CUDAMAT_ERR_HIP; }
     // a workgroup takes tiles of 4 chunks (256 rows); tiles_per_block so that the grid stays within kSpmvGridMax and is a
     // multiple of 8 (the XCD-aware dealing: device.h, xcd_tile)
     const long long tiles = ((long long)p.nchunks + 3) / 4;
@@ -281,7 +252,7 @@ int pat_build(hipStream_t st, int n, int64_t nnz, const int *rp, const int *ci, 
     p.grid = (int)g;
     p.tiles_per_block = (int)((tiles + g - 1) / g);
     p.build_seconds = now_s() - t0;
-    *out = p;
+    *out = std::move(p);
     return CUDAMAT_OK;
 }
 

@@ -25,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "device.h"
 #include "spmv_pb.h"
 
 namespace cm {
@@ -39,18 +40,6 @@ constexpr int kTileMax = 13312;        // doubles per y tile of a row block / x 
 constexpr int kPbAlign = 64;           // every column block's entries start on a 64-entry boundary: the 1 KB product stores, the 1 KB value
                                        // loads and the 256-byte column loads of a phase-1 wave then cover whole 128-byte lines (<= 63 idle
                                        // slots per block: value 0 x column 0, never read by phase 2; -4.5 % per C4 SpMV against packed blocks)
-
-template <typename T>
-static int dalloc(T **p, size_t count)
-{
-    *p = nullptr;
-    hipError_t e = hipMalloc((void **)p, sizeof(T) * (count ? count : 1));
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%zu bytes) failed: %s", sizeof(T) * count, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? CUDAMAT_ERR_NOMEM : CUDAMAT_ERR_HIP;
-    }
-    return CUDAMAT_OK;
-}
 
 void pb_free(PbPlan *p)
 {
@@ -428,29 +417,6 @@ __global__ __launch_bounds__(kBlock) void k_pb_colsum(int NSUB, const int *bins,
     }
 }
 
-// inclusive scan of one value per thread over the workgroup; returns the exclusive prefix, *total = sum
-__device__ __forceinline__ int block_exclusive_scan(int v, int *lds_waves, int *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    __syncthreads();                       // lds_waves may still be read from the previous round
-    if (lane == 63) lds_waves[wave] = inc;
-    __syncthreads();
-    int before = 0, all = 0;
-    for (int w = 0; w < kBlock / 64; w++) {
-        const int t = lds_waves[w];
-        if (w < wave) before += t;
-        all += t;
-    }
-    *total = all;
-    return before + inc - v;
-}
-
 __global__ __launch_bounds__(kBlock) void k_pb_colscan(int NCB, const int *colsum, int *cstart, int align)
 {
     __shared__ int lds_waves[kBlock / 64];
@@ -459,7 +425,7 @@ __global__ __launch_bounds__(kBlock) void k_pb_colscan(int NCB, const int *colsu
         const int c = c0 + threadIdx.x;
         const int v = c < NCB ? (colsum[c] + align - 1) / align * align : 0;     // every block starts on an `align` boundary
         int total;
-        const int ex = block_exclusive_scan(v, lds_waves, &total);
+        const int ex = block_scan_int(v, lds_waves, &total);
         if (c < NCB) cstart[c] = run + ex;
         run += total;
     }
@@ -477,7 +443,7 @@ __global__ __launch_bounds__(kBlock) void k_pb_segscan(int NCB, int NSUB, const 
         const int sidx = s0 + threadIdx.x;
         const int cnt = sidx < NSUB ? b[sidx] : 0;
         int total;
-        const int ex = block_exclusive_scan(cnt, lds_waves, &total);
+        const int ex = block_scan_int(cnt, lds_waves, &total);
         if (sidx < NSUB) {
             const int start = run + ex;
             b[sidx] = start;
@@ -599,14 +565,14 @@ int pb_build_alloc(hipStream_t st, const Config &cfg, int n, int64_t n_cols, int
     bins = nullptr;
     int rc = CUDAMAT_OK;
     do {
-        if ((rc = dalloc(&bins, nbins))) break;
+        if ((rc = dev_alloc(&bins, nbins))) break;
         constexpr int align = kPbAlign;
         const size_t cap = (size_t)nnz + (size_t)(align - 1) * (size_t)p.NCB + 16;
         b->cap = cap;
         // (pc, pr, P and the value array: pb_build_values, which places them)
-        if ((rc = dalloc(&p.cstart, (size_t)p.NCB + 1))) break;
-        if ((rc = dalloc(&p.col0, (size_t)p.NCB + 1))) break;
-        if ((rc = dalloc(&p.order, (size_t)p.NCB))) break;
+        if ((rc = dev_alloc(&p.cstart, (size_t)p.NCB + 1))) break;
+        if ((rc = dev_alloc(&p.col0, (size_t)p.NCB + 1))) break;
+        if ((rc = dev_alloc(&p.order, (size_t)p.NCB))) break;
         {
             // first column of every block (blocks tile [0, n_cols) in order; blocks past the end are empty) and the
             // phase-1 launch parts: the local slice first, then piece after piece of the other slices
@@ -644,8 +610,8 @@ int pb_build_alloc(hipStream_t st, const Config &cfg, int n, int64_t n_cols, int
                 hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("pb column cut upload failed"); break; }
         }
         b->cut = PbCut{(int)p.per, p.chunks, (int)p.chunk_len, p.bpc, p.CB};
-        if ((rc = dalloc(&p.sstart, nbins))) break;
-        if ((rc = dalloc(&p.slen, nbins))) break;
+        if ((rc = dev_alloc(&p.sstart, nbins))) break;
+        if ((rc = dev_alloc(&p.slen, nbins))) break;
         if ((rc = set_max_lds((const void *)k_pb_count))) break;
         if ((rc = set_max_lds((const void *)k_pb_rows<true>))) break;
         // the two-pass fill's scratch (see k_pb_group): one packed word per entry, the buckets' first entries
@@ -659,7 +625,7 @@ int pb_build_alloc(hipStream_t st, const Config &cfg, int n, int64_t n_cols, int
         b->report_classes = cfg.verbose >= 2;
         b->two_pass = cfg.pb_fill2 != 0 && nnz > 0 && nnz < 0x7fffffffLL && p.SR <= 65536 && b->GB <= 64;
         if (b->two_pass) {
-            if (dalloc(&b->smeta, (size_t)nnz) != CUDAMAT_OK || dalloc(&b->gstart, (size_t)p.NSUB * (size_t)(b->NG + 1)) != CUDAMAT_OK) {
+            if (dev_alloc(&b->smeta, (size_t)nnz) != CUDAMAT_OK || dev_alloc(&b->gstart, (size_t)p.NSUB * (size_t)(b->NG + 1)) != CUDAMAT_OK) {
                 // (no room for the scratch: the single-pass fill needs none)
                 if (b->smeta) CM_DROP(hipFree(b->smeta));
                 b->smeta = nullptr;
@@ -1010,6 +976,10 @@ int pb_build_values(hipStream_t st, PbBuild *b, const ValDict *vd)
     const size_t cap = b->cap;
     const bool dict = vd && vd->n > 0;
     int rc = CUDAMAT_OK;
+    if (dict && p.pv) {                    // the drop-in path swaps the fp64 values it allocated early for dictionary indices
+        CM_DROP(hipFree(p.pv));
+        p.pv = nullptr;
+    }
     do {
         if (!p.P && b->place > 0 && sizeof(double) * cap >= kPlaceMinBytes) {
             void *v = nullptr, *c = nullptr, *r = nullptr, *pp = nullptr;
@@ -1023,18 +993,18 @@ int pb_build_values(hipStream_t st, PbBuild *b, const ValDict *vd)
             }
         }
         if (dict) {
-            if (!p.pvi && (rc = dalloc(&p.pvi, cap))) break;
+            if (!p.pvi && (rc = dev_alloc(&p.pvi, cap))) break;
             if (hipMemsetAsync(p.pvi, 0, cap, st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
             p.dict = vd->dict;
             p.ndict = vd->n;
         } else {
-            if (!p.pv && (rc = dalloc(&p.pv, cap))) break;
+            if (!p.pv && (rc = dev_alloc(&p.pv, cap))) break;
             if (hipMemsetAsync(p.pv, 0, sizeof(double) * cap, st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
         }
         if (p.P && p.pc && p.pr && p.pc_zeroed) break;          // (the drop-in path swaps fp64 values for dictionary indices afterwards: the rest is in place)
-        if (!p.pc && (rc = dalloc(&p.pc, cap))) break;
-        if (!p.pr && (rc = dalloc(&p.pr, cap))) break;
-        if (!p.P && (rc = dalloc(&p.P, cap))) break;
+        if (!p.pc && (rc = dev_alloc(&p.pc, cap))) break;
+        if (!p.pr && (rc = dev_alloc(&p.pr, cap))) break;
+        if (!p.P && (rc = dev_alloc(&p.P, cap))) break;
         if (kPbAlign > 1 && hipMemsetAsync(p.pc, 0, sizeof(u16) * cap, st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
         p.pc_zeroed = true;
     } while (0);
@@ -1412,7 +1382,7 @@ int pb_strict_for(cudamat_ctx *ctx, int *strict)
     *strict = 1;
     if (ctx->cfg.pb_strict) return CUDAMAT_OK;
     if (ctx->lds_lane_order < 0) {
-        int *flag = (int *)ctx->scratch, h = 1;
+        int *flag = (int *)ctx->scratch.get(), h = 1;
         CM_HIP(hipMemsetAsync(flag, 0, sizeof(int), ctx->stream));
         hipLaunchKernelGGL(k_lds_order_probe, dim3(1), dim3(64), 0, ctx->stream, flag);
         CM_HIP(hipGetLastError());

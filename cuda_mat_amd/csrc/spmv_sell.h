@@ -11,11 +11,11 @@ struct SellPlan {
     long long slots = 0;           // stored slots incl. padding
     double fill = 1.0;             // slots / nnz
     int grid = 0, chunks_per_block = 0;
-    double *val = nullptr;         // [slots] column-major inside a chunk
-    int *col = nullptr;
-    int *perm = nullptr;           // [nchunks * 64] original row of every chunk lane, -1 = padding row
-    int *len = nullptr;            // [nchunks * 64] entries of that row
-    long long *chunk_off = nullptr;   // [nchunks + 1] first column (of 64 slots) of every chunk
+    DevBuf<double> val;            // [slots] column-major inside a chunk
+    DevBuf<int> col;
+    DevBuf<int> perm;             // [nchunks * 64] original row of every chunk lane, -1 = padding row
+    DevBuf<int> len;              // [nchunks * 64] entries of that row
+    DevBuf<long long> chunk_off;     // [nchunks + 1] first column (of 64 slots) of every chunk
     double build_seconds = 0.0;
 };
 

@@ -12,6 +12,7 @@
 // The window sort bounds both the padding and the distance between a row and its output (good for banded x).
 // Chosen per matrix by timing it against the other forms (solver.hip, ensure_spmv_mode).
 #include <algorithm>
+#include <utility>
 #include <vector>
 
 #include "device.h"
@@ -22,25 +23,7 @@ namespace cm {
 constexpr int kSigma = 1024;          // rows per sorting window (16 chunks)
 constexpr int kChunk = 64;
 
-template <typename T>
-static int dalloc(T **p, size_t count)
-{
-    *p = nullptr;
-    hipError_t e = hipMalloc((void **)p, sizeof(T) * (count ? count : 1));
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%zu bytes) failed: %s", sizeof(T) * count, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? CUDAMAT_ERR_NOMEM : CUDAMAT_ERR_HIP;
-    }
-    return CUDAMAT_OK;
-}
-
-void sell_free(SellPlan *p)
-{
-    void *ptrs[] = {p->val, p->col, p->perm, p->len, p->chunk_off};
-    for (void *q : ptrs)
-        if (q) CM_DROP(hipFree(q));
-    *p = SellPlan();
-}
+void sell_free(SellPlan *p) { *p = SellPlan(); }
 
 // one workgroup per window: sort (length descending, row ascending) with a bitonic network in LDS
 __global__ __launch_bounds__(kBlock) void k_sell_sort(int n, const int *rp, int *perm, int *len, int *width)
@@ -103,41 +86,32 @@ int sell_build(hipStream_t st, int n, int64_t nnz, const int *rp, const int *ci,
     p.nnz = nnz;
     const int nwin = (n + kSigma - 1) / kSigma;
     p.nchunks = nwin * (kSigma / kChunk);
-    int *width = nullptr;
-    int rc = CUDAMAT_OK;
-    do {
-        if (n <= 0) { rc = CUDAMAT_ERR_ARG; set_error("sell_build: empty matrix"); break; }
-        if ((rc = dalloc(&p.perm, (size_t)p.nchunks * kChunk))) break;
-        if ((rc = dalloc(&p.len, (size_t)p.nchunks * kChunk))) break;
-        if ((rc = dalloc(&p.chunk_off, (size_t)p.nchunks + 1))) break;
-        if ((rc = dalloc(&width, (size_t)p.nchunks))) break;
-        hipLaunchKernelGGL(k_sell_sort, dim3(nwin), dim3(kBlock), 0, st, n, rp, p.perm, p.len, width);
-        std::vector<int> hw((size_t)p.nchunks);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(hw.data(), width, sizeof(int) * hw.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("sell sort failed"); break; }
-        std::vector<long long> off((size_t)p.nchunks + 1, 0);
-        for (int c = 0; c < p.nchunks; c++) off[(size_t)c + 1] = off[(size_t)c] + hw[(size_t)c];
-        p.slots = off[(size_t)p.nchunks] * kChunk;
-        p.fill = nnz > 0 ? (double)p.slots / (double)nnz : 1.0;
-        if (max_fill > 0.0 && p.fill > max_fill) {            // too much padding: not worth a copy (not an error)
-            rc = CUDAMAT_ERR_ARG;
-            set_error("sell_build: padded copy would hold %.2f x the entries", p.fill);
-            break;
-        }
-        if (hipMemcpyAsync(p.chunk_off, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
-        if ((rc = dalloc(&p.val, (size_t)p.slots))) break;
-        if ((rc = dalloc(&p.col, (size_t)p.slots))) break;
-        hipLaunchKernelGGL(k_sell_fill, dim3((unsigned)((p.nchunks + 3) / 4)), dim3(kBlock), 0, st, p.nchunks, rp, ci, val,
-                           p.perm, p.len, p.chunk_off, p.val, p.col);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rc = CUDAMAT_ERR_HIP; set_error("sell fill failed"); break; }
-    } while (0);
-    if (width) CM_DROP(hipFree(width));
-    if (rc) {
-        sell_free(&p);
-        return rc;
+    DevBuf<int> width;
+    if (n <= 0) { set_error("sell_build: empty matrix"); return CUDAMAT_ERR_ARG; }
+    CM_TRY(p.perm.alloc((size_t)p.nchunks * kChunk));
+    CM_TRY(p.len.alloc((size_t)p.nchunks * kChunk));
+    CM_TRY(p.chunk_off.alloc((size_t)p.nchunks + 1));
+    CM_TRY(width.alloc((size_t)p.nchunks));
+    hipLaunchKernelGGL(k_sell_sort, dim3(nwin), dim3(kBlock), 0, st, n, rp, p.perm, p.len, width);
+    std::vector<int> hw((size_t)p.nchunks);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(hw.data(), width, sizeof(int) * hw.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) { set_error("sell sort failed"); return CUDAMAT_ERR_HIP; }
+    std::vector<long long> off((size_t)p.nchunks + 1, 0);
+    for (int c = 0; c < p.nchunks; c++) off[(size_t)c + 1] = off[(size_t)c] + hw[(size_t)c];
+    p.slots = off[(size_t)p.nchunks] * kChunk;
+    p.fill = nnz > 0 ? (double)p.slots / (double)nnz : 1.0;
+    if (max_fill > 0.0 && p.fill > max_fill) {            // too much padding: not worth a copy (not an error)
+        set_error("sell_build: padded copy would hold %.2f x the entries", p.fill);
+        return CUDAMAT_ERR_ARG;
     }
+    if (hipMemcpyAsync(p.chunk_off, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) return CUDAMAT_ERR_HIP;
+    CM_TRY(p.val.alloc((size_t)p.slots));
+    CM_TRY(p.col.alloc((size_t)p.slots));
+    hipLaunchKernelGGL(k_sell_fill, dim3((unsigned)((p.nchunks + 3) / 4)), dim3(kBlock), 0, st, p.nchunks, rp, ci, val,
+                       p.perm, p.len, p.chunk_off, p.val, p.col);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { set_error("sell fill failed"); return CUDAMAT_ERR_HIP; }
     // workgroups own contiguous runs of chunks; at most kSpmvGridMax of them (one pair of dot partials each)
     const int per_block = kBlock / kChunk;
     long long blocks = ((long long)p.nchunks + per_block - 1) / per_block;
@@ -148,7 +122,7 @@ int sell_build(hipStream_t st, int n, int64_t nnz, const int *rp, const int *ci,
     }
     p.grid = (int)blocks;
     p.build_seconds = now_s() - t0;
-    *out = p;
+    *out = std::move(p);
     return CUDAMAT_OK;
 }
 

@@ -8,8 +8,8 @@ constexpr int kDictMax = 256;      // distinct values an 8-bit index can name
 
 struct ValDict {
     int n = 0;                       // distinct values (0: the matrix has more than kDictMax, no dictionary)
-    double *dict = nullptr;          // device, kDictMax doubles (ascending bit patterns; the unused tail is 0)
-    unsigned char *idx = nullptr;    // device, one index per entry in CSR order: val[k] == dict[idx[k]] bit for bit
+    DevBuf<double> dict;             // device, kDictMax doubles (ascending bit patterns; the unused tail is 0)
+    DevBuf<unsigned char> idx;       // device, one index per entry in CSR order: val[k] == dict[idx[k]] bit for bit
 };
 
 // Scan the values (device array, nnz entries); when at most kDictMax distinct bit patterns occur, build the

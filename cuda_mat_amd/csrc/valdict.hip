@@ -107,67 +107,69 @@ int valdict_sample_overflows(hipStream_t st, int64_t count, const double *val, v
     return CUDAMAT_OK;
 }
 
-void valdict_free(ValDict *v)
+void valdict_free(ValDict *v) { *v = ValDict(); }
+
+// host copy of flags[0..1] once the stream has drained
+static int read_flags(hipStream_t st, const int *flags, int h[2], const char *what)
 {
-    if (v->dict) CM_DROP(hipFree(v->dict));
-    if (v->idx) CM_DROP(hipFree(v->idx));
-    *v = ValDict();
+    if (hipMemcpyAsync(h, flags, 2 * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        set_error("value dictionary: %s failed (%s)", what, hipGetErrorString(hipGetLastError()));
+        return CUDAMAT_ERR_HIP;
+    }
+    return CUDAMAT_OK;
 }
 
 int valdict_build(hipStream_t st, const Config &cfg, int64_t nnz, const double *val, ValDict *out)
 {
     *out = ValDict();
     if (!cfg.value_dict || nnz < 4096) return CUDAMAT_OK;      // (tiny matrices live in caches anyway)
-    unsigned long long *table = nullptr;
-    int *flags = nullptr;
+    DevBuf<unsigned long long> table;
+    DevBuf<int> flags;
     int h[2] = {0, 0};
-    int rc = CUDAMAT_OK;
+    CM_TRY(table.alloc(kTableSlots));
+    CM_TRY(flags.alloc(2));
+    CM_HIP(hipMemsetAsync(table, 0xFF, sizeof(unsigned long long) * kTableSlots, st));
+    CM_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int), st));
+    // a sample first: arbitrary values overflow the table within the first few thousand entries
+    const int64_t sample = nnz < (1 << 20) ? nnz : (1 << 20);
+    const int64_t pieces[2][2] = {{0, sample}, {sample, nnz - sample}};
+    for (int p = 0; p < 2; p++) {
+        if (pieces[p][1] <= 0) continue;
+        int64_t g = (pieces[p][1] + kBlock - 1) / kBlock;
+        if (g > 8192) g = 8192;
+        hipLaunchKernelGGL(k_dict_probe, dim3((unsigned)g), dim3(kBlock), 0, st, pieces[p][0], pieces[p][1], val, table.get(), flags.get());
+        CM_TRY(read_flags(st, flags, h, "probe"));
+        if (h[1] != 0 || h[0] > kDictMax) return CUDAMAT_OK;   // more distinct values than an index names
+    }
+    if (h[0] < 1) return CUDAMAT_OK;
+    std::vector<unsigned long long> keys(kTableSlots);
+    if (hipMemcpy(keys.data(), table, sizeof(unsigned long long) * kTableSlots, hipMemcpyDeviceToHost) != hipSuccess) return CUDAMAT_ERR_HIP;
+    keys.erase(std::remove(keys.begin(), keys.end(), kEmpty), keys.end());
+    std::sort(keys.begin(), keys.end());
+    if ((int)keys.size() != h[0] || keys.size() > (size_t)kDictMax) {
+        set_error("value dictionary: table count mismatch");
+        return CUDAMAT_ERR_HIP;
+    }
+    std::vector<double> dict((size_t)kDictMax, 0.0);
+    for (size_t i = 0; i < keys.size(); i++) std::memcpy(&dict[i], &keys[i], sizeof(double));
     ValDict v;
-    do {
-        if (hipMalloc((void **)&table, sizeof(unsigned long long) * kTableSlots) != hipSuccess ||
-            hipMalloc((void **)&flags, 2 * sizeof(int)) != hipSuccess) { rc = CUDAMAT_ERR_NOMEM; set_error("value dictionary: out of memory"); break; }
-        if ((rc = CM_RC(hipMemsetAsync(table, 0xFF, sizeof(unsigned long long) * kTableSlots, st)))) break;
-        if ((rc = CM_RC(hipMemsetAsync(flags, 0, 2 * sizeof(int), st)))) break;
-        // a sample first: arbitrary values overflow the table within the first few thousand entries
-        const int64_t sample = nnz < (1 << 20) ? nnz : (1 << 20);
-        const int64_t pieces[2][2] = {{0, sample}, {sample, nnz - sample}};
-        bool over = false;
-        for (int p = 0; p < 2 && !over; p++) {
-            if (pieces[p][1] <= 0) continue;
-            int64_t g = (pieces[p][1] + kBlock - 1) / kBlock;
-            if (g > 8192) g = 8192;
-            hipLaunchKernelGGL(k_dict_probe, dim3((unsigned)g), dim3(kBlock), 0, st, pieces[p][0], pieces[p][1], val, table, flags);
-            if (hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-                rc = CUDAMAT_ERR_HIP; set_error("value dictionary: probe failed (%s)", hipGetErrorString(hipGetLastError())); break;
-            }
-            over = h[1] != 0 || h[0] > kDictMax;
-        }
-        if (rc || over || h[0] < 1) break;
-        std::vector<unsigned long long> keys(kTableSlots);
-        if (hipMemcpy(keys.data(), table, sizeof(unsigned long long) * kTableSlots, hipMemcpyDeviceToHost) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
-        keys.erase(std::remove(keys.begin(), keys.end(), kEmpty), keys.end());
-        std::sort(keys.begin(), keys.end());
-        if ((int)keys.size() != h[0] || keys.size() > (size_t)kDictMax) { rc = CUDAMAT_ERR_HIP; set_error("value dictionary: table count mismatch"); break; }
-        std::vector<double> dict((size_t)kDictMax, 0.0);
-        for (size_t i = 0; i < keys.size(); i++) std::memcpy(&dict[i], &keys[i], sizeof(double));
-        if (hipMalloc((void **)&v.dict, sizeof(double) * kDictMax) != hipSuccess ||
-            hipMalloc((void **)&v.idx, (size_t)nnz + 16) != hipSuccess) { valdict_free(&v); break; }      // no memory: no dictionary
-        if (hipMemcpy(v.dict, dict.data(), sizeof(double) * kDictMax, hipMemcpyHostToDevice) != hipSuccess) { rc = CUDAMAT_ERR_HIP; break; }
-        if ((rc = CM_RC(hipMemsetAsync(flags, 0, 2 * sizeof(int), st)))) break;
-        int64_t g = (nnz + kBlock - 1) / kBlock;
-        if (g > 16384) g = 16384;
-        hipLaunchKernelGGL(k_dict_index, dim3((unsigned)g), dim3(kBlock), 0, st, nnz, val, v.dict, (int)keys.size(), v.idx, flags);
-        if (hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-            rc = CUDAMAT_ERR_HIP; set_error("value dictionary: index pass failed (%s)", hipGetErrorString(hipGetLastError())); break;
-        }
-        if (h[1]) { rc = CUDAMAT_ERR_HIP; set_error("value dictionary: a value is missing from its own dictionary"); break; }
-        v.n = (int)keys.size();
-    } while (0);
-    if (table) CM_DROP(hipFree(table));
-    if (flags) CM_DROP(hipFree(flags));
-    if (rc != CUDAMAT_OK || v.n == 0) valdict_free(&v);
-    else *out = v;
-    return rc;
+    int rc = v.dict.alloc(kDictMax);
+    if (rc == CUDAMAT_OK) rc = v.idx.alloc((size_t)nnz + 16);
+    if (rc == CUDAMAT_ERR_NOMEM) return CUDAMAT_OK;            // no memory: no dictionary
+    CM_TRY(rc);
+    if (hipMemcpy(v.dict, dict.data(), sizeof(double) * kDictMax, hipMemcpyHostToDevice) != hipSuccess) return CUDAMAT_ERR_HIP;
+    CM_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int), st));
+    int64_t g = (nnz + kBlock - 1) / kBlock;
+    if (g > 16384) g = 16384;
+    hipLaunchKernelGGL(k_dict_index, dim3((unsigned)g), dim3(kBlock), 0, st, nnz, val, v.dict.get(), (int)keys.size(), v.idx.get(), flags.get());
+    CM_TRY(read_flags(st, flags, h, "index pass"));
+    if (h[1]) {
+        set_error("value dictionary: a value is missing from its own dictionary");
+        return CUDAMAT_ERR_HIP;
+    }
+    v.n = (int)keys.size();
+    *out = std::move(v);
+    return CUDAMAT_OK;
 }
 
 }  // namespace cm

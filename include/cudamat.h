@@ -424,6 +424,11 @@ int cudamat_pool_trim(void);
 /* what the driver reports free / in total on `device` (hipMemGetInfo) and, of the memory the driver counts as used, how
  * much the library's pool could hand out again without asking it; any pointer may be NULL */
 int cudamat_mem_info(int device, size_t *driver_free, size_t *driver_total, size_t *pool_free);
+/* device allocations of this library that are in use, over all devices of the process: every allocation counts one,
+ * small, pooled or with CUDAMAT_POOL=0, until it is freed (a block still in the pool's free list does not count).  Equal
+ * before and after a piece of work that destroyed everything it created: nothing leaked.  Pinned host memory is not
+ * counted. */
+int cudamat_mem_live(size_t *allocations);
 
 /* The same solve over `ngpu` GPUs of this node, from one process: uniform row blocks, one host
  * thread and one RCCL rank per device (csrc/sharded.cpp).  precond: NONE or BLOCK_ILU0 (each
