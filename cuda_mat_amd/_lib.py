@@ -103,6 +103,8 @@ _SIGS = {
     "cudamat_solver_destroy": (C.c_int, [_P]),
     "cudamat_solver_set_shift": (C.c_int, [_P, _P]),
     "cudamat_solver_ilu0": (C.c_int, [_P]),
+    "cudamat_solver_ilu0_shift": (C.c_int, [_P, _P]),
+    "cudamat_solver_ilu0_shifted": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "cudamat_solver_block_ilu0": (C.c_int, [_P]),
     "cudamat_solver_ilu0_values": (C.c_int, [_P, _P]),
     "cudamat_solver_ilu0_nnz": (C.c_int, [_P, C.POINTER(C.c_int64)]),

@@ -4,6 +4,7 @@ Names and argument meaning follow pbicgstab.h / mmio_wrapper.h of the reference:
   bicgstab(n, nnz, A, iA, jA, b, maxit, tol, debug)                  pbicgstab.h:113
   bicgstab_d(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug)      pbicgstab.h:116 (overload)
   bicgstab_lu_precond(n, nnz, A, iA, jA, b, maxit, tol, debug)       pbicgstab.h:119
+  bicgstab_d_lu_precond(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug)   ILU(0) of A0 + diag(d), the loop with d (new)
   bicgstab_many(n, nnz, A, iA, jA, B, maxit, tol, d, x0)             bicgstab / bicgstab_d for the columns of B (new)
   bicgstab_lu_precond_many(n, nnz, A, iA, jA, B, maxit, tol)         bicgstab_lu_precond for the columns of B (new)
   bicgstab_d_many(n, nnz, A0, iA0, jA0, D, x0, B, maxit, tol)        bicgstab_d with shift D[:, j] for column j of B (new)
@@ -82,6 +83,18 @@ def bicgstab_lu_precond(n, nnz, A, iA, jA, b, maxit, tol, debug=False):
     Like the reference (pbicgstab.cu:408) `ok` is True whenever the solve ran; convergence is
     in stats.converged."""
     x, st = _solve(n, nnz, A, iA, jA, None, None, b, PRECOND_ILU0, LOOP_PBICGSTAB, maxit, tol, debug)
+    return True, x, st.t_solve, st
+
+
+def bicgstab_d_lu_precond(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug=False):
+    """solve (A0 + I*d) x = b from x0 with the ILU(0) preconditioner of A0 + diag(d) (not in the reference: the overload
+    bicgstab_lu_precond(..., d, x0, ...) of include/pbicgstab.h).  Returns what bicgstab_lu_precond returns.  A repeated call
+    with the same matrix reuses the factors only when d is byte-identical to the one they were built from."""
+    if d is None:
+        raise ValueError("d is required (bicgstab_lu_precond is the call without a shift)")
+    if _GPUS > 1:
+        raise ValueError("ILU(0) of the shifted matrix is one-GPU only: use_gpus(%d) is set (block-Jacobi takes no shift)" % _GPUS)
+    x, st = _solve(n, nnz, A0, iA0, jA0, d, x0, b, PRECOND_ILU0, LOOP_PBICGSTAB, maxit, tol, debug)
     return True, x, st.t_solve, st
 
 
@@ -392,8 +405,19 @@ class Solver:
         self._keep.append(comm)
         check(_lib.lib().cudamat_solver_set_comm(self.h, None if comm is None else C.byref(comm)))
 
-    def ilu0(self):
-        check(_lib.lib().cudamat_solver_ilu0(self.h))
+    def ilu0(self, shift=None):
+        """ILU(0) of the matrix, or -- shift: a device vector of n doubles, read during the call only and independent of
+        set_shift -- of A0 + diag(shift) (cudamat_solver_ilu0_shift: one GPU, whole matrix)"""
+        if shift is None:
+            check(_lib.lib().cudamat_solver_ilu0(self.h))
+        else:
+            check(_lib.lib().cudamat_solver_ilu0_shift(self.h, _ptr(shift)))
+
+    def ilu0_shifted(self):
+        """True when the factors are those of a shifted matrix (ilu0(shift=...)): a solver shift may then be preconditioned"""
+        y = C.c_int()
+        check(_lib.lib().cudamat_solver_ilu0_shifted(self.h, C.byref(y)))
+        return bool(y.value)
 
     def trsv_form(self):
         """1: dependency-driven triangular solves, 0: one launch per level"""

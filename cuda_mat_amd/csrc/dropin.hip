@@ -540,9 +540,27 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
         if (g_cache.d_d && !reused) { cudamat_free(ctx, g_cache.d_d); g_cache.d_d = nullptr; }
         // (per-column shifts travel with the call: the solver itself keeps none, and the block goes when the call returns)
         if ((rc = cudamat_solver_set_shift(s, h.shifts ? nullptr : d_d))) break;
-        if (precond != CUDAMAT_PRECOND_NONE && !(reused && s->has_ilu && !s->ilu_block)) {
-            if ((rc = cudamat_solver_ilu0(s))) break;
-            built_ilu = true;
+        if (precond != CUDAMAT_PRECOND_NONE) {
+            // one solve of (A0 + I d) with ILU(0): the factors are those of A0 + diag(d).  The cache compares the matrix, not the
+            // shift, so kept factors serve only a d that is byte-identical to the one they were built from (the solver's copy);
+            // otherwise the factorisation is redone and the rest of the plan stays.  (The batched calls keep their refusals.)
+            const double *d_factor = !many && h.d && precond == CUDAMAT_PRECOND_ILU0 ? d_d.get() : nullptr;
+            bool have = reused && s->has_ilu && !s->ilu_block && s->ilu_shifted == (d_factor != nullptr) &&
+                        (!d_factor || s->ilu_d);
+            if (have && d_factor) {
+                DevBuf<int> flag;
+                int hflag = 1;
+                if ((rc = flag.alloc(1))) break;
+                if ((rc = CM_RC(hipMemsetAsync(flag, 0, sizeof(int), ctx->stream)))) break;
+                if ((rc = device_equal(ctx->stream, d_factor, s->ilu_d, sizeof(double) * (size_t)n, flag))) break;
+                if ((rc = CM_RC(hipMemcpyAsync(&hflag, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream)))) break;
+                if ((rc = CM_RC(hipStreamSynchronize(ctx->stream)))) break;
+                have = hflag == 0;
+            }
+            if (!have) {
+                if ((rc = ilu0_setup(s, false, d_factor, true))) break;
+                built_ilu = true;
+            }
         }
         if (precond != CUDAMAT_PRECOND_NONE && debug) {
             printf("analysis lower %f (s), upper %f (s) \n", s->t_analysis_l, s->t_analysis_u);     // :349

@@ -368,6 +368,8 @@ int ilu0_release(cudamat_solver *s)
     valdict_free(&s->vd_perm);
     s->x_perm.reset();
     s->b_perm.reset();
+    s->xd_idx.reset();
+    s->d_perm.reset();
     s->perm_ready = false;
     s->perm_failed = false;
     s->lu.reset();
@@ -381,6 +383,8 @@ int ilu0_release(cudamat_solver *s)
     s->pm_owned = false;
     s->ilu_block = false;
     s->has_ilu = false;
+    s->ilu_shifted = false;
+    s->ilu_d.reset();
     s->ilu_plans.reset();
     return CUDAMAT_OK;
 }
@@ -1205,12 +1209,25 @@ void ilu0_flush_deferred(cudamat_solver *s)
     if (IluPlans *pl = plans_of(s, false)) flush_deferred(pl->deferred);
 }
 
-static int ilu0_setup_body(cudamat_solver *s, IluPlans *pl);
+static int ilu0_setup_body(cudamat_solver *s, IluPlans *pl, const double *d_factor, bool keep_shift);
 
-int ilu0_setup(cudamat_solver *s, bool block)
+// lu[diag_pos[i]] += d_factor[i]: the copied values of A0 become those of A0 + diag(d_factor) (cudamat_solver_ilu0_shift).
+// One plain add per row, one rounding: contraction is off and there is no product to contract with.
+__global__ __launch_bounds__(kBlock) void k_shift_diag(int64_t n, const int *diag_pos, const double *d_factor, double *lu)
+{
+#pragma clang fp contract(off)
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const int p = diag_pos[i];
+        lu[p] = lu[p] + d_factor[i];
+    }
+}
+
+int ilu0_setup(cudamat_solver *s, bool block, const double *d_factor, bool keep_shift)
 {
     CM_ARG(block || !s->sharded, "ILU(0) of the whole matrix is single-GPU only (use the block variant)");
     CM_ARG(s->cols_sorted, "ILU(0) needs every row's column indices strictly increasing (mmio_wrapper.h:123 delivers that)");
+    CM_ARG(!d_factor || (!block && !s->sharded), "ILU(0) of a shifted matrix is single-GPU, whole-matrix only");
     CM_HIP(hipSetDevice(s->ctx->device));
     Range range_ilu("cudamat: ILU(0) analysis + factorisation + factor layout");
     {
@@ -1220,14 +1237,14 @@ int ilu0_setup(cudamat_solver *s, bool block)
     }
     IluPlans *pl = plans_of(s, true);
     pl->analysed = false;                  // (consumed: a second ilu0_setup on this solver starts over)
-    const int rc = ilu0_setup_body(s, pl);
+    const int rc = ilu0_setup_body(s, pl, d_factor, keep_shift);
     if (rc) return ilu0_fail(s, rc);
     pl->d_flags.reset();                   // the scratch of the analysis has served
     pl->d_lev.reset();
     return CUDAMAT_OK;
 }
 
-static int ilu0_setup_body(cudamat_solver *s, IluPlans *pl)
+static int ilu0_setup_body(cudamat_solver *s, IluPlans *pl, const double *d_factor, bool keep_shift)
 {
     hipStream_t st = s->ctx->stream;
     const int n = s->n;
@@ -1241,6 +1258,17 @@ static int ilu0_setup_body(cudamat_solver *s, IluPlans *pl)
     if (hipMemcpyAsync(s->lu, s->pm_val, sizeof(double) * (size_t)s->pm_nnz, hipMemcpyDeviceToDevice, st) != hipSuccess) {
         set_error("copy of A values failed");
         return CUDAMAT_ERR_HIP;
+    }
+    if (d_factor && n) {      // the factors of A0 + diag(d_factor)
+        hipLaunchKernelGGL(k_shift_diag, dim3(row_grid(n)), dim3(kBlock), 0, st, (int64_t)n, s->diag_pos, d_factor, s->lu);
+        if (hipGetLastError() != hipSuccess) { set_error("diagonal shift launch failed"); return CUDAMAT_ERR_HIP; }
+    }
+    if (d_factor && n && keep_shift) {      // (the drop-in call compares the next call's d with this copy: dropin.hip)
+        CM_TRY(s->ilu_d.alloc((size_t)n));
+        if (hipMemcpyAsync(s->ilu_d, d_factor, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+            set_error("copy of the factor shift failed");
+            return CUDAMAT_ERR_HIP;
+        }
     }
     const int maxrow = maxrow_all;
     const int cap = ((maxrow + 63) / 64) * 64 + 64;
@@ -1293,6 +1321,12 @@ static int ilu0_setup_body(cudamat_solver *s, IluPlans *pl)
         if (pl->L.hybrid && pl->U.hybrid) {
             CM_TRY(mapUL.alloc((size_t)n));
             hipLaunchKernelGGL(k_compose_perm, dim3(gp), dim3(kBlock), 0, st, n, s->U.row_of, posL, mapUL);
+            // ... and the other way round, for the shift term of the loop in level-major spaces: where in U's space x_i sits
+            // for the row at each position of L's (shifted factors only: no other factors meet a shift, loops.hip)
+            if (d_factor) {
+                CM_TRY(s->xd_idx.alloc((size_t)n));
+                hipLaunchKernelGGL(k_compose_perm, dim3(gp), dim3(kBlock), 0, st, n, s->L.row_of, pl->posU, s->xd_idx);
+            }
             if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
                 set_error("permutation maps failed");
                 return CUDAMAT_ERR_HIP;
@@ -1361,6 +1395,7 @@ static int ilu0_setup_body(cudamat_solver *s, IluPlans *pl)
         // near launch loses its one-workgroup-per-CU residency.  Removed in round 4; HISTORY.md.)
     }
     s->has_ilu = true;
+    s->ilu_shifted = d_factor != nullptr;
     return CUDAMAT_OK;
 }
 
@@ -1431,6 +1466,19 @@ extern "C" int cudamat_solver_ilu0(cudamat_solver *s)
 {
     CM_ARG(s, "solver is NULL");
     return ilu0_setup(s, false);
+}
+
+extern "C" int cudamat_solver_ilu0_shift(cudamat_solver *s, const double *d_factor)
+{
+    CM_ARG(s, "solver is NULL");
+    return ilu0_setup(s, false, d_factor);
+}
+
+extern "C" int cudamat_solver_ilu0_shifted(cudamat_solver *s, int *yes)
+{
+    CM_ARG(s && yes, "null pointer");
+    *yes = s->has_ilu && s->ilu_shifted ? 1 : 0;
+    return CUDAMAT_OK;
 }
 
 extern "C" int cudamat_solver_ilu0_nnz(cudamat_solver *s, int64_t *count)

@@ -95,6 +95,8 @@ struct SpmvArgs {
     int check;
     ScalarSrc half;
     int pb_strict;        // blocked form, phase 2: add a row's products of one wave instruction rank by rank (Config::pb_strict)
+    const int *xd_idx;    // blocked form, phase 2: the shift term of row i reads xd[xd_idx[i]] (nullptr: xd[i]) -- rows and x in
+                          // different index spaces (the loop in level-major spaces with a shift, loops.hip)
 };
 int launch_spmv(hipStream_t s, const SpmvPlan &plan, const SpmvArgs &a);
 

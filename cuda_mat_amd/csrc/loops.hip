@@ -148,7 +148,11 @@ int Solve::setup()
     CM_ARG(maxit >= 0, "maxit");
     CM_ARG(!(precond == CUDAMAT_PRECOND_ILU0 && s->sharded),
            "ILU(0) of the whole matrix is single-GPU only (SURVEY 8e); sharded runs take CUDAMAT_PRECOND_BLOCK_ILU0");
-    CM_ARG(!(precond && s->d), "the (A0 + I d) variant has no preconditioner (pbicgstab.h:110)");
+    // a shift takes the factors of a shifted matrix only (cudamat_solver_ilu0_shift): A0 is never factored silently in its place
+    CM_ARG(!(precond && s->d) || (precond == CUDAMAT_PRECOND_ILU0 && s->has_ilu && s->ilu_shifted && !s->ilu_block),
+           "the (A0 + I d) variant has no preconditioner (pbicgstab.h:110)");
+    CM_ARG(!(precond && s->d && loop == CUDAMAT_LOOP_PIPELINED),
+           "the pipelined loop takes no preconditioner together with a shift (CUDAMAT_LOOP_PBICGSTAB / _PBICGSTAB2 do)");
     CM_HIP(hipSetDevice(s->ctx->device));
     cfg = &s->ctx->cfg;
     t_begin = now_s();
@@ -172,9 +176,10 @@ int Solve::setup()
     // order, the second in U's, and A is stored with rows in L's order and columns in U's positions (ilu_perm_matrix).
     // Then no vector is permuted inside the loop: per M^-1 application the only indexed access left besides the near
     // gathers is U reading its right-hand side from L's space (1 per row instead of 4).  b and x0 are permuted on the way
-    // in, x on the way out.  One GPU, reference loop; the option TRSV_PERM = 0 disables.
-    perm = precond == CUDAMAT_PRECOND_ILU0 && !s->sharded && loop == CUDAMAT_LOOP_PBICGSTAB && s->L.lm && s->U.lm && !s->d &&
-           cfg->trsv_perm && !s->perm_failed;
+    // in, x on the way out.  One GPU, reference loop; the option TRSV_PERM = 0 disables.  With a shift the term d_i x_i of
+    // a row in L's space meets x in U's: d is gathered into L's order below, x is read through the map xd_idx (spmv_local).
+    perm = precond == CUDAMAT_PRECOND_ILU0 && !s->sharded && loop == CUDAMAT_LOOP_PBICGSTAB && s->L.lm && s->U.lm &&
+           (!s->d || s->xd_idx) && cfg->trsv_perm && !s->perm_failed;
     if (perm && !s->perm_ready) {
         const int rcp = ilu_perm_matrix(s);
         if (rcp == CUDAMAT_ERR_NOMEM) { perm = false; s->perm_failed = true; }    // no room for the second blocked copy: permute per
@@ -187,6 +192,10 @@ int Solve::setup()
         if (!(flags & CUDAMAT_FLAG_X0_ONES)) CM_TRY(perm_to_space(s, true, x, s->x_perm));
         b = s->b_perm;
         x = s->x_perm;
+        if (s->d) {     // the shift in L's order -- gathered at every solve: the caller may have changed its contents
+            if (!s->d_perm) CM_TRY(s->d_perm.alloc((size_t)n));
+            CM_TRY(perm_to_space(s, false, s->d, s->d_perm));
+        }
     }
 
     // residual history: two entries per iteration (half / full step) or one; capped at 2^20 entries (8 MB) -- a solve

@@ -419,6 +419,9 @@ extern "C" int cudamat_solver_solve_shifts(cudamat_solver *s, int nrhs, const do
     CM_ARG(B && X, "null pointer");
     CM_ARG(ldb >= s->n && ldx >= s->n && (!D || ldd >= s->n), "leading dimension below the rows");
     CM_ARG(!(D && precond), "the (A0 + I d) variant has no preconditioner (pbicgstab.h:110)");
+    // ... and neither has the solver's own shift in a batch, whichever form the columns would take and whatever factors the
+    // solver holds (those of cudamat_solver_ilu0_shift serve the single solve only: loops.hip)
+    CM_ARG(!(s->d && precond), "the (A0 + I d) variant has no preconditioner (pbicgstab.h:110)");
     CM_ARG(maxit >= 0, "maxit");
     CM_ARG(loop == CUDAMAT_LOOP_PBICGSTAB || loop == CUDAMAT_LOOP_PBICGSTAB2 || loop == CUDAMAT_LOOP_PIPELINED, "loop");
     CM_HIP(hipSetDevice(s->ctx->device));

@@ -150,6 +150,8 @@ struct cudamat_solver {
     cm::DevBuf<int> pm_own_rp, pm_own_ci;        // the diagonal block's copy (pm_owned)
     cm::DevBuf<double> pm_own_val;
     bool ilu_block = false;    // factors belong to CUDAMAT_PRECOND_BLOCK_ILU0
+    bool ilu_shifted = false;  // factors are those of A0 + diag(ilu_d) (cudamat_solver_ilu0_shift): a solver shift may use them
+    cm::DevBuf<double> ilu_d;  // a copy of that shift (n doubles), kept for the drop-in call's cache only (else empty)
     cm::DevBuf<double> lu;     // pm_nnz doubles on that matrix's pattern
     cm::DevBuf<int> diag_pos;  // position of the diagonal in each row
     cm::TriFactor L, U;
@@ -159,6 +161,8 @@ struct cudamat_solver {
     cm::PbPlan pb_perm{};
     cm::ValDict vd_perm;
     cm::DevBuf<double> x_perm, b_perm;
+    cm::DevBuf<int> xd_idx;     // shifted factors: position in U's space of the row at each position of L's (that loop's d_i x_i)
+    cm::DevBuf<double> d_perm;  // the solver's shift in L's order, gathered at every solve (its contents may change between solves)
     bool perm_ready = false;    // pb_perm is built
     bool perm_failed = false;   // ... could not be (out of memory): the loop permutes around every M^-1 instead
     bool perm_active = false;   // the solve in progress runs in the level-major spaces (spmv_local uses pb_perm)
@@ -206,7 +210,9 @@ int precond_apply(cudamat_solver *s, const double *in, double *tmp, double *out,
 constexpr int kSortRowMax = 1024;     // longest row k_sort_rows stages (level-major index spaces need every row below it)
 int launch_sort_rows(hipStream_t st, int nrows, const int *src_rp, const int *src_of, const int *dst_rp, const int *ci,
                      const double *val, const int *colmap, int *out_ci, double *out_val);
-int ilu0_setup(cudamat_solver *s, bool block);
+// d_factor (device, n doubles, read during the call only): factor A0 + diag(d_factor); single GPU, whole matrix.
+// keep_shift: the solver keeps a copy of it (ilu_d: the drop-in call's cache asks whether the next call's d is the same)
+int ilu0_setup(cudamat_solver *s, bool block, const double *d_factor = nullptr, bool keep_shift = false);
 // the pattern-only part of ilu0_setup (diagonal positions, level analysis of L and U), kept for the ilu0_setup that follows
 int ilu0_analyse_early(cudamat_solver *s);
 void ilu0_flush_deferred(cudamat_solver *s);

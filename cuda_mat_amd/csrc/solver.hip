@@ -393,6 +393,10 @@ int spmv_local(cudamat_solver *s, const double *x_local, double *y, int dot, con
     a.half = half;
     a.pb_strict = 0;
     if (s->spmv_mode == 1 || s->perm_active) CM_TRY(pb_strict_for(s->ctx, &a.pb_strict));
+    if (s->perm_active && s->d) {        // rows in L's space, x in U's: the shift in L's order meets x at the row's position in U's
+        a.d = s->d_perm;
+        a.xd_idx = s->xd_idx;
+    }
     if (overlapped) {
         // The gather in pieces on the communicator's stream, phase 1 piece by piece behind it:
         //   comm stream  :  [wait x ready] piece 0 | piece 1 | ...

@@ -1295,6 +1295,7 @@ struct Pb2Args {
     double *parts;
     const LoopState *st;
     int strict;      // 1: a row's products of one wave instruction are added by SEPARATE instructions, rank by rank
+    const int *xd_idx;   // k_pb_phase2<., ., ., true>: the shift term of row i reads xd[xd_idx[i]]; the other instantiations never look at it
 };
 
 // One wave instruction's worth of products into the wave's y tile.  Equal rows sit in ADJACENT active lanes (a segment is
@@ -1400,7 +1401,10 @@ int pb_strict_for(cudamat_ctx *ctx, int *strict)
 }
 
 // DEPTH: segment loads a wave issues before it consumes the first (4; 8 / 16 when few waves are resident: shards)
-template <int NW, int LPS, int DEPTH>
+// IDX: the shift term of row i reads xd[xd_idx[i]] (launched only with a shift and a map).  A compile-time choice: as a test at
+// run time the map's pointer joins the argument loads at the kernel's entry and costs EVERY launch two SGPRs -- in the
+// DEPTH = 16 instantiations two more spills, in <16, 32, 8> a wave of occupancy (8 -> 7), with or without a shift.
+template <int NW, int LPS, int DEPTH, bool IDX = false>
 __global__ __launch_bounds__(64 * NW) void k_pb_phase2(Pb2Args a)
 {
     extern __shared__ __attribute__((aligned(16))) double yt[];   // NW * SR, then 2 * NW for the reduction
@@ -1496,7 +1500,7 @@ __global__ __launch_bounds__(64 * NW) void k_pb_phase2(Pb2Args a)
         const int row = (int)(row0 + i);
         double sum = my[i];
         if (a.d) {
-            const double dx = a.d[row] * a.xd[row];
+            const double dx = a.d[row] * a.xd[IDX ? a.xd_idx[row] : row];
             sum = sum + dx;
         }
         double out = a.alpha * sum;
@@ -1580,22 +1584,28 @@ int launch_pb_phase2(hipStream_t st, const PbPlan &p, const SpmvArgs &a)
     b.n = p.n; b.NCB = p.NCB; b.SR = p.SR;
     b.sstart = p.sstart; b.slen = p.slen;
     b.P = p.P; b.pr = p.pr;
-    b.d = a.d; b.xd = a.xd;
+    b.d = a.d; b.xd = a.xd; b.xd_idx = a.xd_idx;
     b.alpha = a.alpha; b.beta = a.beta;
     b.y = a.y; b.dot = a.dot; b.w = a.w; b.parts = a.parts;
     b.st = a.loop.st;
     b.strict = a.pb_strict;
     const size_t lds = sizeof(double) * ((size_t)p.NW * p.SR + 2 * (size_t)p.NW);
-#define CM_P2D(NWV, LPSV, DV)                                                                             \
-    do {                                                                                                  \
-        CM_TRY(set_max_lds((const void *)k_pb_phase2<NWV, LPSV, DV>));                                   \
-        hipLaunchKernelGGL((k_pb_phase2<NWV, LPSV, DV>), dim3(p.NRB), dim3(64 * NWV), lds, st, b);       \
+    // The instantiations with the map exist for the depths a plan gets by its shape, 4 and 16 (pb_build_alloc); a depth of 8 comes
+    // from the option PB_DEPTH alone and runs them with 4: the depth is the number of loads in flight, the products of a row are
+    // added in the same order at every depth.
+    const bool idx = b.d && b.xd_idx;
+#define CM_P2D(NWV, LPSV, DV, IDXV)                                                                               \
+    do {                                                                                                          \
+        CM_TRY(set_max_lds((const void *)k_pb_phase2<NWV, LPSV, DV, IDXV>));                                     \
+        hipLaunchKernelGGL((k_pb_phase2<NWV, LPSV, DV, IDXV>), dim3(p.NRB), dim3(64 * NWV), lds, st, b);         \
     } while (0)
 #define CM_P2(NWV, LPSV)                                                                                  \
     do {                                                                                                  \
-        if (p.depth >= 16) CM_P2D(NWV, LPSV, 16);                                                         \
-        else if (p.depth >= 8) CM_P2D(NWV, LPSV, 8);                                                      \
-        else CM_P2D(NWV, LPSV, 4);                                                                        \
+        if (idx && p.depth >= 16) CM_P2D(NWV, LPSV, 16, true);                                            \
+        else if (idx) CM_P2D(NWV, LPSV, 4, true);                                                         \
+        else if (p.depth >= 16) CM_P2D(NWV, LPSV, 16, false);                                             \
+        else if (p.depth >= 8) CM_P2D(NWV, LPSV, 8, false);                                               \
+        else CM_P2D(NWV, LPSV, 4, false);                                                                 \
     } while (0)
 #define CM_P2_LPS(NWV)                                           \
     do {                                                         \

@@ -85,3 +85,17 @@ bool bicgstab_lu_precond(int n, int nnz, double *A, int *iA, int *jA, double *b,
     return run(n, nnz, A, iA, jA, nullptr, nullptr, b, CUDAMAT_PRECOND_ILU0, CUDAMAT_LOOP_PBICGSTAB, maxit, tol, debug, x,
                dtAlg, true);
 }
+
+bool bicgstab_lu_precond(int n, int nnz, double *A0, int *iA0, int *jA0, double *d, double *x0, double *b, int maxit,
+                         double tol, bool debug, double *x, double *dtAlg)
+{
+    // not in the reference: ILU(0) of A0 + diag(d), then the same loop with that shift
+    if (g_gpus > 1) {
+        std::fprintf(stderr, "!!!! cudamat: ILU(0) of the shifted matrix is one-GPU only (cudamat_use_gpus(%d) is set; "
+                             "block-Jacobi takes no shift)\n", g_gpus);
+        if (dtAlg) *dtAlg = 0.0;
+        return false;
+    }
+    return run(n, nnz, A0, iA0, jA0, d, x0, b, CUDAMAT_PRECOND_ILU0, CUDAMAT_LOOP_PBICGSTAB, maxit, tol, debug, x, dtAlg,
+               true);
+}

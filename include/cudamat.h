@@ -282,11 +282,21 @@ int cudamat_solver_create_host(cudamat_ctx *ctx, int n_local, int64_t n_cols, in
                                int base, cudamat_solver **out);
 int cudamat_solver_destroy(cudamat_solver *s);
 /* (A0 + diag(d)) variant, pbicgstab.h:116; d is a device vector of n_local doubles
- * that must stay alive; NULL removes it.                                             */
+ * that must stay alive; NULL removes it.  A solver with a shift takes CUDAMAT_PRECOND_ILU0 only with factors built by
+ * cudamat_solver_ilu0_shift (loops CUDAMAT_LOOP_PBICGSTAB / _PBICGSTAB2; any other combination is CUDAMAT_ERR_ARG): the
+ * factors of A0 alone are never used, or built, silently in their place.  The shift of the factors and this one are
+ * independent: factors built with one d may precondition a solve with another (a weaker, still valid M).           */
 int cudamat_solver_set_shift(cudamat_solver *s, const double *d);
 /* ILU(0) of the local block sharing A's pattern + level analysis of L and U
- * (pbicgstab.cu:336-359).  Single rank only.                                          */
+ * (pbicgstab.cu:336-359).  Single rank only.  A second call (of this or of _ilu0_shift) starts the set-up over.  */
 int cudamat_solver_ilu0(cudamat_solver *s);
+/* The same for A0 + diag(d_factor): d_factor (device, n_local doubles) is added to the copied diagonal values, one rounding
+ * each, before the factorisation; it is read during the call only and has nothing to do with set_shift.  An explicit zero
+ * on A0's diagonal is fine when the shifted pivot is not zero; a diagonal entry missing from the pattern stays an error.
+ * NULL: cudamat_solver_ilu0.  Single GPU, whole matrix only (no block-Jacobi or sharded variant).                    */
+int cudamat_solver_ilu0_shift(cudamat_solver *s, const double *d_factor);
+/* *yes = 1 when the solver's factors came from cudamat_solver_ilu0_shift with a non-NULL d_factor, else 0            */
+int cudamat_solver_ilu0_shifted(cudamat_solver *s, int *yes);
 /* the same on the rank's DIAGONAL BLOCK (rows and columns it owns) -- allowed in a sharded solver;
  * no collective is involved, neither here nor in the preconditioning steps            */
 int cudamat_solver_block_ilu0(cudamat_solver *s);

@@ -132,6 +132,17 @@ bool bicgstab_lu_precond(int n, int nnz,
                          int maxit, double tol, bool debug,
                          double OUT(*x), double OUT(*dtAlg));
 
+/* EXTENSION of this library (the reference has no such overload): (A0 + I*d) x = b from the initial guess x0 with the
+ * ILU(0) preconditioner of the shifted matrix A0 + diag(d).  Every diagonal entry of A0 must be stored (an explicit zero
+ * is fine) and every shifted pivot must be non-zero.  A repeated call with the same matrix reuses the factors only when d
+ * is byte-identical to the one they were built from.  Single GPU only: after cudamat_use_gpus(k > 1) the call returns false
+ * with a message (block-Jacobi, which stands in for ILU(0) there, takes no shift). */
+bool bicgstab_lu_precond(int n, int nnz,
+                         double IN(*A0), int IN(*iA0), int IN(*jA0),
+                         double IN(*d), double IN(*x0), double IN(*b),
+                         int maxit, double tol, bool debug,
+                         double OUT(*x), double OUT(*dtAlg));
+
 /* statistics of the last solve issued by the calling thread */
 const cudamat_stats *cudamat_last_stats();
 
