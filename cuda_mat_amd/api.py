@@ -419,6 +419,18 @@ class Solver:
         check(_lib.lib().cudamat_solver_ilu0_shifted(self.h, C.byref(y)))
         return bool(y.value)
 
+    def ilu0_refactor(self, shift=None):
+        """numeric-only refactorisation (cudamat_solver_ilu0_refactor): the values of the factors the solver holds become those of
+        A0 + diag(shift) (a device vector of n doubles, read during the call only; None: of A0); the level analysis, the split,
+        the maps and the permuted matrix are kept.  Bit-identical to a fresh ilu0(shift)."""
+        check(_lib.lib().cudamat_solver_ilu0_refactor(self.h, None if shift is None else _ptr(shift)))
+
+    def ilu0_refactor_info(self):
+        """(refactorisations since the set-up of the current factors, wall seconds of the last one, device bytes of the value maps)"""
+        cnt, sec, nb = C.c_int(), C.c_double(), C.c_size_t()
+        check(_lib.lib().cudamat_solver_ilu0_refactor_info(self.h, C.byref(cnt), C.byref(sec), C.byref(nb)))
+        return cnt.value, sec.value, nb.value
+
     def trsv_form(self):
         """1: dependency-driven triangular solves, 0: one launch per level"""
         f = C.c_int()

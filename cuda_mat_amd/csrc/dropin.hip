@@ -558,7 +558,10 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
                 have = hflag == 0;
             }
             if (!have) {
-                if ((rc = ilu0_setup(s, false, d_factor, true))) break;
+                // a kept solver with whole-matrix factors of another d (or of none): only the numbers change -- the level
+                // analysis, the split and the permuted copy stay (option ILU0_REFACTOR = 0: the whole set-up again)
+                const bool numbers_only = reused && s->has_ilu && !s->ilu_block && !s->sharded && ctx->cfg.ilu0_refactor;
+                if ((rc = numbers_only ? ilu0_refactor(s, d_factor, true) : ilu0_setup(s, false, d_factor, true))) break;
                 built_ilu = true;
             }
         }

@@ -70,6 +70,19 @@ struct IluPlans {
     // matrix, solver.hip ensure_perm_matrix), scratch vectors of the original-space wrapper (precond_apply_any)
     cm::DevBuf<int> posU;
     cm::DevBuf<double> perm_a, perm_b;
+    // numeric-only refactorisation (ilu0_refactor): where in `lu` every stored value of a SPLIT factor comes from, one int per
+    // entry -- the near parts in their own order, the far plans' pv in (column block, row block, row, column) order up to
+    // cstart[NCB] (-1: an alignment pad, which stays 0.0).  Built at the first refactor, nothing before; unsplit factors
+    // need none (k_fill_factor over the kept row pointers is their refresh).
+    struct FactorSrc {
+        cm::DevBuf<int> near;
+        std::vector<cm::DevBuf<int>> far;           // far[g] beside TriHost::far[g] (empty where that plan is)
+        std::vector<int64_t> far_len;
+    } srcL, srcU;
+    bool src_built = false;
+    size_t src_bytes = 0;
+    int refactors = 0;                              // since the set-up of the current factors
+    double refactor_seconds = 0.0;                  // wall time of the last one, stream drained
     ~IluPlans();                                    // flushes `deferred` (ilu.hip)
 };
 

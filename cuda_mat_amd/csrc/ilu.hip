@@ -20,6 +20,7 @@
 //                       levels -- the reference form the others are bit-identical to, and the fallback when a
 //                       dependency-driven solve times out (another spinning kernel on the same GPU).
 // Block-Jacobi (row-sharded runs): the same machinery on the rank's diagonal block (select_precond_matrix).
+// A new shift on a kept solver: ilu0_refactor recomputes the numbers only (ilu0_numeric + the value refresh, end of this file).
 // Algorithmic bytes per preconditioner application: 12 nnz + 8 (n+1) + 32 n.
 #include <algorithm>
 #include <vector>
@@ -921,59 +922,96 @@ int launch_sort_rows(hipStream_t st, int nrows, const int *src_rp, const int *sr
     return CUDAMAT_OK;
 }
 
+// the groups as ranges of level-major positions (rows are stored level by level)
+static int group_cuts(const TriFactor &F, const TriHost &H, GroupCuts *gc)
+{
+    const int K = (int)H.grp_level.size() - 1;
+    if (K > 128) { set_error("factor split: more than 128 groups"); return CUDAMAT_ERR_ARG; }
+    *gc = GroupCuts{};
+    gc->K = K;
+    for (int g = 0; g <= K; g++) gc->start[g] = F.level_ptr[(size_t)H.grp_level[(size_t)g]];
+    return CUDAMAT_OK;
+}
+
+// a whole level-major factor (frp / fci / fval, fnnz entries) cut into its near and its far entries
+struct SplitParts {
+    DevBuf<int> nrp, qrp, nci, qci;
+    DevBuf<double> nval, qval;
+    std::vector<int> far_at;               // K + 1: the far part's row pointer at the group boundaries
+    int64_t nnz_near = 0, nnz_far = 0;
+};
+
+static int split_entries(cudamat_solver *s, const TriFactor &F, const TriHost &H, const int *frp, const int *fci, const double *fval,
+                         int64_t fnnz, const int *pos, SplitParts *sp)
+{
+    hipStream_t st = s->ctx->stream;
+    const int n = s->n;
+    const int K = (int)H.grp_level.size() - 1;
+    double t_stamp = now_s();
+    GroupCuts gc{};
+    CM_TRY(group_cuts(F, H, &gc));
+    DevBuf<int> d_cn, d_cf, ci_new;
+    CM_TRY(d_cn.alloc((size_t)n));
+    CM_TRY(d_cf.alloc((size_t)n));
+    CM_TRY(ci_new.alloc((size_t)(fnnz > 0 ? fnnz : 1)));
+    constexpr int kSplitWaves = 4;
+    const unsigned grid = (unsigned)((n + kSplitWaves - 1) / kSplitWaves);
+    hipLaunchKernelGGL(k_split_count<kSplitWaves>, dim3(grid), dim3(64 * kSplitWaves), 0, st, n, frp, fci, pos, gc, ci_new, d_cn, d_cf);
+    // row pointers of the near and the far part: prefix sums on the device; the host needs the two totals and the far
+    // pointer at the group boundaries only
+    CM_TRY(sp->nrp.alloc((size_t)n + 1));
+    CM_TRY(sp->qrp.alloc((size_t)n + 1));
+    CM_TRY(device_exclusive_scan(st, n, d_cn, sp->nrp));
+    CM_TRY(device_exclusive_scan(st, n, d_cf, sp->qrp));
+    int tot_near = 0, tot_far = 0;
+    sp->far_at.assign((size_t)K + 1, 0);
+    bool copied = hipMemcpy(&tot_near, sp->nrp + n, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess &&
+                  hipMemcpy(&tot_far, sp->qrp + n, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+    for (int g = 0; g <= K && copied; g++)
+        copied = hipMemcpy(&sp->far_at[(size_t)g], sp->qrp + F.level_ptr[(size_t)H.grp_level[(size_t)g]], sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+    if (!copied) { set_error("factor split scan failed"); return CUDAMAT_ERR_HIP; }
+    sp->nnz_near = tot_near;
+    sp->nnz_far = tot_far;
+    CM_STAMP("split count + device scan");
+    CM_TRY(sp->nci.alloc((size_t)sp->nnz_near));
+    CM_TRY(sp->nval.alloc((size_t)sp->nnz_near));
+    CM_TRY(sp->qci.alloc((size_t)sp->nnz_far));
+    CM_TRY(sp->qval.alloc((size_t)sp->nnz_far));
+    // (far rows come out in increasing level-major column order, as the blocked builder needs them)
+    hipLaunchKernelGGL(k_split_fill<kSplitWaves>, dim3(grid), dim3(64 * kSplitWaves), 0, st, n, frp, ci_new, fval, gc, sp->nrp, sp->nci,
+                       sp->nval, sp->qrp, sp->qci, sp->qval);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { set_error("factor split failed"); return CUDAMAT_ERR_HIP; }
+    CM_STAMP("split fill (far rows sorted)");
+    return CUDAMAT_OK;
+}
+
+// One blocked SpMV plan per group: rows of the group (level-major, contiguous) x the columns of the EARLIER groups -- in
+// level-major space those are the positions [0, r0), so only that prefix of `out` is tiled.  *use = false: the group has no
+// far part (the first group, an empty one).
+static int far_plan_build(cudamat_solver *s, const Config &cfg, const TriFactor &F, const TriHost &H, const SplitParts &sp, int g, PbPlan *out,
+                          bool *use)
+{
+    const int r0 = F.level_ptr[(size_t)H.grp_level[(size_t)g]], r1 = F.level_ptr[(size_t)H.grp_level[(size_t)g + 1]];
+    const int64_t cnt = (int64_t)sp.far_at[(size_t)g + 1] - sp.far_at[(size_t)g];
+    *use = g >= 1 && r1 > r0 && cnt > 0;
+    if (!*use) return CUDAMAT_OK;
+    return pb_build(s->ctx->stream, cfg, r1 - r0, r0, cnt, sp.qrp + r0, sp.qci, sp.qval, out);
+}
+
 // the split itself; on failure F is intact and split_factor takes back what H holds of it
 static int split_factor_build(cudamat_solver *s, TriFactor &F, TriHost &H, const int *pos)
 {
     hipStream_t st = s->ctx->stream;
     const int n = s->n;
     const int K = (int)H.grp_level.size() - 1;
+    SplitParts sp;
+    CM_TRY(split_entries(s, F, H, F.rp, F.ci, F.val, F.nnz, pos, &sp));
     double t_stamp = now_s();
-    // the groups as ranges of level-major positions (rows are stored level by level)
-    GroupCuts gc{};
-    if (K > 128) { set_error("factor split: more than 128 groups"); return CUDAMAT_ERR_ARG; }
-    gc.K = K;
-    for (int g = 0; g <= K; g++) gc.start[g] = F.level_ptr[(size_t)H.grp_level[(size_t)g]];
-    DevBuf<int> d_cn, d_cf, nrp, qrp, nci, qci, ci_new;
-    DevBuf<double> nval, qval;
-    CM_TRY(d_cn.alloc((size_t)n));
-    CM_TRY(d_cf.alloc((size_t)n));
-    CM_TRY(ci_new.alloc((size_t)(F.nnz > 0 ? F.nnz : 1)));
-    constexpr int kSplitWaves = 4;
-    const unsigned grid = (unsigned)((n + kSplitWaves - 1) / kSplitWaves);
-    hipLaunchKernelGGL(k_split_count<kSplitWaves>, dim3(grid), dim3(64 * kSplitWaves), 0, st, n, F.rp, F.ci, pos, gc, ci_new, d_cn, d_cf);
-    // row pointers of the near and the far part: prefix sums on the device; the host needs the two totals and the far
-    // pointer at the group boundaries only
-    CM_TRY(nrp.alloc((size_t)n + 1));
-    CM_TRY(qrp.alloc((size_t)n + 1));
-    CM_TRY(device_exclusive_scan(st, n, d_cn, nrp));
-    CM_TRY(device_exclusive_scan(st, n, d_cf, qrp));
-    int tot_near = 0, tot_far = 0;
-    std::vector<int> hf_grp((size_t)K + 1, 0);
-    bool copied = hipMemcpy(&tot_near, nrp + n, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess &&
-                  hipMemcpy(&tot_far, qrp + n, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
-    for (int g = 0; g <= K && copied; g++)
-        copied = hipMemcpy(&hf_grp[(size_t)g], qrp + F.level_ptr[(size_t)H.grp_level[(size_t)g]], sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
-    if (!copied) { set_error("factor split scan failed"); return CUDAMAT_ERR_HIP; }
-    const int64_t nnz_near = tot_near, nnz_far = tot_far;
-    CM_STAMP("split count + device scan");
-    CM_TRY(nci.alloc((size_t)nnz_near));
-    CM_TRY(nval.alloc((size_t)nnz_near));
-    CM_TRY(qci.alloc((size_t)nnz_far));
-    CM_TRY(qval.alloc((size_t)nnz_far));
-    // (far rows come out in increasing level-major column order, as the blocked builder needs them)
-    hipLaunchKernelGGL(k_split_fill<kSplitWaves>, dim3(grid), dim3(64 * kSplitWaves), 0, st, n, F.rp, ci_new, F.val, gc, nrp, nci,
-                       nval, qrp, qci, qval);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { set_error("factor split failed"); return CUDAMAT_ERR_HIP; }
-    CM_STAMP("split fill (far rows sorted)");
-    // one blocked SpMV plan per group: rows of the group (level-major, contiguous) x the columns of the EARLIER
-    // groups -- in level-major space those are the positions [0, r0), so only that prefix of `out` is tiled
     H.far.assign((size_t)K, PbPlan());
     int rc = CUDAMAT_OK;
     for (int g = 1; g < K && !rc; g++) {
-        const int r0 = F.level_ptr[(size_t)H.grp_level[(size_t)g]], r1 = F.level_ptr[(size_t)H.grp_level[(size_t)g + 1]];
-        const int64_t cnt = (int64_t)hf_grp[(size_t)g + 1] - hf_grp[(size_t)g];
-        if (r1 <= r0 || cnt <= 0) continue;
-        rc = pb_build(st, s->ctx->cfg, r1 - r0, r0, cnt, qrp + r0, qci, qval, &H.far[(size_t)g]);
+        bool use = false;
+        rc = far_plan_build(s, s->ctx->cfg, F, H, sp, g, &H.far[(size_t)g], &use);
     }
     CM_STAMP("far plans (pb_build)");
     CM_TRY(rc);
@@ -981,10 +1019,10 @@ static int split_factor_build(cudamat_solver *s, TriFactor &F, TriHost &H, const
     CM_HIP(hipMemsetAsync(H.far_buf, 0, sizeof(double) * (size_t)n, st));
     // the level kernels keep only the near entries: the whole factor's arrays are released here, now that the far plans
     // are built, not earlier
-    F.rp = std::move(nrp);
-    F.ci = std::move(nci);
-    F.val = std::move(nval);
-    F.nnz = nnz_near;
+    F.rp = std::move(sp.nrp);
+    F.ci = std::move(sp.nci);
+    F.val = std::move(sp.nval);
+    F.nnz = sp.nnz_near;
     H.lanes = pick_lanes(n ? (double)F.nnz / n : 1.0);
     return CUDAMAT_OK;
 }
@@ -1244,17 +1282,17 @@ int ilu0_setup(cudamat_solver *s, bool block, const double *d_factor, bool keep_
     return CUDAMAT_OK;
 }
 
-static int ilu0_setup_body(cudamat_solver *s, IluPlans *pl, const double *d_factor, bool keep_shift)
+// The NUMBERS of the factorisation: lu = the matrix's values (+ d_factor on the diagonal), eliminated level by level.  Needs the
+// analysis (diag_pos, L's levels, the longest row) and two ints of device scratch; shared by the set-up and by ilu0_refactor,
+// which therefore run the same kernels in the same launch shapes.
+static int ilu0_numeric(cudamat_solver *s, int *d_flags, int maxrow_all, const double *d_factor, bool keep_shift)
 {
     hipStream_t st = s->ctx->stream;
     const int n = s->n;
-    int *const d_flags = pl->d_flags;
-    const int maxrow_all = pl->maxrow_all;
     int hflags[2] = {0, 0};
     // ---- factorisation on a copy of A's values (pbicgstab.cu:316, :356-363)
-    const double t1 = now_s();
-    double t_stamp = t1;
-    CM_TRY(s->lu.alloc((size_t)s->pm_nnz));
+    double t_stamp = now_s();
+    if (!s->lu) CM_TRY(s->lu.alloc((size_t)s->pm_nnz));
     if (hipMemcpyAsync(s->lu, s->pm_val, sizeof(double) * (size_t)s->pm_nnz, hipMemcpyDeviceToDevice, st) != hipSuccess) {
         set_error("copy of A values failed");
         return CUDAMAT_ERR_HIP;
@@ -1264,11 +1302,13 @@ static int ilu0_setup_body(cudamat_solver *s, IluPlans *pl, const double *d_fact
         if (hipGetLastError() != hipSuccess) { set_error("diagonal shift launch failed"); return CUDAMAT_ERR_HIP; }
     }
     if (d_factor && n && keep_shift) {      // (the drop-in call compares the next call's d with this copy: dropin.hip)
-        CM_TRY(s->ilu_d.alloc((size_t)n));
+        if (!s->ilu_d) CM_TRY(s->ilu_d.alloc((size_t)n));
         if (hipMemcpyAsync(s->ilu_d, d_factor, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st) != hipSuccess) {
             set_error("copy of the factor shift failed");
             return CUDAMAT_ERR_HIP;
         }
+    } else {
+        s->ilu_d.reset();                   // (a refactorisation without a kept shift: the copy of the previous one goes)
     }
     const int maxrow = maxrow_all;
     const int cap = ((maxrow + 63) / 64) * 64 + 64;
@@ -1304,6 +1344,16 @@ static int ilu0_setup_body(cudamat_solver *s, IluPlans *pl, const double *d_fact
         return CUDAMAT_ERR_ZERO_PIVOT;
     }
     CM_STAMP("numeric ILU(0)");
+    return CUDAMAT_OK;
+}
+
+static int ilu0_setup_body(cudamat_solver *s, IluPlans *pl, const double *d_factor, bool keep_shift)
+{
+    hipStream_t st = s->ctx->stream;
+    const int n = s->n;
+    const double t1 = now_s();
+    CM_TRY(ilu0_numeric(s, pl->d_flags, pl->maxrow_all, d_factor, keep_shift));
+    double t_stamp = now_s();
     CM_TRY(fill_factor(s, false, s->L));
     CM_TRY(fill_factor(s, true, s->U));
     if (hipStreamSynchronize(st) != hipSuccess) { set_error("factor fill failed"); return CUDAMAT_ERR_HIP; }
@@ -1460,7 +1510,258 @@ int ilu_perm_matrix(cudamat_solver *s)
     return CUDAMAT_OK;
 }
 
+// ---------------------------------------------------------------- numeric-only refactorisation (cudamat_solver_ilu0_refactor)
+// The factors of A0 + diag(d') on the structure the solver already holds: lu is recomputed by ilu0_numeric, then every stored
+// copy of its values is refreshed in place -- unsplit factors by k_fill_factor over the kept row pointers, split ones by the
+// two kernels below through a map "stored entry -> position in lu" (IluPlans::FactorSrc), built once.
+//
+// The refresh streams over DESTINATION order: 4 bytes of map and 8 bytes of store per entry are sequential, the 8-byte read of
+// lu is the one gather.  For the near parts the map is increasing inside a row and the rows of a level are increasing, so the
+// gather walks lu nearly in order; for a far plan it follows the plan's (column block, row block, row, column) order, i.e. it
+// revisits a sub-block's rows once per column block.  Algorithmic bytes per entry: 4 + 8 + 8 = 20.
+template <int VEC>
+__global__ __launch_bounds__(kBlock) void k_refresh_values(int64_t count, const int *src, const double *lu, double *val)
+{
+    vec_loop<VEC>(count, [&](int64_t i, auto w) {
+        constexpr int W = decltype(w)::value;
+        int at[W];
+        double v[W];
+        if constexpr (W == 2) {
+            const int2 q = ((const int2 *)src)[i];
+            at[0] = q.x;
+            at[1] = q.y;
+        } else {
+            at[0] = src[i];
+        }
+#pragma unroll
+        for (int j = 0; j < W; j++) v[j] = at[j] >= 0 ? lu[at[j]] : 0.0;        // (-1: an alignment pad of a blocked copy)
+        store_row<W>(val, i, v, kAll);
+    });
+}
+
+static int launch_refresh_values(hipStream_t s, int64_t count, const int *src, const double *lu, double *val)
+{
+    if (count <= 0) return CUDAMAT_OK;
+    CM_VEC_LAUNCH(all_aligned16(val) && (((uintptr_t)src) & 7) == 0, vec_grid(count), k_refresh_values<VEC>, count, src, lu, val);
+}
+
+// dinv[pr] = 1 / (U's diagonal of the row at position pr): the expression of k_fill_factor, one division, one rounding
+__global__ __launch_bounds__(kBlock) void k_refresh_dinv(int64_t n, const int *row_of, const int *diag_pos, const double *lu, double *dinv)
+{
+#pragma clang fp contract(off)
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t pr = (int64_t)blockIdx.x * kBlock + threadIdx.x; pr < n; pr += stride) dinv[pr] = 1.0 / lu[diag_pos[row_of[pr]]];
+}
+
+// the map of one array filled from a value array that held every entry's (position in lu) + 1 as a double (exact: < 2^31):
+// 0.0 is an alignment pad -> -1
+__global__ __launch_bounds__(kBlock) void k_src_from_tags(int64_t count, const double *tag, int *src)
+{
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) src[i] = (int)tag[i] - 1;
+}
+
+__global__ __launch_bounds__(kBlock) void k_tags(int64_t count, double *tag)
+{
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) tag[i] = (double)(i + 1);
+}
+
+// The maps of one split factor.  No second builder: the pipeline of the set-up (k_fill_factor -> split_entries -> pb_build per
+// group) runs once more on the tags instead of the values -- where an entry lands depends on the pattern alone -- and the
+// positions are read out of what it leaves.  The far plans built here are temporaries; each is checked against the shape of
+// the plan it mirrors (the PB_* switches may have changed since the set-up).
+static int refactor_maps_of(cudamat_solver *s, bool upper, const TriFactor &F, const TriHost &H, const int *pos, const double *tags,
+                            IluPlans::FactorSrc *out, size_t *bytes)
+{
+    hipStream_t st = s->ctx->stream;
+    const int n = s->n;
+    const int K = (int)H.grp_level.size() - 1;
+    // the whole factor in level-major order, as fill_factor left it before the split: row pointers, columns, tags
+    DevBuf<int> frp, fci, d_len;
+    DevBuf<double> fval, dinv_unused;
+    CM_TRY(frp.alloc((size_t)n + 1));
+    CM_TRY(d_len.alloc((size_t)n));
+    const unsigned gp = (unsigned)(((long long)n + kBlock - 1) / kBlock), gp8 = (unsigned)(((long long)n * 8 + kBlock - 1) / kBlock);      // (one thread per row / 8 lanes per row, as the set-up launches them)
+    if (n) hipLaunchKernelGGL(k_factor_len, dim3(gp), dim3(kBlock), 0, st, n, F.row_of, s->pm_rp, s->diag_pos, upper ? 1 : 0, d_len);
+    CM_HIP(hipGetLastError());
+    CM_TRY(device_exclusive_scan(st, n, d_len, frp));
+    int fnnz = 0;
+    CM_HIP(hipMemcpy(&fnnz, frp + n, sizeof(int), hipMemcpyDeviceToHost));
+    CM_TRY(fci.alloc((size_t)fnnz));
+    CM_TRY(fval.alloc((size_t)fnnz));
+    if (upper) CM_TRY(dinv_unused.alloc((size_t)n));
+    if (n) hipLaunchKernelGGL(k_fill_factor, dim3(gp8), dim3(kBlock), 0, st, n, s->pm_rp, s->pm_ci, tags, s->diag_pos, upper ? 1 : 0,
+                       F.row_of, frp, fci, fval, dinv_unused);
+    CM_HIP(hipGetLastError());
+    SplitParts sp;
+    CM_TRY(split_entries(s, F, H, frp, fci, fval, fnnz, pos, &sp));
+    if (sp.nnz_near != F.nnz) { set_error("ILU(0) refactor: the near part has %lld entries, the factor holds %lld", (long long)sp.nnz_near, (long long)F.nnz); return CUDAMAT_ERR_HIP; }
+    fci.reset();
+    fval.reset();
+    CM_TRY(out->near.alloc((size_t)sp.nnz_near));
+    if (sp.nnz_near) hipLaunchKernelGGL(k_src_from_tags, dim3(row_grid(sp.nnz_near)), dim3(kBlock), 0, st, sp.nnz_near, sp.nval, out->near);
+    CM_HIP(hipGetLastError());
+    *bytes += sizeof(int) * (size_t)sp.nnz_near;
+    out->far.clear();
+    out->far.resize((size_t)K);
+    out->far_len.assign((size_t)K, 0);
+    Config cfg = s->ctx->cfg;
+    cfg.pb_place = 0;                       // a temporary: nothing to place, nothing to print
+    cfg.verbose = 0;
+    for (int g = 1; g < K; g++) {
+        const PbPlan &have = H.far[(size_t)g];
+        PbPlan tmp;
+        bool use = false;
+        CM_TRY(far_plan_build(s, cfg, F, H, sp, g, &tmp, &use));
+        if (!use) {
+            if (have.pv) { set_error("ILU(0) refactor: group %d has a far plan and no far entries", g); return CUDAMAT_ERR_HIP; }
+            continue;
+        }
+        int total = -1;
+        const bool same = have.pv && tmp.pv && have.n == tmp.n && have.n_cols == tmp.n_cols && have.nnz == tmp.nnz && have.NCB == tmp.NCB &&
+                          have.CB == tmp.CB && have.NSUB == tmp.NSUB && have.SR == tmp.SR && have.NW == tmp.NW;
+        int rc = same ? CUDAMAT_OK : CUDAMAT_ERR_ARG;
+        if (!same) set_error("ILU(0) refactor: the blocked-copy switches (PB_*) differ from those of the set-up; run cudamat_solver_ilu0[_shift] again");
+        if (!rc) rc = CM_RC(hipMemcpy(&total, tmp.cstart + tmp.NCB, sizeof(int), hipMemcpyDeviceToHost));
+        if (!rc) rc = out->far[(size_t)g].alloc((size_t)total);
+        if (!rc && total > 0) {
+            hipLaunchKernelGGL(k_src_from_tags, dim3(row_grid(total)), dim3(kBlock), 0, st, (int64_t)total, tmp.pv, out->far[(size_t)g]);
+            rc = CM_RC(hipGetLastError());
+            if (!rc) rc = CM_RC(hipStreamSynchronize(st));
+        }
+        pb_free(&tmp);
+        CM_TRY(rc);
+        out->far_len[(size_t)g] = total;
+        *bytes += sizeof(int) * (size_t)total;
+    }
+    CM_HIP(hipStreamSynchronize(st));
+    return CUDAMAT_OK;
+}
+
+static int refactor_maps(cudamat_solver *s, IluPlans *pl)
+{
+    hipStream_t st = s->ctx->stream;
+    const int n = s->n;
+    double t_stamp = now_s();
+    DevBuf<int> posL, posU;
+    DevBuf<double> tags;
+    CM_TRY(posL.alloc((size_t)n));
+    CM_TRY(posU.alloc((size_t)n));
+    CM_TRY(tags.alloc((size_t)s->pm_nnz));
+    const unsigned gp = (unsigned)(((long long)n + kBlock - 1) / kBlock);
+    if (n) hipLaunchKernelGGL(k_invert_perm, dim3(gp), dim3(kBlock), 0, st, n, s->L.row_of, posL);
+    if (n) hipLaunchKernelGGL(k_invert_perm, dim3(gp), dim3(kBlock), 0, st, n, s->U.row_of, posU);
+    hipLaunchKernelGGL(k_tags, dim3(row_grid(s->pm_nnz)), dim3(kBlock), 0, st, (int64_t)s->pm_nnz, tags);
+    CM_HIP(hipGetLastError());
+    size_t bytes = 0;
+    int rc = refactor_maps_of(s, false, s->L, pl->L, posL, tags, &pl->srcL, &bytes);
+    if (!rc) rc = refactor_maps_of(s, true, s->U, pl->U, posU, tags, &pl->srcU, &bytes);
+    if (rc) {       // nothing half built stays
+        pl->srcL = IluPlans::FactorSrc();
+        pl->srcU = IluPlans::FactorSrc();
+        return rc;
+    }
+    pl->src_built = true;
+    pl->src_bytes = bytes;
+    CM_STAMP("value maps (built once)");
+    return CUDAMAT_OK;
+}
+
+// every stored value of one split factor from lu
+static int refresh_split_factor(cudamat_solver *s, bool upper, TriFactor &F, TriHost &H, const IluPlans::FactorSrc &src)
+{
+    hipStream_t st = s->ctx->stream;
+    CM_TRY(launch_refresh_values(st, F.nnz, src.near, s->lu, F.val));
+    for (size_t g = 0; g < H.far.size(); g++)
+        if (H.far[g].pv) CM_TRY(launch_refresh_values(st, src.far_len[g], src.far[g], s->lu, H.far[g].pv));
+    if (upper && s->n) {
+        hipLaunchKernelGGL(k_refresh_dinv, dim3(row_grid(s->n)), dim3(kBlock), 0, st, (int64_t)s->n, F.row_of, s->diag_pos, s->lu, F.dinv);
+        CM_HIP(hipGetLastError());
+    }
+    return CUDAMAT_OK;
+}
+
+int ilu0_refactor(cudamat_solver *s, const double *d_factor, bool keep_shift)
+{
+    CM_ARG(s->has_ilu, "ILU(0) refactor: the solver has no factors (call cudamat_solver_ilu0 or _ilu0_shift first)");
+    CM_ARG(!s->sharded, "ILU(0) refactor: a sharded solver's factors are not refactored (single GPU, whole matrix only)");
+    CM_ARG(!s->ilu_block, "ILU(0) refactor: block-Jacobi factors are not refactored (single GPU, whole matrix only)");
+    IluPlans *pl = plans_of(s, false);
+    CM_ARG(pl, "ILU(0) refactor: the solver has no factors (call cudamat_solver_ilu0 or _ilu0_shift first)");
+    CM_HIP(hipSetDevice(s->ctx->device));
+    Range range_ilu("cudamat: ILU(0) numeric refactorisation");
+    hipStream_t st = s->ctx->stream;
+    const int n = s->n;
+    CM_HIP(hipStreamSynchronize(st));
+    const double t0 = now_s();
+    double t_stamp = t0;
+    const bool split = s->L.lm && s->U.lm;
+    const bool first = split && !pl->src_built;
+    // what may fail for want of memory comes first: the factors are intact until the numbers change
+    if (first) CM_TRY(refactor_maps(s, pl));
+    if (!pl->d_flags) CM_TRY(pl->d_flags.alloc(5));
+    if (split && d_factor && !s->xd_idx && n) {
+        // the shift term of the loop in level-major spaces (ilu0_setup_body builds this map for shifted factors only)
+        DevBuf<int> posU;
+        const unsigned gp = (unsigned)(((long long)n + kBlock - 1) / kBlock);
+        const int *pu = pl->posU;
+        if (!pu) {      // (released once the permuted matrix was built)
+            CM_TRY(posU.alloc((size_t)n));
+            hipLaunchKernelGGL(k_invert_perm, dim3(gp), dim3(kBlock), 0, st, n, s->U.row_of, posU);
+            pu = posU;
+        }
+        CM_TRY(s->xd_idx.alloc((size_t)n));
+        hipLaunchKernelGGL(k_compose_perm, dim3(gp), dim3(kBlock), 0, st, n, s->L.row_of, pu, s->xd_idx);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+            s->xd_idx.reset();
+            set_error("permutation maps failed");
+            return CUDAMAT_ERR_HIP;
+        }
+    }
+    auto numbers = [&]() -> int {
+        CM_TRY(ilu0_numeric(s, pl->d_flags, pl->maxrow_all, d_factor, keep_shift));
+        t_stamp = now_s();                  // (ilu0_numeric stamps its own part and ends drained)
+        if (split) {
+            CM_TRY(refresh_split_factor(s, false, s->L, pl->L, pl->srcL));
+            CM_TRY(refresh_split_factor(s, true, s->U, pl->U, pl->srcU));
+        } else {
+            CM_TRY(fill_factor(s, false, s->L));
+            CM_TRY(fill_factor(s, true, s->U));
+        }
+        if (hipStreamSynchronize(st) != hipSuccess) { set_error("factor refresh failed"); return CUDAMAT_ERR_HIP; }
+        CM_STAMP("value refresh");
+        return CUDAMAT_OK;
+    };
+    const int rc = numbers();
+    if (rc) return ilu0_fail(s, rc);        // (a zero pivot, as after a failed set-up: no factors)
+    s->ilu_shifted = d_factor != nullptr;
+    pl->refactors++;
+    pl->refactor_seconds = now_s() - t0;
+    s->t_factor = pl->refactor_seconds;     // (cudamat_stats.t_factor of the next solve: what these factors cost)
+    if (s->ctx->cfg.verbose)
+        fprintf(stderr, "[cudamat] ilu0 refactor (numbers only%s) %8.3f ms\n", first ? "; value maps built" : "", pl->refactor_seconds * 1e3);
+    return CUDAMAT_OK;
+}
+
 }  // namespace cm
+
+extern "C" int cudamat_solver_ilu0_refactor(cudamat_solver *s, const double *d_factor)
+{
+    CM_ARG(s, "ILU(0) refactor: solver is NULL");
+    return ilu0_refactor(s, d_factor);
+}
+
+extern "C" int cudamat_solver_ilu0_refactor_info(cudamat_solver *s, int *count, double *seconds_last, size_t *map_bytes)
+{
+    CM_ARG(s, "ILU(0) refactor info: solver is NULL");
+    const IluPlans *pl = s->has_ilu ? plans_of(s, false) : nullptr;
+    if (count) *count = pl ? pl->refactors : 0;
+    if (seconds_last) *seconds_last = pl ? pl->refactor_seconds : 0.0;
+    if (map_bytes) *map_bytes = pl ? pl->src_bytes : 0;
+    return CUDAMAT_OK;
+}
+
 
 extern "C" int cudamat_solver_ilu0(cudamat_solver *s)
 {

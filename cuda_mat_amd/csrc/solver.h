@@ -213,6 +213,9 @@ int launch_sort_rows(hipStream_t st, int nrows, const int *src_rp, const int *sr
 // d_factor (device, n doubles, read during the call only): factor A0 + diag(d_factor); single GPU, whole matrix.
 // keep_shift: the solver keeps a copy of it (ilu_d: the drop-in call's cache asks whether the next call's d is the same)
 int ilu0_setup(cudamat_solver *s, bool block, const double *d_factor = nullptr, bool keep_shift = false);
+// the numbers of the factors the solver holds become those of A0 + diag(d_factor) (nullptr: of A0); everything that depends on
+// the pattern alone stays (cudamat_solver_ilu0_refactor).  A zero pivot leaves the solver without factors, as a failed set-up does.
+int ilu0_refactor(cudamat_solver *s, const double *d_factor, bool keep_shift = false);
 // the pattern-only part of ilu0_setup (diagonal positions, level analysis of L and U), kept for the ilu0_setup that follows
 int ilu0_analyse_early(cudamat_solver *s);
 void ilu0_flush_deferred(cudamat_solver *s);

@@ -95,6 +95,28 @@ static void check_owned()
         EXPECT(frees == 6 && a.get() == nullptr);  // reset() twice frees once
     }
     EXPECT(frees == 6);
+    {
+        // the shape of the refactorisation's value maps (csrc/ilu.h, IluPlans::FactorSrc): one owner and a vector of owners
+        // inside a struct that is resized, filled with gaps, rebuilt, and dropped by assigning an empty one
+        struct Maps {
+            IntBuf near;
+            std::vector<IntBuf> far;
+        } m;
+        m.near.adopt(block());
+        m.far.resize(5);                           // (groups without a far part stay empty)
+        for (size_t g = 1; g < m.far.size(); g += 2) m.far[g].adopt(block());
+        EXPECT(frees == 6 && !m.far[0] && m.far[1].get() != nullptr && m.far[3].get() != nullptr);
+        m.far.clear();
+        EXPECT(frees == 8);                        // clear() frees what the elements held
+        m.far.resize(9);                           // (reallocation moves owners, it never copies or frees them)
+        m.far[8].adopt(block());
+        m.far.resize(64);
+        EXPECT(frees == 8 && m.far[8].get() != nullptr);
+        m = Maps();                                // a failed build leaves nothing half built
+        EXPECT(frees == 10 && !m.near && m.far.empty());
+        m.near.adopt(block());
+    }
+    EXPECT(frees == 11);
 }
 
 int main(int argc, char **argv)

@@ -288,15 +288,30 @@ int cudamat_solver_destroy(cudamat_solver *s);
  * independent: factors built with one d may precondition a solve with another (a weaker, still valid M).           */
 int cudamat_solver_set_shift(cudamat_solver *s, const double *d);
 /* ILU(0) of the local block sharing A's pattern + level analysis of L and U
- * (pbicgstab.cu:336-359).  Single rank only.  A second call (of this or of _ilu0_shift) starts the set-up over.  */
+ * (pbicgstab.cu:336-359).  Single rank only.  A second call (of this or of _ilu0_shift) starts the set-up over;
+ * cudamat_solver_ilu0_refactor keeps it and recomputes the values only.                                            */
 int cudamat_solver_ilu0(cudamat_solver *s);
 /* The same for A0 + diag(d_factor): d_factor (device, n_local doubles) is added to the copied diagonal values, one rounding
  * each, before the factorisation; it is read during the call only and has nothing to do with set_shift.  An explicit zero
  * on A0's diagonal is fine when the shifted pivot is not zero; a diagonal entry missing from the pattern stays an error.
  * NULL: cudamat_solver_ilu0.  Single GPU, whole matrix only (no block-Jacobi or sharded variant).                    */
 int cudamat_solver_ilu0_shift(cudamat_solver *s, const double *d_factor);
-/* *yes = 1 when the solver's factors came from cudamat_solver_ilu0_shift with a non-NULL d_factor, else 0            */
+/* *yes = 1 when the solver's factors came from cudamat_solver_ilu0_shift with a non-NULL d_factor, else 0 (after a
+ * refactorisation: whether the last one had a non-NULL d_factor)                                                       */
 int cudamat_solver_ilu0_shifted(cudamat_solver *s, int *yes);
+/* Numeric-only refactorisation: the VALUES of the factors the solver holds become those of A0 + diag(d_factor) (device,
+ * n_local doubles, read during the call only; NULL: those of A0).  Everything that depends on the pattern alone is kept --
+ * the level analysis, the far / near split and its blocked copies' structure, the permutation maps, the chosen solve forms
+ * and, when already built, the permuted copy of the matrix -- so the result is bit-identical to a fresh
+ * cudamat_solver_ilu0_shift(d_factor) on the same matrix and switches, at a fraction of its cost.  Any transition is allowed
+ * (A0 -> d, d -> d', d -> A0, A0 -> A0).  Split factors keep one int per stored entry from the first call on (see
+ * _refactor_info); unsplit ones need nothing.  CUDAMAT_ERR_ARG: no factors yet, block-Jacobi factors, a sharded solver.
+ * CUDAMAT_ERR_ZERO_PIVOT leaves the solver without factors, as a failed set-up does.                                   */
+int cudamat_solver_ilu0_refactor(cudamat_solver *s, const double *d_factor);
+/* Without touching the device: *count = refactorisations the current factors have seen since their set-up, *seconds_last =
+ * wall time of the last one (stream drained), *map_bytes = device bytes of the value maps (0 before the first
+ * refactorisation and for unsplit factors).  Any of the three may be NULL.                                             */
+int cudamat_solver_ilu0_refactor_info(cudamat_solver *s, int *count, double *seconds_last, size_t *map_bytes);
 /* the same on the rank's DIAGONAL BLOCK (rows and columns it owns) -- allowed in a sharded solver;
  * no collective is involved, neither here nor in the preconditioning steps            */
 int cudamat_solver_block_ilu0(cudamat_solver *s);
