@@ -5,5 +5,5 @@ from ._lib import (FLAG_DEBUG, FLAG_GUARD, FLAG_NO_EXIT, FLAG_PROFILE, FLAG_X0_O
                    LOOP_PBICGSTAB2, LOOP_PIPELINED, PRECOND_BLOCK_ILU0, PRECOND_ILU0, PRECOND_NONE, Comm, CudamatError, Stats, build,
                    device_count, lib)
 from .api import (Context, DeviceArray, Solver, Timer, bicgstab, bicgstab_d,  # noqa: F401
-                  bicgstab_d_lu_precond, bicgstab_d_many, bicgstab_lu_precond, bicgstab_lu_precond_many, bicgstab_many,
+                  bicgstab_d_lu_precond, bicgstab_d_lu_precond_many, bicgstab_d_many, bicgstab_lu_precond, bicgstab_lu_precond_many, bicgstab_many,
                   loadMMSparseMatrix, toDenseVector, use_gpus)

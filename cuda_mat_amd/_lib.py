@@ -143,6 +143,12 @@ _SIGS = {
                                               C.c_double, C.c_int, _P, C.POINTER(C.c_int)]),
     "cudamat_solve_shifts": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int,
                                        C.c_int, C.c_int, C.c_double, _P, C.POINTER(C.c_int)]),
+    "cudamat_solver_solve_shifts_ilu0": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                   _P, C.POINTER(C.c_int)]),
+    "cudamat_solver_precond_apply_shifts": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int]),
+    "cudamat_solver_ilu0_shifts_values": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int64]),
+    "cudamat_solve_shifts_ilu0": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int,
+                                            C.c_int, C.c_double, _P, C.POINTER(C.c_int)]),
     "cudamat_solve": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int,
                                 C.c_double, C.c_int, _P, C.POINTER(Stats)]),
     "cudamat_plan_cache_clear": (C.c_int, []),

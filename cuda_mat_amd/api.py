@@ -8,6 +8,8 @@ Names and argument meaning follow pbicgstab.h / mmio_wrapper.h of the reference:
   bicgstab_many(n, nnz, A, iA, jA, B, maxit, tol, d, x0)             bicgstab / bicgstab_d for the columns of B (new)
   bicgstab_lu_precond_many(n, nnz, A, iA, jA, B, maxit, tol)         bicgstab_lu_precond for the columns of B (new)
   bicgstab_d_many(n, nnz, A0, iA0, jA0, D, x0, B, maxit, tol)        bicgstab_d with shift D[:, j] for column j of B (new)
+  bicgstab_d_lu_precond_many(n, nnz, A0, iA0, jA0, D, x0, B, maxit, tol)   bicgstab_d_lu_precond with shift D[:, j], and the
+                                                                     ILU(0) of A0 + diag(D[:, j]), for column j of B (new)
   loadMMSparseMatrix(filename, elem_type, csrFormat)                 mmio_wrapper.h:133
   toDenseVector(n, nnz, A, IA)                                       pbicgstab.cu:1101
 Each solver returns (ok, x, dtAlg, stats): `ok` is the reference's bool, x the
@@ -124,6 +126,16 @@ def bicgstab_many(n, nnz, A, iA, jA, B, maxit, tol, d=None, x0=None):
     return [bool(s.converged) for s in stats], np.ascontiguousarray(X), (stats[0].t_solve if k else 0.0), stats, form.value
 
 
+def _shift_block(D, n, k):
+    """D as an (n, k) block: given as one, or as k scalars sigma_j meaning d_j = sigma_j * 1"""
+    D = np.asarray(D, dtype=np.float64)
+    if D.ndim == 1 and D.shape[0] == k:
+        D = np.broadcast_to(D[None, :], (n, k))
+    if D.shape != (n, k):
+        raise ValueError("D must have shape (n, k) = (%d, %d), or hold k scalars; got %s" % (n, k, D.shape))
+    return D
+
+
 def bicgstab_d_many(n, nnz, A0, iA0, jA0, D, x0, B, maxit, tol):
     """bicgstab_d for a family of shifted systems (A0 + I*d_j) x_j = b_j in one call (cudamat_solve_shifts): the matrix is
     shared, column j of B is solved with the shift D[:, j].  D: shape (n, k), or k scalars sigma_j meaning d_j = sigma_j * 1
@@ -137,12 +149,7 @@ def bicgstab_d_many(n, nnz, A0, iA0, jA0, D, x0, B, maxit, tol):
     if len(iA0) != n + 1 or len(A0) < nnz or len(jA0) < nnz or B.ndim != 2 or B.shape[0] != n:
         raise ValueError("array sizes do not match n / nnz")
     k = B.shape[1]
-    D = np.asarray(D, dtype=np.float64)
-    if D.ndim == 1 and D.shape[0] == k:
-        D = np.broadcast_to(D[None, :], (n, k))
-    if D.shape != (n, k):
-        raise ValueError("D must have shape (n, k) = (%d, %d), or hold k scalars; got %s" % (n, k, D.shape))
-    Df, Bf = np.asfortranarray(D), np.asfortranarray(B)
+    Df, Bf = np.asfortranarray(_shift_block(D, n, k)), np.asfortranarray(B)
     x0f = None
     if x0 is not None:
         x0f = np.asarray(x0, dtype=np.float64)
@@ -156,6 +163,36 @@ def bicgstab_d_many(n, nnz, A0, iA0, jA0, D, x0, B, maxit, tol):
                                           LOOP_PBICGSTAB2, maxit, tol, st, C.byref(form)))
     stats = [st[j] for j in range(k)]
     return [bool(s.converged) for s in stats], np.ascontiguousarray(X), (stats[0].t_solve if k else 0.0), stats, form.value
+
+
+def bicgstab_d_lu_precond_many(n, nnz, A0, iA0, jA0, D, x0, B, maxit, tol):
+    """bicgstab_d_lu_precond for a family of shifted systems (A0 + I*d_j) x_j = b_j in one call (cudamat_solve_shifts_ilu0):
+    column j of B is solved with the shift D[:, j] and preconditioned with the ILU(0) of A0 + diag(D[:, j]) -- one set of
+    factors per column.  D: shape (n, k), or k scalars, as in bicgstab_d_many; x0: shape (n, k), or None for ones.  The loop is
+    LOOP_PBICGSTAB; the columns run one factorisation and one solve each unless CUDAMAT_MANY_PRECOND = batched | auto sends
+    them through the K-wide factorisation and the multi-column triangular solves.  The plan cache compares the matrix, not
+    the shifts.  Returns (ok, X, dtAlg, stats, form) as bicgstab_lu_precond_many does: ok[j] True whenever the solve ran."""
+    A0, iA0, jA0 = _np(A0, np.float64), _np(iA0, np.int32), _np(jA0, np.int32)
+    B = np.asarray(B, dtype=np.float64)
+    if B.ndim == 1:
+        B = B[:, None]
+    if len(iA0) != n + 1 or len(A0) < nnz or len(jA0) < nnz or B.ndim != 2 or B.shape[0] != n:
+        raise ValueError("array sizes do not match n / nnz")
+    k = B.shape[1]
+    Df, Bf = np.asfortranarray(_shift_block(D, n, k)), np.asfortranarray(B)
+    x0f = None
+    if x0 is not None:
+        x0f = np.asarray(x0, dtype=np.float64)
+        if x0f.size != n * k:
+            raise ValueError("x0 must have shape (n, k)")
+        x0f = np.asfortranarray(x0f.reshape(n, k))
+    X = np.zeros((n, k), order="F")
+    st = (Stats * max(k, 1))()
+    form = C.c_int(0)
+    check(_lib.lib().cudamat_solve_shifts_ilu0(n, nnz, _vp(A0), _vp(iA0), _vp(jA0), k, _vp(Df), n, _vp(Bf), n, _vp(x0f), _vp(X), n,
+                                               maxit, tol, st, C.byref(form)))
+    stats = [st[j] for j in range(k)]
+    return [True] * k, np.ascontiguousarray(X), (stats[0].t_solve if k else 0.0), stats, form.value
 
 
 def bicgstab_lu_precond_many(n, nnz, A, iA, jA, B, maxit, tol):
@@ -541,3 +578,32 @@ class Solver:
         check(_lib.lib().cudamat_solver_solve_shifts(self.h, int(nrhs), _ptr(D), int(ldd), _ptr(B), int(ldb), _ptr(X), int(ldx),
                                                      precond, loop, maxit, tol, flags, st, C.byref(form)))
         return [st[j] for j in range(int(nrhs))], form.value
+
+    def solve_shifts_ilu0(self, nrhs, D, ldd, B, ldb, X, ldx, maxit=2000, tol=1e-8, flags=0):
+        """(A0 + diag D_j) x_j = b_j with the ILU(0) of A0 + diag D_j as column j's preconditioner (the reference loop; one set
+        of factors per column, K-wide under MANY_PRECOND = batched | auto): returns (list of Stats, form)"""
+        st = (Stats * max(int(nrhs), 1))()
+        form = C.c_int(0)
+        check(_lib.lib().cudamat_solver_solve_shifts_ilu0(self.h, int(nrhs), _ptr(D), int(ldd), _ptr(B), int(ldb), _ptr(X), int(ldx),
+                                                          maxit, tol, flags, st, C.byref(form)))
+        return [st[j] for j in range(int(nrhs))], form.value
+
+    def precond_apply_shifts(self, nrhs, D, ldd, In, ldin, Out, ldout):
+        """Out_j = U_j^-1 L_j^-1 In_j with the factors of A0 + diag D_j: column j is bit-identical to precond_apply after
+        ilu0(shift=D_j)"""
+        check(_lib.lib().cudamat_solver_precond_apply_shifts(self.h, int(nrhs), _ptr(D), int(ldd), _ptr(In), int(ldin), _ptr(Out),
+                                                             int(ldout)))
+
+    def ilu0_shifts_values(self, nrhs, D, ldd):
+        """array of shape (entries of the factors, nrhs): column j is what ilu0_values() returns after ilu0(shift=D_j)"""
+        nrhs = int(nrhs)
+        if nrhs == 0:
+            return np.zeros((0, 0))
+        cnt = C.c_int64(self.nnz)       # one GPU, whole matrix: the factors share the matrix's pattern
+        ld = max(cnt.value, 1)
+        out = self.ctx.empty(ld * nrhs)
+        try:
+            check(_lib.lib().cudamat_solver_ilu0_shifts_values(self.h, nrhs, _ptr(D), int(ldd), out.ptr, ld))
+            return out.download().reshape(nrhs, ld)[:, :cnt.value].T.copy()
+        finally:
+            out.free()

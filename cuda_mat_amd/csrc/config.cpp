@@ -85,7 +85,7 @@ const Option kOptions[] = {
     OPT_ENUM("MANY_FORM", many_form, "auto=0,batched=1,columns=2",
              "several right-hand sides: batched (one SpMM per step for up to 8 columns) / columns (one solve per column); auto: the faster as timed at the first solve"),
     OPT_ENUM("MANY_PRECOND", many_precond, "columns=0,auto=1,batched=2",
-             "several right-hand sides with ILU(0): columns (one preconditioned solve per column, default) / batched (multi-column triangular solves and one SpMM per step for up to 8 columns, where the factors are covered) / auto: the faster as timed at the first such solve; MANY_FORM = columns overrides"),
+             "several right-hand sides with ILU(0): columns (one preconditioned solve per column, default) / batched (multi-column triangular solves and one SpMM per step for up to 8 columns, where the factors are covered) / auto: the faster as timed at the first such solve; MANY_FORM = columns overrides.  Governs cudamat_solver_solve_shifts_ilu0 (one set of ILU(0) factors per column) the same way: columns = one factorisation and one solve per column, batched = the K-wide factorisation and triangular solves with per-column values, auto = both timed with their factorisations"),
     {"TEST_COMM_FAIL", K_FAIL, nullptr, nullptr, 0, 0, nullptr, "rank:k -- fault injection: that rank's k-th all-reduce reports an error (tests)"},
 };
 

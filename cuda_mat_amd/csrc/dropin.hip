@@ -540,7 +540,9 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
         if (g_cache.d_d && !reused) { cudamat_free(ctx, g_cache.d_d); g_cache.d_d = nullptr; }
         // (per-column shifts travel with the call: the solver itself keeps none, and the block goes when the call returns)
         if ((rc = cudamat_solver_set_shift(s, h.shifts ? nullptr : d_d))) break;
-        if (precond != CUDAMAT_PRECOND_NONE) {
+        // (per-column shifts with ILU(0): every column gets its own factors inside cudamat_solver_solve_shifts_ilu0)
+        const bool per_column_factors = many && h.shifts && precond == CUDAMAT_PRECOND_ILU0;
+        if (precond != CUDAMAT_PRECOND_NONE && !per_column_factors) {
             // one solve of (A0 + I d) with ILU(0): the factors are those of A0 + diag(d).  The cache compares the matrix, not the
             // shift, so kept factors serve only a d that is byte-identical to the one they were built from (the solver's copy);
             // otherwise the factorisation is redone and the rest of the plan stays.  (The batched calls keep their refusals.)
@@ -570,7 +572,10 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
             printf("csrilu0 (HIP, level-scheduled) time(s) = %10.8f \n", s->t_factor);            // :355,363
         }
         int flags = (debug ? CUDAMAT_FLAG_DEBUG : 0) | (h.x0 ? 0 : CUDAMAT_FLAG_X0_ONES);
-        if (many) {
+        if (per_column_factors) {
+            if ((rc = cudamat_solver_solve_shifts_ilu0(s, h.nrhs, d_d, n, d_b, n, d_x, n, maxit, tol, flags, out, form))) break;
+            st = out[0];
+        } else if (many) {
             if ((rc = cudamat_solver_solve_shifts(s, h.nrhs, h.shifts ? d_d : nullptr, n, d_b, n, d_x, n, precond, loop, maxit, tol,
                                                   flags, out, form))) break;
             st = out[0];
@@ -728,6 +733,14 @@ extern "C" int cudamat_solve_shifts(int n, int nnz, const double *A0, const int 
 {
     return solve_many_host(n, nnz, A0, iA0, jA0, D, ldd, true, nrhs, B, ldb, x0, X, ldx, CUDAMAT_PRECOND_NONE, loop, maxit, tol, out,
                            form);
+}
+
+extern "C" int cudamat_solve_shifts_ilu0(int n, int nnz, const double *A0, const int *iA0, const int *jA0, int nrhs, const double *D,
+                                         int ldd, const double *B, int ldb, const double *x0, double *X, int ldx, int maxit, double tol,
+                                         cudamat_stats *out, int *form)
+{
+    return solve_many_host(n, nnz, A0, iA0, jA0, D, ldd, true, nrhs, B, ldb, x0, X, ldx, CUDAMAT_PRECOND_ILU0, CUDAMAT_LOOP_PBICGSTAB,
+                           maxit, tol, out, form);
 }
 
 // cudamat_solver_create from HOST arrays: the same staged creation, run beside the upload (what cudamat_solve does for its

@@ -21,12 +21,15 @@
 //                       dependency-driven solve times out (another spinning kernel on the same GPU).
 // Block-Jacobi (row-sharded runs): the same machinery on the rank's diagonal block (select_precond_matrix).
 // A new shift on a kept solver: ilu0_refactor recomputes the numbers only (ilu0_numeric + the value refresh, end of this file).
+// K shifted matrices at once (cudamat_solver_solve_shifts_ilu0): ilu0_numeric_cols -- k_ilu0_init_cols, k_ilu0_level_cols<K, WAVES>,
+// k_fill_factor_cols -- factors A0 + diag(D_c), c < K, in one pass over the shared pattern, values interleaved.
 // Algorithmic bytes per preconditioner application: 12 nnz + 8 (n+1) + 32 n.
 #include <algorithm>
 #include <vector>
 
 #include "device.h"
 #include "ilu.h"
+#include "trsm.h"
 
 using namespace cm;
 
@@ -348,6 +351,195 @@ __global__ __launch_bounds__(64 * WAVES) void k_ilu0_level_fast(int row_begin, i
     for (int q = lane; q < len; q += 64) lu[rs + q] = sv[q];
 }
 
+// ---------------------------------------------------------------- K-wide numeric ILU(0): A0 + diag(D_c), c < K, in one pass
+// The K matrices share the pattern, so the column ids, the pivots' positions and every binary search are shared; only the values
+// differ.  Values are interleaved as the vectors of batch.h are: lu[p*K + c].  One wave per row of the level, as above; the
+// row's K value columns are staged in LDS (sv[q*K + c]), its column ids and the per-pivot tables (position of the pivot's
+// diagonal, end of the pivot's row) once.  Per pivot-row entry a lane does ONE binary search and then K updates.  Per entry
+// and column the operations are those of k_ilu0_level / k_ilu0_level_fast in the same order -- lik = sv / piv, then for every
+// pivot at most one sv -= lik * u, written as there so that it contracts as there -- hence column c carries the bits of the
+// single-column factorisation of A0 + diag(D_c).  As in the fast kernel the entries and the pivot of pivot row kk + 1 are in
+// flight while pivot kk is applied (they belong to earlier levels and are final).
+// LDS per wave: cap * (8 K + 12) bytes (trsm.h: ilu0_cols_waves).  zp: the smallest (column << 32 | row) with a zero pivot.
+template <int K, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_ilu0_level_cols(int row_begin, int row_end, const int *row_of, const int *rp,
+                                                               const int *ci, const int *diag_pos, double *lu, int cap,
+                                                               unsigned long long *zp)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int pr = row_begin + blockIdx.x * WAVES + wave;
+    if (pr >= row_end) return;
+    double *sv = smem + (size_t)wave * cap * K;
+    int *sc = (int *)(smem + (size_t)WAVES * cap * K) + (size_t)wave * cap * 3;
+    int *mk = sc + cap;
+    int *me = mk + cap;
+    const int i = row_of[pr];
+    const int rs = rp[i], len = rp[i + 1] - rs;
+    const int nlow = diag_pos[i] - rs;
+    for (int q = lane; q < len; q += 64) {
+        double v[K];
+        load_row<K>(lu, rs + q, v);
+        store_row<K>(sv, q, v, kAll);
+        sc[q] = ci[rs + q];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int q = lane; q < nlow; q += 64) {
+        const int k = sc[q];
+        mk[q] = diag_pos[k];
+        me[q] = rp[k + 1];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    bool have = false;
+    int j = 0;
+    double u[K], piv[K];
+#pragma unroll
+    for (int c = 0; c < K; c++) u[c] = piv[c] = 0.0;
+    if (nlow > 0) {
+        const int pp = mk[0] + 1 + lane;
+        have = pp < me[0];
+        if (have) {
+            j = ci[pp];
+            load_row<K>(lu, pp, u);
+        }
+        load_row<K>(lu, mk[0], piv);
+    }
+    for (int kk = 0; kk < nlow; kk++) {
+        const int dk = mk[kk], ke = me[kk];
+        bool have_n = false;
+        int jn = 0;
+        double un[K], pivn[K];
+#pragma unroll
+        for (int c = 0; c < K; c++) un[c] = pivn[c] = 0.0;
+        if (kk + 1 < nlow) {
+            const int ppn = mk[kk + 1] + 1 + lane;
+            have_n = ppn < me[kk + 1];
+            if (have_n) {
+                jn = ci[ppn];
+                load_row<K>(lu, ppn, un);
+            }
+            load_row<K>(lu, mk[kk + 1], pivn);
+        }
+        double lik[K];
+        load_row<K>(sv, kk, lik);                        // every lane reads the same LDS words
+#pragma unroll
+        for (int c = 0; c < K; c++) {
+            if (piv[c] == 0.0 && lane == 0) atomicMin(zp, ((unsigned long long)c << 32) | (unsigned)sc[kk]);
+            lik[c] = lik[c] / piv[c];
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (lane == 0) store_row<K>(sv, kk, lik, kAll);
+        if (have) {
+            int lo = kk + 1, hi = len;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (sc[mid] < j) lo = mid + 1; else hi = mid;
+            }
+            if (lo < len && sc[lo] == j) {
+                double t[K];
+                load_row<K>(sv, lo, t);
+#pragma unroll
+                for (int c = 0; c < K; c++) t[c] -= lik[c] * u[c];
+                store_row<K>(sv, lo, t, kAll);
+            }
+        }
+        for (int pp = dk + 1 + 64 + lane; pp < ke; pp += 64) {       // pivot rows with more than 64 upper entries
+            const int j2 = ci[pp];
+            int lo = kk + 1, hi = len;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (sc[mid] < j2) lo = mid + 1; else hi = mid;
+            }
+            if (lo < len && sc[lo] == j2) {
+                double t[K], u2[K];
+                load_row<K>(lu, pp, u2);
+                load_row<K>(sv, lo, t);
+#pragma unroll
+                for (int c = 0; c < K; c++) t[c] -= lik[c] * u2[c];
+                store_row<K>(sv, lo, t, kAll);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        have = have_n;
+        j = jn;
+#pragma unroll
+        for (int c = 0; c < K; c++) {
+            u[c] = un[c];
+            piv[c] = pivn[c];
+        }
+    }
+    if (nlow >= 0 && lane == 0) {                        // zero pivot of row i
+        double dv[K];
+        load_row<K>(sv, nlow, dv);
+#pragma unroll
+        for (int c = 0; c < K; c++)
+            if (dv[c] == 0.0) atomicMin(zp, ((unsigned long long)c << 32) | (unsigned)i);
+    }
+    for (int q = lane; q < len; q += 64) {
+        double v[K];
+        load_row<K>(sv, q, v);
+        store_row<K>(lu, rs + q, v, kAll);
+    }
+}
+
+// lu[p*K + c] = A0's value p, plus D_c[i] on the diagonal of row i: the copy and k_shift_diag in one kernel -- one plain add
+// per diagonal entry and column, one rounding (contraction is off and there is no product to contract with).  8 lanes per row.
+// Padding columns (c >= kc) take the last real column's shift: they can never report a pivot no real column has.
+template <int K>
+__global__ __launch_bounds__(kBlock) void k_ilu0_init_cols(int n, const int *rp, const int *diag_pos, const double *val,
+                                                          const double *D, int64_t ldd, int kc, double *lu)
+{
+#pragma clang fp contract(off)
+    constexpr int L = 8;
+    const int lane = threadIdx.x & (L - 1);
+    const long long row = ((long long)blockIdx.x * kBlock + threadIdx.x) / L;
+    if (row >= n) return;
+    const int i = (int)row;
+    const int dp = diag_pos[i];
+    for (int p = rp[i] + lane; p < rp[i + 1]; p += L) {
+        const double a = val[p];
+        double v[K];
+#pragma unroll
+        for (int c = 0; c < K; c++) v[c] = a;
+        if (p == dp) {
+#pragma unroll
+            for (int c = 0; c < K; c++) v[c] = a + D[(size_t)(c < kc ? c : kc - 1) * (size_t)ldd + (size_t)i];
+        }
+        store_row<K>(lu, p, v, kAll);
+    }
+}
+
+// k_fill_factor's job for K value columns: one triangular part of lu into level-major order, fval[(o + k)*K + c], and
+// dinv[pr*K + c] = 1 / U's diagonal (the expression of k_fill_factor: one division, one rounding).  The pattern side (frp,
+// row_of; the column ids are not written again) is the solver's own.
+template <int K>
+__global__ __launch_bounds__(kBlock) void k_fill_factor_cols(int n, const int *rp, const double *lu, const int *diag_pos, int upper,
+                                                            const int *row_of, const int *frp, double *fval, double *dinv)
+{
+    constexpr int L = 8;
+    const int lane = threadIdx.x & (L - 1);
+    const long long pr = ((long long)blockIdx.x * kBlock + threadIdx.x) / L;
+    if (pr >= n) return;
+    const int r = row_of[pr];
+    const int s = upper ? diag_pos[r] + 1 : rp[r];
+    const int e = upper ? rp[r + 1] : diag_pos[r];
+    const int o = frp[pr];
+    for (int k = lane; k < e - s; k += L) {
+        double v[K];
+        load_row<K>(lu, s + k, v);
+        store_row<K>(fval, o + k, v, kAll);
+    }
+    if (upper && lane == 0) {
+        double v[K];
+        load_row<K>(lu, diag_pos[r], v);
+#pragma unroll
+        for (int c = 0; c < K; c++) v[c] = 1.0 / v[c];
+        store_row<K>(dinv, pr, v, kAll);
+    }
+}
 
 }  // namespace cm
 
@@ -1344,6 +1536,83 @@ static int ilu0_numeric(cudamat_solver *s, int *d_flags, int maxrow_all, const d
         return CUDAMAT_ERR_ZERO_PIVOT;
     }
     CM_STAMP("numeric ILU(0)");
+    return CUDAMAT_OK;
+}
+
+// ---- the K-wide form of the same (trsm.h): the factors of A0 + diag(D_c) for the K columns of one block, on the solver's
+// structure (diag_pos, L's levels, the factors' row pointers and row maps) and into the caller's buffers; nothing of the solver's
+// own factors is written
+bool ilu0_cols_covered(cudamat_solver *s, int K)
+{
+    IluPlans *pl = plans_of(s, false);
+    return pl && trsm_covered(s) && ilu0_cols_waves(K, pl->maxrow_all) >= 1;
+}
+
+template <int K>
+static int ilu0_numeric_cols_k(cudamat_solver *s, IluPlans *pl, int kc, const double *D, int64_t ldd, const ColFactors &f,
+                               unsigned long long *zp)
+{
+    hipStream_t st = s->ctx->stream;
+    const int n = s->n;
+    const unsigned grid8 = (unsigned)(((long long)n * 8 + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_ilu0_init_cols<K>, dim3(grid8), dim3(kBlock), 0, st, n, s->pm_rp, s->diag_pos, s->pm_val, D, ldd, kc, f.lu);
+    const int cap = ilu0_cols_cap(pl->maxrow_all);
+    const int waves = ilu0_cols_waves(K, pl->maxrow_all);
+    const size_t lds = (size_t)waves * (size_t)cap * (size_t)(8 * K + 12);
+    CM_TRY(set_max_lds((const void *)k_ilu0_level_cols<K, 1>));
+    CM_TRY(set_max_lds((const void *)k_ilu0_level_cols<K, 2>));
+    CM_TRY(set_max_lds((const void *)k_ilu0_level_cols<K, 4>));
+    for (int l = 0; l < s->L.nlevels; l++) {
+        const int r0 = s->L.level_ptr[(size_t)l], r1 = s->L.level_ptr[(size_t)l + 1];
+        const int rows = r1 - r0;
+        if (rows <= 0) continue;
+        if (waves == 4)
+            hipLaunchKernelGGL((k_ilu0_level_cols<K, 4>), dim3((rows + 3) / 4), dim3(256), lds, st, r0, r1, s->L.row_of, s->pm_rp, s->pm_ci,
+                               s->diag_pos, f.lu, cap, zp);
+        else if (waves == 2)
+            hipLaunchKernelGGL((k_ilu0_level_cols<K, 2>), dim3((rows + 1) / 2), dim3(128), lds, st, r0, r1, s->L.row_of, s->pm_rp, s->pm_ci,
+                               s->diag_pos, f.lu, cap, zp);
+        else
+            hipLaunchKernelGGL((k_ilu0_level_cols<K, 1>), dim3(rows), dim3(64), lds, st, r0, r1, s->L.row_of, s->pm_rp, s->pm_ci,
+                               s->diag_pos, f.lu, cap, zp);
+    }
+    hipLaunchKernelGGL(k_fill_factor_cols<K>, dim3(grid8), dim3(kBlock), 0, st, n, s->pm_rp, f.lu, s->diag_pos, 0, s->L.row_of, s->L.rp,
+                       f.lval, (double *)nullptr);
+    hipLaunchKernelGGL(k_fill_factor_cols<K>, dim3(grid8), dim3(kBlock), 0, st, n, s->pm_rp, f.lu, s->diag_pos, 1, s->U.row_of, s->U.rp,
+                       f.uval, f.dinv);
+    return CUDAMAT_OK;
+}
+
+int ilu0_numeric_cols(cudamat_solver *s, int K, int kc, const double *D, int64_t ldd, const ColFactors &f, unsigned long long *zp,
+                      int *zp_col, int *zp_row)
+{
+    IluPlans *pl = plans_of(s, false);
+    if (!pl || !ilu0_cols_covered(s, K) || kc < 1 || kc > K) {
+        set_error("K-wide ILU(0): structure missing, not covered, or a row beyond the %d entries a block of %d columns stages", ilu0_cols_max_row(K), K);
+        return CUDAMAT_ERR_ARG;
+    }
+    hipStream_t st = s->ctx->stream;
+    CM_HIP(hipMemsetAsync(zp, 0xFF, sizeof(unsigned long long), st));
+    int rc = CUDAMAT_ERR_ARG;
+    switch (K) {
+    case 1: rc = ilu0_numeric_cols_k<1>(s, pl, kc, D, ldd, f, zp); break;
+    case 2: rc = ilu0_numeric_cols_k<2>(s, pl, kc, D, ldd, f, zp); break;
+    case 4: rc = ilu0_numeric_cols_k<4>(s, pl, kc, D, ldd, f, zp); break;
+    case 8: rc = ilu0_numeric_cols_k<8>(s, pl, kc, D, ldd, f, zp); break;
+    default: set_error("K-wide ILU(0): %d columns per block", K);
+    }
+    CM_TRY(rc);
+    if (hipGetLastError() != hipSuccess) { set_error("K-wide ilu0 launch failed"); return CUDAMAT_ERR_HIP; }
+    unsigned long long h = 0;
+    if (hipMemcpyAsync(&h, zp, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        set_error("K-wide ilu0 failed");
+        return CUDAMAT_ERR_HIP;
+    }
+    if (h != ~0ULL) {
+        *zp_col = (int)(h >> 32);
+        *zp_row = (int)(h & 0xffffffffULL);
+        return CUDAMAT_ERR_ZERO_PIVOT;                 // (the caller words the message: it knows the block's first column)
+    }
     return CUDAMAT_OK;
 }
 

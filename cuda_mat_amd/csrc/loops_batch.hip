@@ -1,6 +1,7 @@
 // loops_batch.hip -- several right-hand sides for one resident matrix: cudamat_solver_spmm, cudamat_solver_precond_apply_many,
 // cudamat_solver_solve_many, cudamat_solver_history_col; and their forms with one shift vector per column,
-// (A0 + I d_j) x_j = b_j: cudamat_solver_spmm_shifts, cudamat_solver_solve_shifts.
+// (A0 + I d_j) x_j = b_j: cudamat_solver_spmm_shifts, cudamat_solver_solve_shifts; with one set of ILU(0) factors per column on
+// top: cudamat_solver_solve_shifts_ilu0, cudamat_solver_precond_apply_shifts, cudamat_solver_ilu0_shifts_values.
 //
 // Each column is an INDEPENDENT run of the reference loop (pbicgstab.cu:45-154; :581-754 for the (A0 + I d) variant) with its
 // own rho, alpha, omega, stopping tests, breakdown guard and history; nothing of one column enters another (this is not
@@ -27,10 +28,16 @@
 // every SpMM of the loop -- r0 = b - (A0 + I d_j) x0_j included -- adds dk_j .* x_j where it would add d .* x_j; the solver's own
 // shift is not read.  Column by column, the solver's shift points at column j of D for the length of that column's solve (a
 // caller's set_shift + solve, bit for bit) and is put back when the call returns, whatever it returns.
+// Per-column shifts WITH ILU(0) (cudamat_solver_solve_shifts_ilu0, end of this file): M_j = ILU(0)(A0 + diag d_j), one set of
+// factor values per column on the solver's shared structure.  Per block: the K-wide numeric factorisation (ilu.hip) into the
+// fourth buffer group (many.lu_b, lval_b, uval_b, dinv_b), then run_group with pc and shifts, whose two preconditioner
+// applications read those (precond_apply_cols, trsv.hip).  cudamat_solver_solve_shifts keeps its refusal of the pair.
 #include <math.h>
+#include <stdint.h>
 #include <string.h>
 
 #include "batch.h"
+#include "ilu.h"
 #include "solver.h"
 #include "trsm.h"
 
@@ -47,13 +54,17 @@ int64_t many_rows(const cudamat_solver *s)
     return rows > 0 ? rows : 1;
 }
 
-// The interleaved buffers come in three groups, each a list of (owner, doubles for K columns, zeroed at allocation?): the plain
+// The interleaved buffers come in four groups, each a list of (owner, doubles for K columns, zeroed at allocation?): the plain
 // loop's -- seven vectors (r, rw, p, v, t, b, x), the partial sums; the K loop states go with them --, the
 // three further blocks of the preconditioned loop: ph = M^-1 p, sh = M^-1 r and the scratch of L^-1; and the per-column
-// shifts' one block.
-enum Group { G_PLAIN = 0, G_PRECOND = 1, G_SHIFTS = 2 };
+// shifts' one block; and the per-column factors of one block (the K-wide LU values, L's and U's values in level-major order,
+// 1 / U's diagonal: sized by the solver's ILU(0) structure, which must exist).
+enum Group { G_PLAIN = 0, G_PRECOND = 1, G_SHIFTS = 2, G_FACTORS = 3 };
 
-int &group_cap(cudamat_solver *s, Group g) { return g == G_PRECOND ? s->many.pcap : g == G_SHIFTS ? s->many.dcap : s->many.cap; }
+int &group_cap(cudamat_solver *s, Group g)
+{
+    return g == G_PRECOND ? s->many.pcap : g == G_SHIFTS ? s->many.dcap : g == G_FACTORS ? s->many.fcap : s->many.cap;
+}
 
 struct Buf {
     DevBuf<double> *p;
@@ -66,6 +77,9 @@ std::vector<Buf> many_group(cudamat_solver *s, Group g, int K)
     ManyWork &m = s->many;
     const size_t nv = (size_t)K * (size_t)many_rows(s);
     if (g == G_SHIFTS) return {{&m.dk, nv, true}};
+    if (g == G_FACTORS)      // (every entry of every column, padding included, is written by each factorisation)
+        return {{&m.lu_b, (size_t)K * (size_t)s->pm_nnz, false}, {&m.lval_b, (size_t)K * (size_t)s->L.nnz, false},
+                {&m.uval_b, (size_t)K * (size_t)s->U.nnz, false}, {&m.dinv_b, (size_t)K * (size_t)s->n, false}};
     if (g == G_PRECOND) return {{&m.pw, nv, true}, {&m.s, nv, true}, {&m.lt, nv, true}};
     const size_t pv = 2 * (size_t)K * kVecGridMax, ps = 2 * (size_t)K * kSpmvGridMax;
     return {{&m.r, nv, true}, {&m.rw, nv, true}, {&m.p, nv, true}, {&m.v, nv, true}, {&m.t, nv, true}, {&m.b, nv, true},
@@ -77,6 +91,7 @@ void free_group(cudamat_solver *s, Group g)
 {
     for (const Buf &b : many_group(s, g, 0)) b.p->reset();
     if (g == G_PLAIN) s->many.st.reset();
+    if (g == G_FACTORS) s->many.fzp.reset();
     group_cap(s, g) = 0;
 }
 
@@ -90,6 +105,7 @@ void many_release(cudamat_solver *s)
     free_group(s, G_PLAIN);
     free_group(s, G_PRECOND);
     free_group(s, G_SHIFTS);
+    free_group(s, G_FACTORS);
     m.hist.reset();
     m.hist_bytes = 0;
 }
@@ -103,7 +119,10 @@ namespace {
 // one in place.  The stream is drained before anything is freed.
 int ensure_many(cudamat_solver *s, Group g, int K)
 {
-    if (group_cap(s, g) >= K) return CUDAMAT_OK;
+    ManyWork &mw = s->many;
+    // (the factor group is sized by the ILU(0) structure: another structure -- a set-up in between -- is another size)
+    const bool same_structure = mw.f_nnz == s->pm_nnz && mw.f_lnnz == s->L.nnz && mw.f_unnz == s->U.nnz;
+    if (group_cap(s, g) >= K && (g != G_FACTORS || same_structure)) return CUDAMAT_OK;
     hipStream_t st = s->ctx->stream;
     CM_HIP(hipStreamSynchronize(st));
     if (g != G_PLAIN) free_group(s, g);
@@ -114,24 +133,27 @@ int ensure_many(cudamat_solver *s, Group g, int K)
         if (b.zero && (rc = CM_RC(hipMemsetAsync(b.p->get(), 0, sizeof(double) * b.count, st)))) break;
     }
     if (!rc && g == G_PLAIN) rc = s->many.st.alloc((size_t)K);       // the K loop states
+    if (!rc && g == G_FACTORS) rc = s->many.fzp.alloc(1);            // the zero-pivot word
     if (rc) {
         CM_DROP(hipStreamSynchronize(st));
         free_group(s, g);
         return rc;
     }
     group_cap(s, g) = K;
+    if (g == G_FACTORS) { mw.f_nnz = s->pm_nnz; mw.f_lnnz = s->L.nnz; mw.f_unnz = s->U.nnz; }
     return CUDAMAT_OK;
 }
 
-// Is there room for the batched form of a call with nrhs columns (the plain group, with `precond` / `shifts` their groups too,
-// for its widest block)?  Buffers that do not fit are not an error of the call -- *room = false, it runs column by column --; any other
+// Is there room for the batched form of a call with nrhs columns (the plain group, with `precond` / `shifts` / `factors` their
+// groups too, for its widest block)?  Buffers that do not fit are not an error of the call -- *room = false, it runs column by column --; any other
 // failure is.
-int many_room(cudamat_solver *s, int nrhs, bool precond, bool shifts, bool *room)
+int many_room(cudamat_solver *s, int nrhs, bool precond, bool shifts, bool *room, bool factors = false)
 {
     const int K = pow2_cols(nrhs < kBatchMax ? nrhs : kBatchMax);
     int rc = ensure_many(s, G_PLAIN, K);
     if (rc == CUDAMAT_OK && precond) rc = ensure_many(s, G_PRECOND, K);
     if (rc == CUDAMAT_OK && shifts) rc = ensure_many(s, G_SHIFTS, K);
+    if (rc == CUDAMAT_OK && factors) rc = ensure_many(s, G_FACTORS, K);
     *room = rc == CUDAMAT_OK;
     return rc == CUDAMAT_ERR_NOMEM ? CUDAMAT_OK : rc;
 }
@@ -179,9 +201,10 @@ struct ShiftGuard {
 // precond: CUDAMAT_PRECOND_NONE, or CUDAMAT_PRECOND_ILU0 with covered factors (trsm_covered), the reference loop and
 // the preconditioned group allocated (many_room).  shifts: column j is (A0 + I d_j) x_j = b_j with the shifts of many.dk, filled
 // here from D (column-major, ldd) unless D == NULL (filled already); the shift group allocated (many_room).
+// cf (with precond and shifts): M_j is column j of these per-column factors (trsm.h), not the solver's own.
 int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, double *X, int64_t ldx, int precond, int loop,
               int maxit, double tol, int flags, LoopState *fin, std::vector<double> *hist_out, double *t_loop,
-              bool shifts = false, const double *D = nullptr, int64_t ldd = 0)
+              bool shifts = false, const double *D = nullptr, int64_t ldd = 0, const ColFactors *cf = nullptr)
 {
     ManyWork &m = s->many;
     const bool pc = precond != CUDAMAT_PRECOND_NONE;
@@ -227,7 +250,7 @@ int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, do
         CM_TRY(launch_update_p_b(st, K, la, m.parts_full, np_full, n, m.r, m.p, m.v));
         const double *pw = m.p;
         if (pc) {                                                                           // :92-98
-            CM_TRY(precond_apply_b(s, K, m.p, m.lt, m.pw));
+            CM_TRY(cf ? precond_apply_cols(s, K, *cf, m.p, m.lt, m.pw) : precond_apply_b(s, K, m.p, m.lt, m.pw));
             pw = m.pw;
         }
         // v = A pw, rw.v                                                                      :104-106
@@ -240,7 +263,7 @@ int run_group(cudamat_solver *s, int K, int kc, const double *B, int64_t ldb, do
         const double *sv = m.r;
         if (pc) {              // the tests are decided before M^-1 r is computed, as in Solve::iterate_reference
             CM_TRY(launch_check_half_b(st, K, la, m.parts_half, np_half));
-            CM_TRY(precond_apply_b(s, K, m.r, m.lt, m.s));
+            CM_TRY(cf ? precond_apply_cols(s, K, *cf, m.r, m.lt, m.s) : precond_apply_b(s, K, m.r, m.lt, m.s));
             sv = m.s;
         }
         SpmmArgs a2 = spmm_args(s, sv, m.t, dk);
@@ -497,6 +520,303 @@ extern "C" int cudamat_solver_solve_many(cudamat_solver *s, int nrhs, const doub
                                          int loop, int maxit, double tol, int flags, cudamat_stats *st, int *form)
 {
     return cudamat_solver_solve_shifts(s, nrhs, nullptr, 0, B, ldb, X, ldx, precond, loop, maxit, tol, flags, st, form);
+}
+
+// ---------------------------------------------------------------- one set of ILU(0) factors per column (shifted families)
+namespace {
+
+ColFactors col_factors(cudamat_solver *s)
+{
+    ManyWork &m = s->many;
+    ColFactors f;
+    f.lu = m.lu_b; f.lval = m.lval_b; f.uval = m.uval_b; f.dinv = m.dinv_b;
+    return f;
+}
+
+// a zero pivot met while column `col` was factored on its own: the message names the column too
+int zero_pivot_in_column(int col)
+{
+    char saved[400];
+    snprintf(saved, sizeof(saved), "%s", cudamat_last_error());
+    set_error("column %d: %s", col, saved);
+    return CUDAMAT_ERR_ZERO_PIVOT;
+}
+
+// the ILU(0) structure these calls work on: a solver without one gets it as cudamat_solver_ilu0_shift(D_0) gives it.
+// *fresh0: the solver's factors are those of column 0, just built
+int cols_structure(cudamat_solver *s, const double *D, bool *fresh0)
+{
+    *fresh0 = false;
+    if (s->has_ilu) return CUDAMAT_OK;
+    const int rc = ilu0_setup(s, false, D);
+    if (rc == CUDAMAT_ERR_ZERO_PIVOT) return zero_pivot_in_column(0);
+    CM_TRY(rc);
+    *fresh0 = true;
+    return CUDAMAT_OK;
+}
+
+// column by column: the solver's own factors become those of A0 + diag(d_j) -- cudamat_solver_ilu0_shift when it holds no shifted
+// factors yet, cudamat_solver_ilu0_refactor otherwise: what a caller writes today
+int own_factors_of(cudamat_solver *s, const double *dj, int col, bool already)
+{
+    if (already) return CUDAMAT_OK;
+    const bool shifted = s->has_ilu && s->ilu_shifted && !s->ilu_block;
+    const int rc = shifted ? ilu0_refactor(s, dj) : ilu0_setup(s, false, dj);
+    return rc == CUDAMAT_ERR_ZERO_PIVOT ? zero_pivot_in_column(col) : rc;
+}
+
+// the K-wide factorisation of one block into the factor group; *seconds: what it took (it ends drained)
+int factor_block(cudamat_solver *s, const ColBlock &c, const double *D, int64_t ldd, double *seconds)
+{
+    CM_HIP(hipStreamSynchronize(s->ctx->stream));
+    const double t0 = now_s();
+    int col = 0, row = 0;
+    const int rc = ilu0_numeric_cols(s, c.K, c.kc, D + (size_t)c.c0 * (size_t)ldd, ldd, col_factors(s), s->many.fzp, &col, &row);
+    if (rc == CUDAMAT_ERR_ZERO_PIVOT)
+        set_error("ILU(0) of A0 + diag(D_j): zero pivot in column %d, row %d", c.c0 + col, row);
+    if (seconds) *seconds = now_s() - t0;
+    return rc;
+}
+
+// MANY_PRECOND = auto for the per-column factors: K-wide factorisation + batched loop against kc x (refactorisation + single
+// solve), the factorisation on both sides; timed once per solver and K on scratch right-hand sides with the block's own shifts.
+// The column side works on the solver's own factors: their values are saved first and put back, bit for bit.
+int prefer_batched_cols(cudamat_solver *s, const ColBlock &c, const double *D, int64_t ldd, bool *batched, double *t_tune)
+{
+    ManyWork &m = s->many;
+    const double t0 = now_s();
+    hipStream_t st = s->ctx->stream;
+    const int n = s->n, K = c.K;
+    const double *Dc = D + (size_t)c.c0 * (size_t)ldd;
+    const double it = 4e7 / (double)(s->nnz + 1);
+    const int N = it < 4.0 ? 4 : it > 64.0 ? 64 : (int)it;
+    double &tb = m.t_cols_batch[log2_cols(K)];
+    if (tb < 0.0) {
+        LoopState fin[kBatchMax];
+        const ColFactors f = col_factors(s);
+        for (int rep = 0; rep < 2; rep++) {
+            CM_TRY(launch_fill(st, (int64_t)K * n, 1.0, m.b));
+            CM_TRY(launch_fill(st, (int64_t)K * n, 0.0, m.x));
+            CM_HIP(hipStreamSynchronize(st));
+            const double t = now_s();
+            CM_TRY(factor_block(s, c, D, ldd, nullptr));
+            CM_TRY(run_group(s, K, c.kc, nullptr, 0, nullptr, 0, CUDAMAT_PRECOND_ILU0, CUDAMAT_LOOP_PBICGSTAB, rep ? N : 2, 1e-8,
+                             CUDAMAT_FLAG_NO_EXIT, fin, nullptr, nullptr, true, Dc, ldd, &f));      // (D holds c.kc columns)
+            tb = now_s() - t;
+        }
+    }
+    if (m.t_cols_single < 0.0) {
+        IluPlans *pl = plans_of(s, false);
+        DevBuf<double> lu, lv, uv, di;
+        CM_TRY(lu.alloc((size_t)s->pm_nnz));
+        CM_TRY(lv.alloc((size_t)s->L.nnz));
+        CM_TRY(uv.alloc((size_t)s->U.nnz));
+        CM_TRY(di.alloc((size_t)n));
+        struct Pair { double *keep, *own; size_t count; } pairs[4] = {{lu, s->lu, (size_t)s->pm_nnz}, {lv, s->L.val, (size_t)s->L.nnz},
+                                                                     {uv, s->U.val, (size_t)s->U.nnz}, {di, s->U.dinv, (size_t)n}};
+        for (const Pair &p : pairs)
+            if (p.count) CM_HIP(hipMemcpyAsync(p.keep, p.own, sizeof(double) * p.count, hipMemcpyDeviceToDevice, st));
+        const bool was_shifted = s->ilu_shifted;
+        const double was_t_factor = s->t_factor, was_seconds = pl->refactor_seconds;
+        const int was_refactors = pl->refactors;
+        ShiftGuard own(s);
+        CM_TRY(ensure_work(s));
+        CM_TRY(ensure_spmv_mode(s));
+        s->d = Dc;
+        int rc = CUDAMAT_OK;
+        for (int rep = 0; rep < 2 && !rc; rep++) {
+            rc = launch_fill(st, n, 1.0, m.b);
+            if (!rc) rc = launch_fill(st, n, 0.0, m.x);
+            if (!rc) rc = CM_RC(hipStreamSynchronize(st));
+            const double t = now_s();
+            if (!rc) rc = ilu0_refactor(s, Dc);
+            cudamat_stats dummy;
+            if (!rc) rc = cudamat_solver_solve(s, m.b, m.x, CUDAMAT_PRECOND_ILU0, CUDAMAT_LOOP_PBICGSTAB, rep ? N : 2, 1e-8, CUDAMAT_FLAG_NO_EXIT, &dummy);
+            if (!rc) rc = CM_RC(hipStreamSynchronize(st));
+            m.t_cols_single = now_s() - t;
+        }
+        if (rc) { m.t_cols_single = -1.0; return rc; }      // (a zero pivot here cannot be: the K-wide pass of this block had none)
+        for (const Pair &p : pairs)
+            if (p.count) CM_HIP(hipMemcpyAsync(p.own, p.keep, sizeof(double) * p.count, hipMemcpyDeviceToDevice, st));
+        CM_HIP(hipStreamSynchronize(st));
+        s->ilu_shifted = was_shifted;
+        s->t_factor = was_t_factor;
+        pl->refactors = was_refactors;
+        pl->refactor_seconds = was_seconds;
+    }
+    *batched = tb < 0.97 * (double)c.kc * m.t_cols_single;
+    if (s->ctx->cfg.verbose)
+        fprintf(stderr, "[cudamat] per-column ILU(0): %d iterations + factorisation, single %.3f ms x %d columns, batched (K = %d) %.3f ms -> %s\n",
+                N, 1e3 * m.t_cols_single, c.kc, K, 1e3 * tb, *batched ? "batched" : "columns");
+    *t_tune += now_s() - t0;
+    return CUDAMAT_OK;
+}
+
+// the common checks of the three entry points, and which form a call may take at all
+int cols_batchable(cudamat_solver *s, int nrhs, bool loop_buffers, bool *ok)
+{
+    *ok = s->ctx->cfg.many_form != 2 && trsm_covered(s);
+    if (*ok) CM_TRY(many_room(s, nrhs, loop_buffers, loop_buffers, ok, true));
+    return CUDAMAT_OK;
+}
+
+}  // namespace
+
+extern "C" int cudamat_solver_solve_shifts_ilu0(cudamat_solver *s, int nrhs, const double *D, int ldd, const double *B, int ldb,
+                                                double *X, int ldx, int maxit, double tol, int flags, cudamat_stats *st, int *form)
+{
+    CM_ARG(s, "solver is NULL");
+    CM_ARG(nrhs >= 0, "nrhs < 0");
+    if (form) *form = 0;
+    if (nrhs == 0) return CUDAMAT_OK;
+    CM_ARG(D && B && X, "null pointer");
+    CM_ARG(ldd >= s->n && ldb >= s->n && ldx >= s->n, "leading dimension below the rows");
+    CM_ARG(maxit >= 0, "maxit");
+    CM_ARG(!s->sharded && s->n_cols == s->n && s->n > 0, "ILU(0) of a shifted matrix is single-GPU, whole-matrix only");
+    CM_HIP(hipSetDevice(s->ctx->device));
+    const double t0 = now_s();
+    const Config &cfg = s->ctx->cfg;
+    const int loop = CUDAMAT_LOOP_PBICGSTAB, n = s->n;
+    hipStream_t stream = s->ctx->stream;
+    ShiftGuard own(s);                   // (the solver's shift is column j of D while column j is solved, and what it was afterwards)
+    bool fresh0 = false;
+    CM_TRY(cols_structure(s, D, &fresh0));
+    const bool guarded = (flags & CUDAMAT_FLAG_GUARD) || cfg.guard;
+    bool may_batch = cfg.many_precond != 0 && !(flags & (CUDAMAT_FLAG_DEBUG | CUDAMAT_FLAG_PROFILE)) && !guarded;
+    if (may_batch) CM_TRY(cols_batchable(s, nrhs, true, &may_batch));
+    if (!may_batch && cfg.verbose) fprintf(stderr, "[cudamat] per-column ILU(0): column by column\n");
+    const std::vector<ColBlock> blocks = col_blocks(nrhs);
+    double t_tune = 0.0, t_solve = 0.0;
+    std::vector<char> batched(blocks.size(), 0);
+    for (size_t b = 0; b < blocks.size(); b++) {
+        bool yes = may_batch && ilu0_cols_covered(s, blocks[b].K);
+        if (yes && cfg.many_precond == 1) CM_TRY(prefer_batched_cols(s, blocks[b], D, ldd, &yes, &t_tune));
+        batched[b] = yes ? 1 : 0;
+    }
+    // X is written only once no column can fail any more: a single batched block factors before it writes; everything else
+    // works on a copy of X, which replaces X at the end.  Column j of the copy sits where column j of X sits relative to a
+    // 16-byte boundary (the single solve's vector kernels choose their form by that: the caller's loop on X, bit for bit).
+    const bool staged = !(blocks.size() == 1 && batched[0]);
+    DevBuf<double> xs;
+    double *Xw = X;
+    int64_t ldw = ldx;
+    if (staged) {
+        ldw = (int64_t)n + ((ldx - n) & 1);
+        CM_TRY(xs.alloc((size_t)ldw * (size_t)nrhs + 2));
+        Xw = xs.get() + (((uintptr_t)X >> 3) & 1);
+        if (!(flags & CUDAMAT_FLAG_X0_ONES))
+            for (int j = 0; j < nrhs; j++)
+                CM_HIP(hipMemcpyAsync(Xw + (size_t)j * ldw, X + (size_t)j * ldx, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream));
+    }
+    std::vector<cudamat_stats> out((size_t)nrhs);
+    std::vector<std::vector<double>> hists((size_t)nrhs);
+    bool any_batched = false;
+    for (size_t b = 0; b < blocks.size(); b++) {
+        const ColBlock &c = blocks[b];
+        if (batched[b]) {
+            double tf = 0.0, tl = 0.0;
+            CM_TRY(factor_block(s, c, D, ldd, &tf));
+            const ColFactors f = col_factors(s);
+            LoopState fin[kBatchMax];
+            CM_TRY(run_group(s, c.K, c.kc, B + (size_t)c.c0 * ldb, ldb, Xw + (size_t)c.c0 * ldw, ldw, CUDAMAT_PRECOND_ILU0, loop, maxit,
+                             tol, flags, fin, hists.data() + c.c0, &tl, true, D + (size_t)c.c0 * ldd, ldd, &f));
+            t_solve += tl;
+            for (int j = 0; j < c.kc; j++) {
+                cudamat_stats &o = out[(size_t)(c.c0 + j)];
+                fill_stats(s, fin[j], CUDAMAT_PRECOND_ILU0, &o);
+                o.t_factor = tf;             // the block's K-wide factorisation
+            }
+            any_batched = true;
+            continue;
+        }
+        for (int j = c.c0; j < c.c0 + c.kc; j++) {
+            const double *dj = D + (size_t)j * ldd;
+            cudamat_stats &sj = out[(size_t)j];
+            s->d = dj;
+            CM_TRY(own_factors_of(s, dj, j, fresh0 && j == 0));
+            CM_TRY(cudamat_solver_solve(s, B + (size_t)j * ldb, Xw + (size_t)j * ldw, CUDAMAT_PRECOND_ILU0, loop, maxit, tol, flags, &sj));
+            t_solve += sj.t_solve;
+            int cnt = 0;
+            std::vector<double> &h = hists[(size_t)j];
+            h.assign((size_t)(s->hist_count > 0 ? s->hist_count : 0), 0.0);
+            if (!h.empty()) CM_TRY(cudamat_solver_history(s, h.data(), (int)h.size(), &cnt));
+        }
+    }
+    if (staged) {
+        for (int j = 0; j < nrhs; j++)
+            CM_HIP(hipMemcpyAsync(X + (size_t)j * ldx, Xw + (size_t)j * ldw, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream));
+        CM_HIP(hipStreamSynchronize(stream));
+    }
+    s->many.hist_host.swap(hists);
+    const double t_total = now_s() - t0;
+    for (cudamat_stats &o : out) {
+        o.t_solve = t_solve;
+        o.t_total = t_total;
+        o.t_tune += t_tune;
+    }
+    if (st) memcpy(st, out.data(), sizeof(cudamat_stats) * (size_t)nrhs);
+    if (form) *form = any_batched ? 1 : 0;
+    return CUDAMAT_OK;
+}
+
+extern "C" int cudamat_solver_precond_apply_shifts(cudamat_solver *s, int nrhs, const double *D, int ldd, const double *In, int ldin,
+                                                   double *Out, int ldout)
+{
+    CM_ARG(s, "solver is NULL");
+    CM_ARG(nrhs >= 0, "nrhs < 0");
+    if (nrhs == 0) return CUDAMAT_OK;
+    CM_ARG(D && In && Out, "null pointer");
+    CM_ARG(ldd >= s->n && ldin >= s->n && ldout >= s->n, "leading dimension below the rows");
+    CM_ARG(!s->sharded && s->n_cols == s->n && s->n > 0, "ILU(0) of a shifted matrix is single-GPU, whole-matrix only");
+    CM_HIP(hipSetDevice(s->ctx->device));
+    bool fresh0 = false, may_batch = false;
+    CM_TRY(cols_structure(s, D, &fresh0));
+    CM_TRY(cols_batchable(s, nrhs, false, &may_batch));
+    ManyWork &m = s->many;
+    hipStream_t st = s->ctx->stream;
+    for (const ColBlock &c : col_blocks(nrhs)) {
+        if (may_batch && ilu0_cols_covered(s, c.K)) {
+            CM_TRY(factor_block(s, c, D, ldd, nullptr));
+            CM_TRY(launch_batch_in(st, c.K, c.kc, s->n, s->n, In + (size_t)c.c0 * ldin, ldin, 0.0, m.b));
+            CM_TRY(precond_apply_cols(s, c.K, col_factors(s), m.b, m.t, m.x));
+            CM_TRY(launch_batch_out(st, c.K, c.kc, s->n, m.x, Out + (size_t)c.c0 * ldout, ldout));
+            continue;
+        }
+        CM_TRY(ensure_work(s));
+        for (int j = c.c0; j < c.c0 + c.kc; j++) {
+            CM_TRY(own_factors_of(s, D + (size_t)j * ldd, j, fresh0 && j == 0));
+            CM_TRY(precond_apply(s, In + (size_t)j * ldin, s->t, Out + (size_t)j * ldout));
+        }
+    }
+    return CUDAMAT_OK;
+}
+
+extern "C" int cudamat_solver_ilu0_shifts_values(cudamat_solver *s, int nrhs, const double *D, int ldd, double *Out, int64_t ldo)
+{
+    CM_ARG(s, "solver is NULL");
+    CM_ARG(nrhs >= 0, "nrhs < 0");
+    if (nrhs == 0) return CUDAMAT_OK;
+    CM_ARG(D && Out, "null pointer");
+    CM_ARG(ldd >= s->n, "leading dimension below the rows");
+    CM_ARG(!s->sharded && s->n_cols == s->n && s->n > 0, "ILU(0) of a shifted matrix is single-GPU, whole-matrix only");
+    CM_HIP(hipSetDevice(s->ctx->device));
+    bool fresh0 = false, may_batch = false;
+    CM_TRY(cols_structure(s, D, &fresh0));
+    CM_ARG(ldo >= s->pm_nnz, "leading dimension below the entries of the factors (cudamat_solver_ilu0_nnz)");
+    CM_TRY(cols_batchable(s, nrhs, false, &may_batch));
+    hipStream_t st = s->ctx->stream;
+    for (const ColBlock &c : col_blocks(nrhs)) {
+        if (may_batch && ilu0_cols_covered(s, c.K)) {
+            CM_TRY(factor_block(s, c, D, ldd, nullptr));
+            CM_TRY(launch_batch_out(st, c.K, c.kc, s->pm_nnz, s->many.lu_b, Out + (size_t)c.c0 * (size_t)ldo, ldo));
+            continue;
+        }
+        for (int j = c.c0; j < c.c0 + c.kc; j++) {
+            CM_TRY(own_factors_of(s, D + (size_t)j * ldd, j, fresh0 && j == 0));
+            CM_HIP(hipMemcpyAsync(Out + (size_t)j * (size_t)ldo, s->lu, sizeof(double) * (size_t)s->pm_nnz, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    return CUDAMAT_OK;
 }
 
 extern "C" int cudamat_solver_history_col(cudamat_solver *s, int col, double *hist_host, int cap, int *count)

@@ -46,12 +46,21 @@ struct ManyWork {
     // per-column shifts (cudamat_solver_spmm_shifts / _solve_shifts): one block of `dcap` columns, allocated at its first use
     int dcap = 0;
     DevBuf<double> dk;
+    // per-column factors of one block (cudamat_solver_solve_shifts_ilu0): the K-wide LU values on the matrix's pattern, L's and
+    // U's values in level-major order, 1 / U's diagonal -- `fcap` columns, sized for the structure with f_nnz / f_lnnz / f_unnz
+    // entries; the zero-pivot word of the factorisation.  Allocated at the first use, rebuilt per block, not kept across calls.
+    int fcap = 0;
+    int64_t f_nnz = 0, f_lnnz = 0, f_unnz = 0;
+    DevBuf<double> lu_b, lval_b, uval_b, dinv_b;
+    DevBuf<unsigned long long> fzp;
     DevBuf<double> hist;        // device: per column a history of the batch's length (hist_bytes in all)
     size_t hist_bytes = 0;
     std::vector<std::vector<double>> hist_host;   // per column: the residual history of the last cudamat_solver_solve_many
     // form choice (MANY_FORM / MANY_PRECOND = auto): seconds of tune_iters iterations, single loop (< 0: not timed) and batched by log2 K
     double t_single = -1.0, t_batch[4] = {-1.0, -1.0, -1.0, -1.0};
     int tune_loop = -1, tune_precond = -1, tune_shifts = -1, tune_iters = 0;
+    // ... and of cudamat_solver_solve_shifts_ilu0 (factorisation included on both sides): per column, < 0: not timed
+    double t_cols_single = -1.0, t_cols_batch[4] = {-1.0, -1.0, -1.0, -1.0};
 };
 
 }  // namespace cm

@@ -16,6 +16,9 @@
 // serves K columns, and the factor's indices and values (12 B per entry) are read once instead of K times.
 // Every column of the block is computed (padding columns of a short batch too: plain arithmetic on whatever they hold, NaN
 // or Inf included); the callers never copy a padding column back.
+// One more template parameter, PV: the factor VALUES are per column too (fval[k*K + j], dinv[pr*K + j]: the ILU(0) of K shifted
+// matrices on one pattern, ilu.hip) -- trsm_apply_cols / precond_apply_cols.  Indices, levels, grids and form choice are the
+// solver's own; by the argument above column j is bit-identical to the K = 1 kernel on the factors of column j alone.
 //
 // Single-column only: the dependency-driven k_trsv_syncfree.  Its protocol publishes one 8-byte value per row; a K-wide row
 // would be K publications read by 16-byte loads, which needs an argument about tearing that has not been made.  Also not
@@ -45,7 +48,17 @@ namespace cm {
 // rhs_of = nullptr (L: the right-hand side is in L's space) or the U-position -> L-position map (U).
 // LANES lanes per row, exactly the SpMV inner loop; rows of one level are independent.  far (K = 1 only: hybrid factors
 // have no multi-column form) holds the entries whose column lies in an earlier group.
-template <int LANES, int K>
+// PV ("per-column values", the factors of K shifted matrices on one pattern: cudamat_solver_solve_shifts_ilu0): fval and dinv
+// hold K values per entry / row, interleaved like the vectors -- fval[k*K + j], dinv[pr*K + j] -- and column j takes its own:
+// the same operations in the same order as the K = 1 kernel on the factors of column j alone, so the same bits.
+template <int K, bool PV>
+__device__ __forceinline__ void load_vals(const double *v, int64_t k, double (&a)[PV ? K : 1])
+{
+    if constexpr (PV) load_row<K>(v, k, a);
+    else a[0] = v[k];
+}
+
+template <int LANES, int K, bool PV = false>
 __device__ __forceinline__ void tri_rows(int r0, int r1, int first, int stride, const int *frp, const int *fci,
                                          const double *fval, const int *rhs_of, const int *out_of, const double *dinv,
                                          const double *far, const double *rhs, double *out)
@@ -57,43 +70,46 @@ __device__ __forceinline__ void tri_rows(int r0, int r1, int first, int stride, 
 #pragma unroll
         for (int j = 0; j < K; j++) sum[j] = 0.0;
         for (int k = s + lane; k < e; k += LANES) {
-            const double a = fval[k];
+            double a[PV ? K : 1];
+            load_vals<K, PV>(fval, k, a);
             double xv[K];
             load_row<K>(out, fci[k], xv);
 #pragma unroll
-            for (int j = 0; j < K; j++) sum[j] += a * xv[j];
+            for (int j = 0; j < K; j++) sum[j] += a[PV ? j : 0] * xv[j];
         }
 #pragma unroll
         for (int j = 0; j < K; j++) sum[j] = group_sum<LANES>(sum[j]);
         if (lane == 0) {
             double v[K];
             load_row<K>(rhs, rhs_of ? rhs_of[pr] : pr, v);
+            double di[PV ? K : 1];
+            if (dinv) load_vals<K, PV>(dinv, pr, di);
 #pragma unroll
             for (int j = 0; j < K; j++) {
                 v[j] = v[j] - sum[j];
                 if constexpr (K == 1) {
                     if (far) v[j] -= far[pr];
                 }
-                if (dinv) v[j] *= dinv[pr];
+                if (dinv) v[j] *= di[PV ? j : 0];
             }
             store_row<K>(out, out_of ? out_of[pr] : pr, v, kAll);
         }
     }
 }
 
-template <int LANES, int K>
+template <int LANES, int K, bool PV = false>
 __global__ __launch_bounds__(kBlock) void k_trsm_level(int r0, int r1, const int *frp, const int *fci, const double *fval,
                                                        const int *rhs_of, const int *out_of, const double *dinv,
                                                        const double *far, const double *rhs, double *out)
 {
     constexpr int RPB = kBlock / LANES;
-    tri_rows<LANES, K>(r0, r1, blockIdx.x * RPB + threadIdx.x / LANES, gridDim.x * RPB, frp, fci, fval, rhs_of, out_of,
-                       dinv, far, rhs, out);
+    tri_rows<LANES, K, PV>(r0, r1, blockIdx.x * RPB + threadIdx.x / LANES, gridDim.x * RPB, frp, fci, fval, rhs_of, out_of,
+                           dinv, far, rhs, out);
 }
 
 // several consecutive small levels in ONE workgroup: a workgroup-scope fence + barrier publishes a
 // level's results (same CU, same L1) to the threads that consume them in the next level.
-template <int LANES, int K>
+template <int LANES, int K, bool PV = false>
 __global__ __launch_bounds__(kBlock) void k_trsm_small_levels(int l0, int l1, const int *level_ptr, const int *frp,
                                                               const int *fci, const double *fval, const int *rhs_of,
                                                               const int *out_of, const double *dinv, const double *far,
@@ -101,8 +117,8 @@ __global__ __launch_bounds__(kBlock) void k_trsm_small_levels(int l0, int l1, co
 {
     constexpr int RPB = kBlock / LANES;
     for (int l = l0; l < l1; l++) {
-        tri_rows<LANES, K>(level_ptr[l], level_ptr[l + 1], threadIdx.x / LANES, RPB, frp, fci, fval, rhs_of, out_of, dinv,
-                           far, rhs, out);
+        tri_rows<LANES, K, PV>(level_ptr[l], level_ptr[l + 1], threadIdx.x / LANES, RPB, frp, fci, fval, rhs_of, out_of, dinv,
+                               far, rhs, out);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __syncthreads();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -237,7 +253,7 @@ __global__ __launch_bounds__(BLOCK) void k_trsv_syncfree(int r0, int r1, const i
 // global memory before the barrier, so nothing but LDS sits between two levels (mat10000: 199 levels per factor).
 // Same per-row summation as tri_rows (lane k takes entries k, k + LANES, ...; xor tree per column) => bit-identical.
 // Factors in the original index space only (row_of): a hybrid factor never takes this form.
-template <int LANES, int K>
+template <int LANES, int K, bool PV = false>
 __global__ __launch_bounds__(kBlock) void k_trsm_lds(int n, int nlev, const int *level_ptr, const int *frp, const int *fci,
                                                      const double *fval, const int *row_of, const double *dinv,
                                                      const double *rhs, double *out)
@@ -245,8 +261,14 @@ __global__ __launch_bounds__(kBlock) void k_trsm_lds(int n, int nlev, const int 
     extern __shared__ __attribute__((aligned(16))) double xs[];       // n x K doubles, original row numbering
     constexpr int RPB = kBlock / LANES;
     const int lane = threadIdx.x & (LANES - 1), team = threadIdx.x / LANES;
+    constexpr int KV = PV ? K : 1;                                     // values per entry / row: one shared, or one per column
     int pr = 0, s = 0, e = 0, r = 0, c = 0;
-    double a = 0.0, di = 1.0;
+    double a[KV], di[KV];
+#pragma unroll
+    for (int j = 0; j < KV; j++) {
+        a[j] = 0.0;
+        di[j] = 1.0;
+    }
     double b[K];
 #pragma unroll
     for (int j = 0; j < K; j++) b[j] = 0.0;
@@ -261,12 +283,12 @@ __global__ __launch_bounds__(kBlock) void k_trsm_lds(int n, int nlev, const int 
         e = frp[pr + 1];
         if (s + lane < e) {
             c = fci[s + lane];
-            a = fval[s + lane];
+            load_vals<K, PV>(fval, s + lane, a);
         }
         if (lane == 0) {
             r = row_of[pr];
             load_row<K>(rhs, r, b);
-            if (dinv) di = dinv[pr];
+            if (dinv) load_vals<K, PV>(dinv, pr, di);
         }
     };
     fetch(0);
@@ -274,7 +296,9 @@ __global__ __launch_bounds__(kBlock) void k_trsm_lds(int n, int nlev, const int 
         const int lend = level_ptr[l + 1];
         const bool have = mine;
         const int pr0 = pr, s0 = s, e0 = e, r0 = r;
-        const double di0 = di;
+        double di0[KV];
+#pragma unroll
+        for (int j = 0; j < KV; j++) di0[j] = di[j];
         double b0[K], sum[K];
 #pragma unroll
         for (int j = 0; j < K; j++) {
@@ -286,14 +310,15 @@ __global__ __launch_bounds__(kBlock) void k_trsm_lds(int n, int nlev, const int 
                 double xv[K];
                 load_row<K>(xs, c, xv);
 #pragma unroll
-                for (int j = 0; j < K; j++) sum[j] = a * xv[j];
+                for (int j = 0; j < K; j++) sum[j] = a[PV ? j : 0] * xv[j];
             }
             for (int k = s0 + lane + LANES; k < e0; k += LANES) {
-                const double av = fval[k];
+                double av[KV];
+                load_vals<K, PV>(fval, k, av);
                 double xv[K];
                 load_row<K>(xs, fci[k], xv);
 #pragma unroll
-                for (int j = 0; j < K; j++) sum[j] += av * xv[j];
+                for (int j = 0; j < K; j++) sum[j] += av[PV ? j : 0] * xv[j];
             }
         }
 #pragma unroll
@@ -303,7 +328,7 @@ __global__ __launch_bounds__(kBlock) void k_trsm_lds(int n, int nlev, const int 
 #pragma unroll
             for (int j = 0; j < K; j++) {
                 v[j] = b0[j] - sum[j];
-                if (dinv) v[j] *= di0;
+                if (dinv) v[j] *= di0[PV ? j : 0];
             }
             store_row<K>(xs, r0, v, kAll);
             store_row<K>(out, r0, v, kAll);
@@ -315,11 +340,12 @@ __global__ __launch_bounds__(kBlock) void k_trsm_lds(int n, int nlev, const int 
 #pragma unroll
             for (int j = 0; j < K; j++) t[j] = 0.0;
             for (int k = qs + lane; k < qe; k += LANES) {
-                const double av = fval[k];
+                double av[KV];
+                load_vals<K, PV>(fval, k, av);
                 double xv[K];
                 load_row<K>(xs, fci[k], xv);
 #pragma unroll
-                for (int j = 0; j < K; j++) t[j] += av * xv[j];
+                for (int j = 0; j < K; j++) t[j] += av[PV ? j : 0] * xv[j];
             }
 #pragma unroll
             for (int j = 0; j < K; j++) t[j] = group_sum<LANES>(t[j]);
@@ -327,10 +353,12 @@ __global__ __launch_bounds__(kBlock) void k_trsm_lds(int n, int nlev, const int 
                 const int rr = row_of[q];
                 double v[K];
                 load_row<K>(rhs, rr, v);
+                double dq[KV];
+                if (dinv) load_vals<K, PV>(dinv, q, dq);
 #pragma unroll
                 for (int j = 0; j < K; j++) {
                     v[j] = v[j] - t[j];
-                    if (dinv) v[j] *= dinv[q];
+                    if (dinv) v[j] *= dq[PV ? j : 0];
                 }
                 store_row<K>(xs, rr, v, kAll);
                 store_row<K>(out, rr, v, kAll);
@@ -391,8 +419,10 @@ static int with_cols(int K, Fn &&f)
 // the level-by-level launch plan (TriHost::seg_begin / seg_end): a wide level is its own launch, a run of narrow levels
 // one single-workgroup launch.  The grids depend on the factor only.  A hybrid factor (K = 1 only, trsm_covered) gets one
 // blocked SpMV per group for its far entries.
-template <int LANES, int K>
-static int launch_level_segments(hipStream_t st, const TriFactor &F, const TriHost &H, const double *rhs, double *out)
+// val / dinv: the factor's own (F.val, F.dinv), or with PV the K-wide values of a block of shifted factors on F's pattern.
+template <int LANES, int K, bool PV = false>
+static int launch_level_segments(hipStream_t st, const TriFactor &F, const TriHost &H, const double *val, const double *dinv,
+                                 const double *rhs, double *out)
 {
     constexpr int RPB = kBlock / LANES;
     int cur_group = -1;
@@ -407,23 +437,24 @@ static int launch_level_segments(hipStream_t st, const TriFactor &F, const TriHo
         const int l0 = H.seg_begin[g], l1 = H.seg_end[g];
         const int r0 = F.level_ptr[(size_t)l0], r1 = F.level_ptr[(size_t)l1];
         if (segment_is_wide(F, H, g)) {
-            hipLaunchKernelGGL((k_trsm_level<LANES, K>), dim3(row_grid(r1 - r0, RPB)), dim3(kBlock), 0, st, r0, r1, F.rp, F.ci,
-                               F.val, F.rhs_of, F.out_of, F.dinv, far, rhs, out);
+            hipLaunchKernelGGL((k_trsm_level<LANES, K, PV>), dim3(row_grid(r1 - r0, RPB)), dim3(kBlock), 0, st, r0, r1, F.rp, F.ci,
+                               val, F.rhs_of, F.out_of, dinv, far, rhs, out);
         } else {
-            hipLaunchKernelGGL((k_trsm_small_levels<LANES, K>), dim3(1), dim3(kBlock), 0, st, l0, l1, H.level_ptr_dev, F.rp,
-                               F.ci, F.val, F.rhs_of, F.out_of, F.dinv, far, rhs, out);
+            hipLaunchKernelGGL((k_trsm_small_levels<LANES, K, PV>), dim3(1), dim3(kBlock), 0, st, l0, l1, H.level_ptr_dev, F.rp,
+                               F.ci, val, F.rhs_of, F.out_of, dinv, far, rhs, out);
         }
     }
     return CUDAMAT_OK;
 }
 
-template <int LANES, int K>
-static int launch_lds(cudamat_solver *s, const TriFactor &F, const TriHost &H, const double *rhs, double *out)
+template <int LANES, int K, bool PV = false>
+static int launch_lds(cudamat_solver *s, const TriFactor &F, const TriHost &H, const double *val, const double *dinv,
+                      const double *rhs, double *out)
 {
     const size_t bytes = sizeof(double) * (size_t)s->n * (size_t)K;
-    CM_TRY(set_max_lds((const void *)k_trsm_lds<LANES, K>));
-    hipLaunchKernelGGL((k_trsm_lds<LANES, K>), dim3(1), dim3(kBlock), bytes, s->ctx->stream, s->n, F.nlevels, H.level_ptr_dev,
-                       F.rp, F.ci, F.val, F.row_of, F.dinv, rhs, out);
+    CM_TRY(set_max_lds((const void *)k_trsm_lds<LANES, K, PV>));
+    hipLaunchKernelGGL((k_trsm_lds<LANES, K, PV>), dim3(1), dim3(kBlock), bytes, s->ctx->stream, s->n, F.nlevels, H.level_ptr_dev,
+                       F.rp, F.ci, val, F.row_of, dinv, rhs, out);
     return CUDAMAT_OK;
 }
 
@@ -526,9 +557,9 @@ int trsv_apply(cudamat_solver *s, const TriFactor &F, bool upper, const double *
     if (H.syncfree && rhs == out) { set_error("triangular solve: rhs and out must not alias"); return CUDAMAT_ERR_ARG; }
     CM_TRY(with_lanes(H.lanes, [&](auto lanes) {
         constexpr int LANES = decltype(lanes)::value;
-        if (H.lds && !H.syncfree) return launch_lds<LANES, 1>(s, F, H, rhs, out);
+        if (H.lds && !H.syncfree) return launch_lds<LANES, 1>(s, F, H, F.val, F.dinv, rhs, out);
         if (H.syncfree) return launch_trsv_syncfree<LANES>(s->ctx->stream, F, H, s->n, rhs, out, pl->err_dev);
-        return launch_level_segments<LANES, 1>(s->ctx->stream, F, H, rhs, out);
+        return launch_level_segments<LANES, 1>(s->ctx->stream, F, H, F.val, F.dinv, rhs, out);
     }));
     CM_HIP(hipGetLastError());
     return CUDAMAT_OK;
@@ -604,8 +635,8 @@ int trsm_apply(cudamat_solver *s, const TriFactor &F, bool upper, int K, const d
     CM_TRY(with_lanes(H.lanes, [&](auto lanes) {
         return with_cols(K, [&](auto cols) {
             constexpr int LANES = decltype(lanes)::value, KC = decltype(cols)::value;
-            if (takes_lds(s, H, KC)) return launch_lds<LANES, KC>(s, F, H, rhs, out);
-            return launch_level_segments<LANES, KC>(s->ctx->stream, F, H, rhs, out);
+            if (takes_lds(s, H, KC)) return launch_lds<LANES, KC>(s, F, H, F.val, F.dinv, rhs, out);
+            return launch_level_segments<LANES, KC>(s->ctx->stream, F, H, F.val, F.dinv, rhs, out);
         });
     }));
     CM_HIP(hipGetLastError());
@@ -616,6 +647,33 @@ int precond_apply_b(cudamat_solver *s, int K, const double *in, double *tmp, dou
 {
     CM_TRY(trsm_apply(s, s->L, false, K, in, tmp));     // pbicgstab.cu:92-94 / :121-123
     CM_TRY(trsm_apply(s, s->U, true, K, tmp, out));     // pbicgstab.cu:96-98 / :125-127
+    return CUDAMAT_OK;
+}
+
+// ---- K columns, each with the values of its own factors (PV): the solver's pattern, levels, launch plan and form choice --
+// the same grids as trsm_apply, so column j runs the very schedule of the single-column solve on the factors of column j
+int trsm_apply_cols(cudamat_solver *s, bool upper, int K, const double *val_b, const double *dinv_b, const double *rhs, double *out)
+{
+    IluPlans *pl = plans_of(s, false);
+    if (!pl || !trsm_covered(s)) { set_error("ILU(0) structure missing or not covered by the multi-column solves"); return CUDAMAT_ERR_ARG; }
+    if (rhs == out) { set_error("triangular solve: rhs and out must not alias"); return CUDAMAT_ERR_ARG; }
+    const TriHost &H = upper ? pl->U : pl->L;
+    const TriFactor &F = upper ? s->U : s->L;
+    CM_TRY(with_lanes(H.lanes, [&](auto lanes) {
+        return with_cols(K, [&](auto cols) {
+            constexpr int LANES = decltype(lanes)::value, KC = decltype(cols)::value;
+            if (takes_lds(s, H, KC)) return launch_lds<LANES, KC, true>(s, F, H, val_b, dinv_b, rhs, out);
+            return launch_level_segments<LANES, KC, true>(s->ctx->stream, F, H, val_b, dinv_b, rhs, out);
+        });
+    }));
+    CM_HIP(hipGetLastError());
+    return CUDAMAT_OK;
+}
+
+int precond_apply_cols(cudamat_solver *s, int K, const ColFactors &f, const double *in, double *tmp, double *out)
+{
+    CM_TRY(trsm_apply_cols(s, false, K, f.lval, nullptr, in, tmp));
+    CM_TRY(trsm_apply_cols(s, true, K, f.uval, f.dinv, tmp, out));
     return CUDAMAT_OK;
 }
 

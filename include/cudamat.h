@@ -402,7 +402,38 @@ int cudamat_solver_spmm_shifts(cudamat_solver *s, int nrhs, const double *X, int
                                int ldy);
 int cudamat_solver_solve_shifts(cudamat_solver *s, int nrhs, const double *D, int ldd, const double *B, int ldb, double *X,
                                 int ldx, int precond, int loop, int maxit, double tol, int flags, cudamat_stats *st, int *form);
-/* residual history of column `col` of the last cudamat_solver_solve_many / _solve_shifts, laid out as cudamat_solver_history's */
+/* The shifted family WITH a preconditioner: (A0 + diag(D_j)) x_j = b_j by the reference loop (CUDAMAT_LOOP_PBICGSTAB), M_j the
+ * ILU(0) of A0 + diag(D_j) -- one set of factors per column.  (cudamat_solver_solve_shifts and _solve_many keep their refusals.)
+ * Blocks of at most 8 columns.  Batched form: the block's K factorisations run as ONE K-wide numeric ILU(0) on the solver's
+ * ILU(0) structure (pattern, levels and searches are shared, values interleaved), then the batched loop with the multi-column
+ * triangular solves reading one value per column; column j's factors, iterate and history are bit-identical to
+ * cudamat_solver_ilu0_shift(D_j) + set_shift(D_j) + the same call with nrhs = 1.  st[j].t_factor: the block's factorisation.
+ * Form: MANY_PRECOND = columns (default) | batched | auto (times both, each side with its factorisation), MANY_FORM = columns
+ * overrides.  Batched needs factors in the original index space on one GPU (see cudamat_solver_precond_apply_many), every
+ * row within the LDS limit of the K-wide factorisation (7616 / 5376 / 3392 / 1920 entries for blocks of 1 / 2 / 4 / 8 columns),
+ * room for the buffers, and none of FLAG_DEBUG / _PROFILE / _GUARD.  Everything else runs column by column, per column what a
+ * caller writes today: set_shift(D_j); cudamat_solver_ilu0_shift(D_j) while the solver holds no shifted factors, else
+ * cudamat_solver_ilu0_refactor(D_j); cudamat_solver_solve(CUDAMAT_PRECOND_ILU0) -- bit for bit.
+ * State the call leaves: the solver's own shift is what it was, on every path.  A solver without ILU(0) structure gets it as
+ * cudamat_solver_ilu0_shift(D_0) gives it.  Batched: the values of factors the solver already held are untouched bit for bit
+ * (the per-column factors live in scratch and are not kept across calls).  Column by column: the solver's factors are those of
+ * the last column, as after the caller's loop.
+ * A zero pivot in any column: CUDAMAT_ERR_ZERO_PIVOT, the message names column and row, X is untouched (a call that is not one
+ * batched block iterates on a copy of X, n x nrhs doubles, which replaces X at the end).  In the batched form the factors the
+ * solver held beforehand stay valid; column by column a zero pivot leaves the solver as cudamat_solver_ilu0_refactor does,
+ * without factors.  nrhs == 0 is a no-op; *form (may be NULL): 1 when any block ran batched.                              */
+int cudamat_solver_solve_shifts_ilu0(cudamat_solver *s, int nrhs, const double *D, int ldd, const double *B, int ldb, double *X,
+                                     int ldx, int maxit, double tol, int flags, cudamat_stats *st, int *form);
+/* Out_j = U_j^-1 L_j^-1 In_j with the ILU(0) factors of A0 + diag(D_j): column j is bit-identical to
+ * cudamat_solver_precond_apply on a solver that holds cudamat_solver_ilu0_shift(D_j).  K-wide (the solver's own factor values
+ * untouched) wherever the batched form above is possible -- MANY_FORM = columns overrides, MANY_PRECOND is not asked --, else
+ * column by column through the solver's own factors, which are then those of the last column.                              */
+int cudamat_solver_precond_apply_shifts(cudamat_solver *s, int nrhs, const double *D, int ldd, const double *In, int ldin,
+                                        double *Out, int ldout);
+/* column j of Out (device, column-major, ldo >= cudamat_solver_ilu0_nnz) = what cudamat_solver_ilu0_values returns after
+ * cudamat_solver_ilu0_shift(D_j), bit for bit; forms as cudamat_solver_precond_apply_shifts                               */
+int cudamat_solver_ilu0_shifts_values(cudamat_solver *s, int nrhs, const double *D, int ldd, double *Out, int64_t ldo);
+/* residual history of column `col` of the last cudamat_solver_solve_many / _solve_shifts / _solve_shifts_ilu0, laid out as cudamat_solver_history's */
 int cudamat_solver_history_col(cudamat_solver *s, int col, double *hist_host, int cap, int *count);
 
 /* ---- drop-in host-pointer solve ---------------------------------------------------- */
@@ -429,6 +460,13 @@ int cudamat_solve_many(int n, int nnz, const double *A, const int *iA, const int
 int cudamat_solve_shifts(int n, int nnz, const double *A0, const int *iA0, const int *jA0, int nrhs, const double *D, int ldd,
                          const double *B, int ldb, const double *x0, double *X, int ldx, int loop, int maxit, double tol,
                          cudamat_stats *st, int *form);
+
+/* cudamat_solve_shifts with the ILU(0) of A0 + diag(D_j) as column j's preconditioner (cudamat_solver_solve_shifts_ilu0 on the
+ * kept solver: the reference loop, the same plan cache, the same form rules).  Arguments are checked before any device is
+ * touched; nrhs == 0 is a successful no-op.                                                                                 */
+int cudamat_solve_shifts_ilu0(int n, int nnz, const double *A0, const int *iA0, const int *jA0, int nrhs, const double *D, int ldd,
+                              const double *B, int ldb, const double *x0, double *X, int ldx, int maxit, double tol,
+                              cudamat_stats *st, int *form);
 
 /* cudamat_solve keeps the solver of its LAST call (CSR copies, SpMV plan, ILU(0) factors: device memory on device 0 --
  * about 16 GB at 1e7 rows x 50 entries, 50 GB with ILU(0)) so that a caller who solves with the same matrix again --

@@ -16,6 +16,12 @@ sequential set_shift + Solver.solve calls and (b) the shared-d batched loop (set
 (a) and (b) use nothing newer than solve_many --, what MANY_FORM = auto picks with shifts, and the SpMM with per-column shifts
 (bytes = 12 nnz + 4 (n + 1) + 8 K (n_cols + n) + 8 K n).  C2 is mat10000 with its diagonal split off and d_j = its diagonal
 times (1 + j/8); the generated systems keep their matrix as A0 and get d_j = (1 + j)/8.  All FLAG_NO_EXIT.
+
+--shifts --precond ilu0: the shifted family with one set of ILU(0) factors per column (Solver.solve_shifts_ilu0, MANY_PRECOND =
+batched: K-wide factorisation + multi-column triangular solves with per-column values) against the column form as a caller
+writes it -- per column set_shift + ilu0_refactor + Solver.solve, nothing newer on that side (--sequential-only runs just that).
+D_j = (1 + j)/8 (0.5 + i/n) on mat10000, the 2000 x 2000 stencil and a random 2e5 x 50 system, K = 2, 4, 8, TRSV_HYBRID = 0.
+Per (config, K): per-column it/s of both loops, factorisation ms per column of both, and the whole call per column.
 """
 import argparse
 import json
@@ -37,8 +43,8 @@ def make(ctx, name):
         err, m, n, nnz, val, row, col = cm.loadMMSparseMatrix(os.path.join(ROOT, "tests", "golden", "mat10000.mtx"))
         rp, ci, v = ctx.array(row, np.int32), ctx.array(col, np.int32), ctx.array(val)
         return cm.Solver(ctx, n, n, nnz, rp, ci, v, int(row[0])), n, nnz, (rp, ci, v)
-    if name.startswith("C3_poisson"):
-        nx, ny = 4000, 2500
+    if "poisson" in name:
+        nx, ny = (int(q) for q in name.split("poisson")[1].split("x"))
         n = nx * ny
         nnz = int(cm.lib().cudamat_poisson5_nnz(nx, ny))
         rp, ci, v = ctx.empty(n + 1, np.int32), ctx.empty(nnz, np.int32), ctx.empty(nnz)
@@ -233,6 +239,60 @@ def run_precond(name, iters, sequential_only, build):
     ctx.close()
 
 
+def run_shifts_precond(name, iters, sequential_only, build):
+    ctx = cm.Context(0)
+    ctx.set_option("TRSV_HYBRID", "0")
+    s, n, nnz, keep = make(ctx, name)
+    B, X = ctx.empty(8 * n), ctx.empty(8 * n)
+    for j in range(8):
+        ctx.gen_xstar(0, n, 100 + j, X.ptr + 8 * j * n)
+    ramp = 0.5 + np.arange(n) / n
+    D = ctx.array(np.concatenate([(1.0 + j) / 8.0 * ramp for j in range(8)]))
+    for j in range(8):                       # b_j = (A0 + diag d_j) x*_j, one SpMV per column
+        s.set_shift(D.ptr + 8 * j * n)
+        s.spmv(X.ptr + 8 * j * n, B.ptr + 8 * j * n)
+    s.set_shift(None)
+    kw = dict(precond=cm.PRECOND_ILU0, loop=cm.LOOP_PBICGSTAB, tol=1e-8, flags=cm.FLAG_NO_EXIT)
+    x = ctx.empty(8 * n)
+    s.ilu0(shift=D)                          # the structure, and the first factors
+    s.set_shift(D)
+    x.zero()
+    s.solve(B, x, maxit=2, **kw)             # warm-up
+    for K in (2, 4, 8):
+        t_s = t_f = 0.0
+        for j in range(K):                   # the caller's loop: set_shift + ilu0_refactor + solve
+            x.zero()
+            ctx.sync()
+            dj = D.ptr + 8 * j * n
+            s.set_shift(dj)
+            s.ilu0_refactor(dj)
+            t_f += s.ilu0_refactor_info()[1]
+            st = s.solve(B.ptr + 8 * j * n, x.ptr + 8 * j * n, maxit=iters, **kw)
+            t_s += st.t_solve
+        s.set_shift(None)
+        line = {"config": name, "precond": "ilu0 per column", "build": build, "n": n, "nnz": nnz, "K": K, "iters": iters,
+                "levels": [st.n_levels_l, st.n_levels_u], "trsv_form_single": st.trsv_form,
+                "columns_col_it_s": K * iters / t_s, "columns_factor_ms_per_column": 1e3 * t_f / K,
+                "columns_call_ms_per_column": 1e3 * (t_s + t_f) / K}
+        if not sequential_only:
+            ctx.set_option("MANY_PRECOND", "batched")
+            x.zero()
+            s.solve_shifts_ilu0(K, D, n, B, n, x, n, maxit=2, tol=1e-8, flags=cm.FLAG_NO_EXIT)          # warm-up
+            x.zero()
+            sts, form_b = s.solve_shifts_ilu0(K, D, n, B, n, x, n, maxit=iters, tol=1e-8, flags=cm.FLAG_NO_EXIT)
+            ctx.set_option("MANY_PRECOND", "columns")
+            t_b, t_fb = sts[0].t_solve, sts[0].t_factor
+            line.update({"batched_form": form_b, "batched_col_it_s": K * iters / t_b, "batched_factor_ms_per_column": 1e3 * t_fb / K,
+                         "batched_call_ms_per_column": 1e3 * (t_b + t_fb) / K, "loop_gain_per_column": t_s / t_b,
+                         "factor_gain_per_column": t_f / t_fb, "call_gain_per_column": (t_s + t_f) / (t_b + t_fb),
+                         "trsm_kernel": s.trsm_kernel(K)})
+        print(json.dumps(line), flush=True)
+    for a in (B, X, x, D):
+        a.free()
+    s.close()
+    ctx.close()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--c4", action="store_true")
@@ -242,6 +302,11 @@ if __name__ == "__main__":
     ap.add_argument("--build", default="this", help="label of the library build in the output lines")
     ap.add_argument("--only", default="", help="run the configs whose name contains this")
     a = ap.parse_args()
+    if a.precond == "ilu0" and a.shifts:
+        for name, it in [("C2_mat10000", 100), ("poisson2000x2000", 3), ("rand2e5x50", 30)]:
+            if a.only in name:
+                run_shifts_precond(name, it, a.sequential_only, a.build)
+        sys.exit(0)
     if a.precond == "ilu0":
         for name, it in [("C2_mat10000", 100), ("C3_poisson4000x2500", 3), ("rand2e5x50", 30)]:
             if a.only in name:
