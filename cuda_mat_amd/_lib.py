@@ -107,6 +107,8 @@ _SIGS = {
     "cudamat_solver_ilu0_shifted": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "cudamat_solver_ilu0_refactor": (C.c_int, [_P, _P]),
     "cudamat_solver_ilu0_refactor_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_size_t)]),
+    "cudamat_solver_set_values": (C.c_int, [_P, _P]),
+    "cudamat_solver_set_values_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "cudamat_solver_block_ilu0": (C.c_int, [_P]),
     "cudamat_solver_ilu0_values": (C.c_int, [_P, _P]),
     "cudamat_solver_ilu0_nnz": (C.c_int, [_P, C.POINTER(C.c_int64)]),

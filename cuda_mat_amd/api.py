@@ -468,6 +468,29 @@ class Solver:
         check(_lib.lib().cudamat_solver_ilu0_refactor_info(self.h, C.byref(cnt), C.byref(sec), C.byref(nb)))
         return cnt.value, sec.value, nb.value
 
+    def set_values(self, val):
+        """new values on the kept structure (cudamat_solver_set_values): val holds nnz doubles in the CSR order of the creation --
+        a DeviceArray, a torch tensor or a raw device pointer, read during the call only, or a host numpy array, which is
+        uploaded to a temporary that is freed after the call.  Bit-identical to a solver created from the new values; the
+        ILU(0) factors stay those of the old ones until ilu0_refactor()."""
+        if isinstance(val, np.ndarray):
+            a = _np(val, np.float64)
+            assert a.size == self.nnz, "set_values: %d values for %d entries" % (a.size, self.nnz)
+            tmp = self.ctx.array(a if self.nnz else np.zeros(1))
+            try:
+                check(_lib.lib().cudamat_solver_set_values(self.h, tmp.ptr))
+            finally:
+                tmp.free()
+        else:
+            check(_lib.lib().cudamat_solver_set_values(self.h, _ptr(val)))
+
+    def set_values_info(self):
+        """(calls since the creation, wall seconds of the last one, device bytes of the value maps, 1 when the last call changed
+        the storage class and the SpMV form is chosen again)"""
+        cnt, sec, nb, reb = C.c_int(), C.c_double(), C.c_size_t(), C.c_int()
+        check(_lib.lib().cudamat_solver_set_values_info(self.h, C.byref(cnt), C.byref(sec), C.byref(nb), C.byref(reb)))
+        return cnt.value, sec.value, nb.value, reb.value
+
     def trsv_form(self):
         """1: dependency-driven triangular solves, 0: one launch per level"""
         f = C.c_int()

@@ -82,6 +82,7 @@ const Option kOptions[] = {
              "1: cudamat_solve_sharded with every rank on device 0 and host-synchronised copies in place of RCCL (debugging aid)"),
     OPT_FLAG("PLAN_CACHE", plan_cache, "0: cudamat_solve does not keep the solver of its last call"),
     OPT_FLAG("ILU0_REFACTOR", ilu0_refactor, "0: cudamat_solve with ILU(0) on a reused plan whose factors belong to another shift repeats the whole ILU(0) set-up instead of the numeric-only refactorisation (cudamat_solver_ilu0_refactor)"),
+    OPT_FLAG("VALUES_REFRESH", values_refresh, "0: cudamat_solve on a cached plan with the same pattern and other values destroys the solver and creates a new one instead of refreshing the values in place (cudamat_solver_set_values)"),
     OPT_ENUM("MANY_FORM", many_form, "auto=0,batched=1,columns=2",
              "several right-hand sides: batched (one SpMM per step for up to 8 columns) / columns (one solve per column); auto: the faster as timed at the first solve"),
     OPT_ENUM("MANY_PRECOND", many_precond, "columns=0,auto=1,batched=2",

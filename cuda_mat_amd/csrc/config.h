@@ -63,6 +63,7 @@ struct Config {
     // ---- drop-in entry point
     int plan_cache = 1;           // PLAN_CACHE         0: cudamat_solve does not keep the solver of its last call
     int ilu0_refactor = 1;        // ILU0_REFACTOR      0: a reused plan whose ILU(0) factors belong to another d repeats the whole ILU(0) set-up
+    int values_refresh = 1;       // VALUES_REFRESH     0: a cached plan with the same pattern and other values is destroyed and created again
     // ---- several right-hand sides
     int many_form = 0;            // MANY_FORM          auto | batched | columns: how cudamat_solver_solve_many runs its columns (0: by timing)
     int many_precond = 0;         // MANY_PRECOND       columns | auto | batched: the same with CUDAMAT_PRECOND_ILU0 (0: column by column; 1: by timing)

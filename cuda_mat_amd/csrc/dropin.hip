@@ -26,6 +26,7 @@
 #include <string.h>
 
 #include "solver.h"
+#include "values.h"
 
 using namespace cm;
 
@@ -175,7 +176,9 @@ struct Uploader {
 // The reference allocates, analyses, solves and frees per call (pbicgstab.cu:157-409).  Here the solver of the last
 // call stays alive: when the next call brings the same matrix (same n, nnz, base and -- compared ON THE DEVICE after
 // the upload, 12 bytes per entry read twice: ~2.5 ms at C4 -- the same row pointers, column indices and values), its
-// device copies, SpMV plan, value dictionary and ILU(0) factors are reused and the call costs upload + loop.
+// device copies, SpMV plan, value dictionary and ILU(0) factors are reused and the call costs upload + loop.  When only the
+// values differ, the cached solver takes them on the structure it holds (set_values, values.hip; option VALUES_REFRESH = 0: a
+// new solver as for any other matrix) and its ILU(0) factors, stale from then on, are refactored before they serve a solve.
 struct PlanCache {
     std::mutex mu;
     cudamat_ctx *ctx = nullptr;
@@ -264,16 +267,17 @@ struct HostSystem {
 };
 
 // ---- a call whose shape matches the cached solver's: upload into scratch arrays, compare on the device, reuse or rebuild
-// from the uploaded copies.  *s_out = the solver to use (the cached one or a new one), *reused says which.
+// from the uploaded copies.  *s_out = the solver to use (the cached one or a new one), *reused says which; *refreshed: the
+// cached one, with this call's values written into it (same pattern, other values).
 int build_or_reuse_candidate(cudamat_ctx *ctx, const Config &cfg, const HostSystem &h, double *d_b, double *d_x, double *d_d,
-                             cudamat_solver **s_out, bool *reused, double *t_up)
+                             cudamat_solver **s_out, bool *reused, bool *refreshed, double *t_up)
 {
     const double t0 = now_s();
     const int n = h.n, nnz = h.nnz, base = h.base;
     DevBuf<int> d_rp, d_ci, flag, tmp;         // the scratch copies of this call: released on the way out
     DevBuf<double> d_val;
     int rc = CUDAMAT_OK;
-    *reused = false;
+    *reused = *refreshed = false;
     *s_out = nullptr;
     CM_HIP(hipSetDevice(ctx->device));
     do {
@@ -293,23 +297,37 @@ int build_or_reuse_candidate(cudamat_ctx *ctx, const Config &cfg, const HostSyst
         }
         *t_up = now_s() - t0;
         // the cached solver holds the matrix rebased to 0: compare the uploaded arrays with it on the device
-        int hflag = 1;
+        // two flag words: [0] the pattern (row pointers, column indices), [1] the values
+        int hflag[2] = {1, 1};
         cudamat_solver *c = g_cache.s;
-        if ((rc = flag.alloc(1))) break;
+        if ((rc = flag.alloc(2))) break;
         // (a flag word that could not be cleared would make any matrix look "different": fail the call instead)
-        if ((rc = CM_RC(hipMemsetAsync(flag, 0, sizeof(int), ctx->stream)))) break;
+        if ((rc = CM_RC(hipMemsetAsync(flag, 0, sizeof(hflag), ctx->stream)))) break;
         rc = tmp.alloc((size_t)nnz > (size_t)n + 1 ? (size_t)nnz : (size_t)n + 1);
         if (!rc) rc = launch_rebase(ctx->stream, (int64_t)n + 1, d_rp, -base, tmp);
         if (!rc) rc = device_equal(ctx->stream, tmp, c->rp, sizeof(int) * ((size_t)n + 1), flag);
         if (!rc && nnz) rc = launch_rebase(ctx->stream, nnz, d_ci, -base, tmp);
         if (!rc && nnz) rc = device_equal(ctx->stream, tmp, c->ci, sizeof(int) * (size_t)nnz, flag);
-        if (!rc && nnz) rc = device_equal(ctx->stream, d_val, c->val, sizeof(double) * (size_t)nnz, flag);
-        if (!rc && hipMemcpyAsync(&hflag, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = CUDAMAT_ERR_HIP;
+        if (!rc && nnz) rc = device_equal(ctx->stream, d_val, c->val, sizeof(double) * (size_t)nnz, flag + 1);
+        if (!rc && hipMemcpyAsync(hflag, flag, sizeof(hflag), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = CUDAMAT_ERR_HIP;
         if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = CUDAMAT_ERR_HIP;
         if (rc) break;
-        if (hflag == 0) {
+        if (hflag[0] == 0 && hflag[1] == 0) {
             *s_out = g_cache.s;
             *reused = true;
+        } else if (hflag[0] == 0 && cfg.values_refresh && !c->sharded) {
+            // same pattern, other values: the numbers are refreshed on the kept structure (option VALUES_REFRESH = 0: destroy +
+            // create).  The factors the solver holds are stale from here on: the ILU(0) entry points refactor them.
+            if ((rc = set_values(c, d_val))) {       // (a solver whose numbers may be half written does not stay in the cache)
+                char saved[512];
+                snprintf(saved, sizeof(saved), "%s", cudamat_last_error());
+                cudamat_solver_destroy(g_cache.s);
+                g_cache.s = nullptr;
+                set_error("%s", saved);
+                break;
+            }
+            *s_out = g_cache.s;
+            *reused = *refreshed = true;
         } else {                     // same shape, another matrix: the old solver goes, its context stays
             cudamat_solver_destroy(g_cache.s);
             g_cache.s = nullptr;
@@ -522,7 +540,7 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
     }
     DevBuf<double> d_b, d_x, d_d;              // the call's right-hand sides, iterates and shifts on the device
     cudamat_solver *s = nullptr;
-    bool reused = false, built_ilu = false;
+    bool reused = false, refreshed = false, built_ilu = false;
     int rc = CUDAMAT_OK;
     cudamat_stats st;
     memset(&st, 0, sizeof(st));
@@ -533,7 +551,7 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
         if ((rc = d_x.alloc((size_t)n * (size_t)h.nrhs))) break;
         if (h.d && (rc = d_d.alloc(h.d_count()))) break;
         if (candidate) {
-            if ((rc = build_or_reuse_candidate(ctx, cfg, h, d_b, d_x, d_d, &s, &reused, &t_up))) break;
+            if ((rc = build_or_reuse_candidate(ctx, cfg, h, d_b, d_x, d_d, &s, &reused, &refreshed, &t_up))) break;
         } else {
             if ((rc = build_beside_upload(ctx, cfg, h, d_b, d_x, d_d, &s, &t_up, speculative, precond, loop))) break;
         }
@@ -547,7 +565,8 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
             // shift, so kept factors serve only a d that is byte-identical to the one they were built from (the solver's copy);
             // otherwise the factorisation is redone and the rest of the plan stays.  (The batched calls keep their refusals.)
             const double *d_factor = !many && h.d && precond == CUDAMAT_PRECOND_ILU0 ? d_d.get() : nullptr;
-            bool have = reused && s->has_ilu && !s->ilu_block && s->ilu_shifted == (d_factor != nullptr) &&
+            // (factors of values the matrix no longer holds -- a refreshed plan -- count as not there: never a lagged M here)
+            bool have = reused && s->has_ilu && !s->ilu_stale && !s->ilu_block && s->ilu_shifted == (d_factor != nullptr) &&
                         (!d_factor || s->ilu_d);
             if (have && d_factor) {
                 DevBuf<int> flag;
@@ -588,8 +607,10 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
     strncpy(saved, cudamat_last_error(), sizeof(saved) - 1);
     saved[sizeof(saved) - 1] = 0;
     st.t_upload = t_up;
-    st.plan_reused = reused ? 1 : 0;
-    if (reused) { st.t_setup = 0.0; st.t_tune = 0.0; }                       // (they describe the call that built the plan)
+    // (plan_reused = 1 says "the same matrix, pattern and values: nothing was set up"; a refreshed plan reports the refresh as its set-up)
+    const double t_refresh = refreshed && s ? s->values_seconds : 0.0;
+    st.plan_reused = reused && !refreshed ? 1 : 0;
+    if (reused) { st.t_setup = t_refresh; st.t_tune = 0.0; }                 // (otherwise they describe the call that built the plan)
     if (reused && !built_ilu) { st.t_analysis = 0.0; st.t_factor = 0.0; }
     // keep the solver for the next call (it owns its own copies of the matrix; the upload buffers go)
     cudamat_solver *const old = g_cache.s;       // the previous call's solver, when it is still alive (may be s itself)
@@ -623,7 +644,7 @@ int solve_host_locked(const Config &cfg, const HostSystem &h, bool speculative, 
         for (int j = 0; j < h.nrhs && rc == CUDAMAT_OK; j++) {
             out[j].t_upload = st.t_upload;
             out[j].plan_reused = st.plan_reused;
-            if (reused) { out[j].t_setup = 0.0; out[j].t_tune = 0.0; }
+            if (reused) { out[j].t_setup = t_refresh; out[j].t_tune = 0.0; }
             out[j].t_total = st.t_total;
         }
     } else if (out) {

@@ -30,6 +30,7 @@
 #include "device.h"
 #include "ilu.h"
 #include "trsm.h"
+#include "values.h"
 
 using namespace cm;
 
@@ -563,8 +564,11 @@ int ilu0_release(cudamat_solver *s)
     s->b_perm.reset();
     s->xd_idx.reset();
     s->d_perm.reset();
+    s->src_perm.reset();
+    s->src_perm_len = 0;
     s->perm_ready = false;
     s->perm_failed = false;
+    s->ilu_stale = false;
     s->lu.reset();
     s->diag_pos.reset();
     s->pm_own_rp.reset();
@@ -1715,6 +1719,7 @@ static int ilu0_setup_body(cudamat_solver *s, IluPlans *pl, const double *d_fact
     }
     s->has_ilu = true;
     s->ilu_shifted = d_factor != nullptr;
+    s->ilu_stale = false;
     return CUDAMAT_OK;
 }
 
@@ -1779,6 +1784,62 @@ int ilu_perm_matrix(cudamat_solver *s)
     return CUDAMAT_OK;
 }
 
+// ---- new values of the matrix itself (cudamat_solver_set_values, values.hip) and the permuted matrix
+// The map "stored entry of pb_perm -> CSR position": the build above once more on tags, without a dictionary, a placement or a
+// line of output -- the tag travels through launch_sort_rows and pb_build as the value did.  The U positions were released
+// when the permuted matrix was built; they are recomputed from U.row_of, as refactor_maps does.
+int ilu_perm_value_map(cudamat_solver *s, const double *tags, DevBuf<int> *map, int64_t *len)
+{
+    CM_ARG(s->perm_ready && s->L.lm && s->U.lm && s->pb_perm.P, "the permuted matrix is not built");
+    hipStream_t st = s->ctx->stream;
+    const int n = s->n;
+    const int64_t nnz = s->pm_nnz;
+    DevBuf<int> posU, d_rp, d_ci, d_len;
+    DevBuf<double> d_val;
+    CM_TRY(posU.alloc((size_t)n));
+    CM_TRY(d_rp.alloc((size_t)n + 1));
+    CM_TRY(d_len.alloc((size_t)n));
+    CM_TRY(d_ci.alloc((size_t)nnz));
+    CM_TRY(d_val.alloc((size_t)nnz));
+    const unsigned gp = (unsigned)(((long long)n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_invert_perm, dim3(gp), dim3(kBlock), 0, st, n, s->U.row_of, posU);
+    hipLaunchKernelGGL(k_perm_row_len, dim3(gp), dim3(kBlock), 0, st, n, s->pm_rp, s->L.row_of, d_len);
+    CM_HIP(hipGetLastError());
+    CM_TRY(device_exclusive_scan(st, n, d_len, d_rp));
+    CM_TRY(launch_sort_rows(st, n, s->pm_rp, s->L.row_of, d_rp, s->pm_ci, tags, posU, d_ci, d_val));
+    Config cfg = s->ctx->cfg;
+    cfg.pb_place = 0;                       // a temporary: nothing to place, nothing to print
+    cfg.verbose = 0;
+    PbPlan tmp;
+    CM_TRY(pb_build(st, cfg, n, n, nnz, d_rp, d_ci, d_val, &tmp, nullptr, nullptr));
+    const int rc = pb_value_map(st, s->pb_perm, tmp, map, len);
+    pb_free(&tmp);
+    return rc;
+}
+
+int ilu_perm_drop(cudamat_solver *s)
+{
+    IluPlans *pl = plans_of(s, false);
+    if (!pl || !s->perm_ready) return CUDAMAT_OK;
+    hipStream_t st = s->ctx->stream;
+    const int n = s->n;
+    if (!pl->posU) {
+        CM_TRY(pl->posU.alloc((size_t)n));
+        hipLaunchKernelGGL(k_invert_perm, dim3((unsigned)(((long long)n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, n, s->U.row_of, pl->posU);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+            pl->posU.reset();
+            set_error("permutation maps failed");
+            return CUDAMAT_ERR_HIP;
+        }
+    }
+    pb_free(&s->pb_perm);
+    valdict_free(&s->vd_perm);
+    s->src_perm.reset();
+    s->src_perm_len = 0;
+    s->perm_ready = false;
+    return CUDAMAT_OK;
+}
+
 // ---------------------------------------------------------------- numeric-only refactorisation (cudamat_solver_ilu0_refactor)
 // The factors of A0 + diag(d') on the structure the solver already holds: lu is recomputed by ilu0_numeric, then every stored
 // copy of its values is refreshed in place -- unsplit factors by k_fill_factor over the kept row pointers, split ones by the
@@ -1787,32 +1848,9 @@ int ilu_perm_matrix(cudamat_solver *s)
 // The refresh streams over DESTINATION order: 4 bytes of map and 8 bytes of store per entry are sequential, the 8-byte read of
 // lu is the one gather.  For the near parts the map is increasing inside a row and the rows of a level are increasing, so the
 // gather walks lu nearly in order; for a far plan it follows the plan's (column block, row block, row, column) order, i.e. it
-// revisits a sub-block's rows once per column block.  Algorithmic bytes per entry: 4 + 8 + 8 = 20.
-template <int VEC>
-__global__ __launch_bounds__(kBlock) void k_refresh_values(int64_t count, const int *src, const double *lu, double *val)
-{
-    vec_loop<VEC>(count, [&](int64_t i, auto w) {
-        constexpr int W = decltype(w)::value;
-        int at[W];
-        double v[W];
-        if constexpr (W == 2) {
-            const int2 q = ((const int2 *)src)[i];
-            at[0] = q.x;
-            at[1] = q.y;
-        } else {
-            at[0] = src[i];
-        }
-#pragma unroll
-        for (int j = 0; j < W; j++) v[j] = at[j] >= 0 ? lu[at[j]] : 0.0;        // (-1: an alignment pad of a blocked copy)
-        store_row<W>(val, i, v, kAll);
-    });
-}
-
-static int launch_refresh_values(hipStream_t s, int64_t count, const int *src, const double *lu, double *val)
-{
-    if (count <= 0) return CUDAMAT_OK;
-    CM_VEC_LAUNCH(all_aligned16(val) && (((uintptr_t)src) & 7) == 0, vec_grid(count), k_refresh_values<VEC>, count, src, lu, val);
-}
+// revisits a sub-block's rows once per column block.  Algorithmic bytes per entry: 4 + 8 + 8 = 20.  The gather
+// kernel (launch_refresh_values) and the tags the maps are read from live in values.hip, which refreshes the matrix' own
+// copies the same way.
 
 // dinv[pr] = 1 / (U's diagonal of the row at position pr): the expression of k_fill_factor, one division, one rounding
 __global__ __launch_bounds__(kBlock) void k_refresh_dinv(int64_t n, const int *row_of, const int *diag_pos, const double *lu, double *dinv)
@@ -1820,20 +1858,6 @@ __global__ __launch_bounds__(kBlock) void k_refresh_dinv(int64_t n, const int *r
 #pragma clang fp contract(off)
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t pr = (int64_t)blockIdx.x * kBlock + threadIdx.x; pr < n; pr += stride) dinv[pr] = 1.0 / lu[diag_pos[row_of[pr]]];
-}
-
-// the map of one array filled from a value array that held every entry's (position in lu) + 1 as a double (exact: < 2^31):
-// 0.0 is an alignment pad -> -1
-__global__ __launch_bounds__(kBlock) void k_src_from_tags(int64_t count, const double *tag, int *src)
-{
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) src[i] = (int)tag[i] - 1;
-}
-
-__global__ __launch_bounds__(kBlock) void k_tags(int64_t count, double *tag)
-{
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) tag[i] = (double)(i + 1);
 }
 
 // The maps of one split factor.  No second builder: the pipeline of the set-up (k_fill_factor -> split_entries -> pb_build per
@@ -1869,8 +1893,7 @@ static int refactor_maps_of(cudamat_solver *s, bool upper, const TriFactor &F, c
     fci.reset();
     fval.reset();
     CM_TRY(out->near.alloc((size_t)sp.nnz_near));
-    if (sp.nnz_near) hipLaunchKernelGGL(k_src_from_tags, dim3(row_grid(sp.nnz_near)), dim3(kBlock), 0, st, sp.nnz_near, sp.nval, out->near);
-    CM_HIP(hipGetLastError());
+    CM_TRY(launch_map_from_tags(st, sp.nnz_near, sp.nval, out->near));
     *bytes += sizeof(int) * (size_t)sp.nnz_near;
     out->far.clear();
     out->far.resize((size_t)K);
@@ -1895,8 +1918,7 @@ static int refactor_maps_of(cudamat_solver *s, bool upper, const TriFactor &F, c
         if (!rc) rc = CM_RC(hipMemcpy(&total, tmp.cstart + tmp.NCB, sizeof(int), hipMemcpyDeviceToHost));
         if (!rc) rc = out->far[(size_t)g].alloc((size_t)total);
         if (!rc && total > 0) {
-            hipLaunchKernelGGL(k_src_from_tags, dim3(row_grid(total)), dim3(kBlock), 0, st, (int64_t)total, tmp.pv, out->far[(size_t)g]);
-            rc = CM_RC(hipGetLastError());
+            rc = launch_map_from_tags(st, (int64_t)total, tmp.pv, out->far[(size_t)g]);
             if (!rc) rc = CM_RC(hipStreamSynchronize(st));
         }
         pb_free(&tmp);
@@ -1921,8 +1943,8 @@ static int refactor_maps(cudamat_solver *s, IluPlans *pl)
     const unsigned gp = (unsigned)(((long long)n + kBlock - 1) / kBlock);
     if (n) hipLaunchKernelGGL(k_invert_perm, dim3(gp), dim3(kBlock), 0, st, n, s->L.row_of, posL);
     if (n) hipLaunchKernelGGL(k_invert_perm, dim3(gp), dim3(kBlock), 0, st, n, s->U.row_of, posU);
-    hipLaunchKernelGGL(k_tags, dim3(row_grid(s->pm_nnz)), dim3(kBlock), 0, st, (int64_t)s->pm_nnz, tags);
     CM_HIP(hipGetLastError());
+    CM_TRY(launch_value_tags(st, (int64_t)s->pm_nnz, tags));
     size_t bytes = 0;
     int rc = refactor_maps_of(s, false, s->L, pl->L, posL, tags, &pl->srcL, &bytes);
     if (!rc) rc = refactor_maps_of(s, true, s->U, pl->U, posU, tags, &pl->srcU, &bytes);
@@ -2005,6 +2027,7 @@ int ilu0_refactor(cudamat_solver *s, const double *d_factor, bool keep_shift)
     const int rc = numbers();
     if (rc) return ilu0_fail(s, rc);        // (a zero pivot, as after a failed set-up: no factors)
     s->ilu_shifted = d_factor != nullptr;
+    s->ilu_stale = false;
     pl->refactors++;
     pl->refactor_seconds = now_s() - t0;
     s->t_factor = pl->refactor_seconds;     // (cudamat_stats.t_factor of the next solve: what these factors cost)

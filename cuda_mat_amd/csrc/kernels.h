@@ -133,6 +133,9 @@ int plan_spmv_compress(hipStream_t s, const Config &cfg, int n_rows, int64_t nnz
 int plan_spmv_align(hipStream_t s, const Config &cfg, int n_rows, int64_t nnz, const int *rp, const double *val, SpmvPlan *plan);
 int plan_spmv_dict(hipStream_t s, int n_rows, int64_t nnz, const int *rp, const unsigned char *vidx, const double *dict,
                    SpmvPlan *plan);
+// new values into whichever of those two copies the plan holds (same storage class; no-op for a plan without one)
+int plan_spmv_refresh_values(hipStream_t s, int n_rows, int64_t nnz, const int *rp, const double *val, const unsigned char *vidx,
+                             const double *dict, SpmvPlan *plan);
 
 int vec_grid(int64_t n);
 // workgroups of a grid-stride kernel over `rows` items, `per_block` of them per workgroup and sweep: at least 1, at most 4096

@@ -187,6 +187,18 @@ struct cudamat_solver {
     int loop_fallbacks = 0;     // solves redone with the three-launch loop for that reason
 
     cm::ManyWork many;          // several right-hand sides (loops_batch.hip)
+
+    // new values on the kept structure (cudamat_solver_set_values, values.hip): where in `val` every stored entry of the blocked
+    // copy (src_pb beside pb) and of the permuted matrix' blocked copy (src_perm beside pb_perm) comes from, one int per entry up
+    // to cstart[NCB] (-1: an alignment pad).  Built at the first call that finds the copy, released with it.
+    cm::DevBuf<int> src_pb, src_perm;
+    int64_t src_pb_len = 0, src_perm_len = 0;
+    int values_count = 0;            // calls since the creation
+    double values_seconds = 0.0;     // wall time of the last one, stream drained
+    int values_rebuilt = 0;          // the last one changed the storage class (dictionary <-> fp64): copies dropped, form chosen again
+    // the factors (ILU(0) or block-Jacobi) are those of values the matrix no longer holds: a lagged preconditioner until the next
+    // factorisation (ilu0_refactor, ilu0, block_ilu0), which clears this
+    bool ilu_stale = false;
 };
 
 namespace cm {
@@ -244,6 +256,8 @@ int trsv_form_code(cudamat_solver *s);           // 0 level launches, 1 dependen
 void trsv_group_counts(cudamat_solver *s, int *groups_l, int *groups_u);   // hybrid factors: groups of levels (0: not split)
 void trsv_disable_syncfree(cudamat_solver *s);   // sticky: level-by-level kernels from now on
 void many_release(cudamat_solver *s);            // the buffers of the batched loop (loops_batch.hip)
+// the SpMV copies in other layouts and the value maps that belong to them: gone, the form is chosen again at the next use
+void spmv_copies_drop(cudamat_solver *s);
 // ---- loops.hip: what the single and the batched host loop (loops_batch.hip) share
 // The lagged look at the progress word of iteration j, published through pinned memory by that iteration's last kernel:
 // *word = the word once its upper half says j + 1.  Waits at most 30 s for that, then gives the stream's queued work a

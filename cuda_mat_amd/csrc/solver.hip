@@ -42,6 +42,16 @@ static void free_work(cudamat_solver *s)
     for (DevBuf<double> *q : vs) q->reset();
 }
 
+void spmv_copies_drop(cudamat_solver *s)
+{
+    pb_free(&s->pb);
+    sell_free(&s->sell);
+    pat_free(&s->pat);
+    s->src_pb.reset();
+    s->src_pb_len = 0;
+    s->spmv_mode = -1;
+}
+
 int ensure_work(cudamat_solver *s)
 {
     if (s->r) return CUDAMAT_OK;
@@ -277,11 +287,8 @@ extern "C" int cudamat_solver_set_comm(cudamat_solver *s, const cudamat_comm *co
     CM_ARG(s, "solver is NULL");
     CM_HIP(hipStreamSynchronize(s->ctx->stream));
     free_work(s);
-    pb_free(&s->pb);
-    sell_free(&s->sell);
-    pat_free(&s->pat);
+    spmv_copies_drop(s);
     ilu0_release(s);           // factors belong to the old partition
-    s->spmv_mode = -1;
     s->overlap = false;
     s->agreed = false;
     s->windowed = false;

@@ -386,6 +386,29 @@ int plan_spmv_dict(hipStream_t s, int n_rows, int64_t nnz, const int *rp, const 
     return rc == CUDAMAT_ERR_NOMEM ? CUDAMAT_OK : rc;
 }
 
+// The value stage once more into the buffers the plan holds (cudamat_solver_set_values): the fill pass of whichever of the two
+// copies above exists, over the kept tile bases -- the offsets are rewritten with what they hold, the idle slots keep their 0.
+// The copy keeps its storage class: the caller has checked that vidx / dict are there exactly when the plan holds indices.
+int plan_spmv_refresh_values(hipStream_t s, int n_rows, int64_t nnz, const int *rp, const double *val, const unsigned char *vidx,
+                             const double *dict, SpmvPlan *plan)
+{
+    if (!plan->stream_rows || !plan->c_off16 || nnz <= 0) return CUDAMAT_OK;
+    const int R = plan->stream_rows;
+    const long long threads = (long long)n_rows * 8;
+    const unsigned grid = (unsigned)((threads + kBlock - 1) / kBlock);
+    if (plan->d_pbase) {
+        if (!vidx || !dict) { set_error("plan_spmv_refresh_values: the plan holds dictionary indices and the values have no dictionary"); return CUDAMAT_ERR_ARG; }
+        hipLaunchKernelGGL(k_tile_pad_fill, dim3(grid), dim3(kBlock), 0, s, n_rows, R, rp, plan->c_off16, vidx, plan->d_pbase, plan->d_off16,
+                           plan->d_val8);
+        plan->c_dict = dict;
+    } else if (plan->a_base) {
+        hipLaunchKernelGGL(k_tile_align_fill, dim3(grid), dim3(kBlock), 0, s, n_rows, R, rp, plan->c_off16, val, plan->a_base, plan->a_off16,
+                           plan->a_val);
+    }
+    CM_HIP(hipGetLastError());
+    return CUDAMAT_OK;
+}
+
 // ------------------------------------------------------------ SpMV, skewed row lengths
 // Tiles of kTileNnz consecutive ENTRIES (not rows): every workgroup streams the same number of entries
 // whatever the row-length distribution (a few rows of 1e5 entries among rows of 8 leave the

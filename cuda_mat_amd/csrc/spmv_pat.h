@@ -35,6 +35,9 @@ struct PatPlan {
 int pat_build(hipStream_t st, int n, int64_t nnz, const int *rp, const int *ci, const double *val, PatPlan *out,
               double max_fill = 0.0, const ValDict *vd = nullptr);
 void pat_free(PatPlan *p);
+// new values (CSR order of `rp`) into the copy, which keeps its storage class: fp64 slots from `val`, or index words from
+// vd->idx with the plan re-pointed at vd's dictionary (the caller has checked that vd->n > 0 exactly when the copy holds indices)
+int pat_refresh_values(hipStream_t st, PatPlan *plan, const int *rp, const double *val, const ValDict *vd);
 // y = alpha*(A x + d.*xd) + beta*y with the same fused dot / prologue options as launch_spmv
 int launch_spmv_pat(hipStream_t st, const PatPlan &plan, const SpmvArgs &a);
 

@@ -256,6 +256,24 @@ int pat_build(hipStream_t st, int n, int64_t nnz, const int *rp, const int *ci, 
     return CUDAMAT_OK;
 }
 
+// the fill pass of pat_build once more (cudamat_solver_set_values): both layouts are closed-form in (row, entry of the row)
+int pat_refresh_values(hipStream_t st, PatPlan *p, const int *rp, const double *val, const ValDict *vd)
+{
+    const long long padded = (long long)p->nchunks * kPatChunk;
+    if (padded <= 0) return CUDAMAT_OK;
+    const unsigned grid = (unsigned)((padded + kBlock - 1) / kBlock);
+    if (p->vidx) {
+        if (!vd || vd->n <= 0) { set_error("pat_refresh_values: the copy holds dictionary indices and the values have no dictionary"); return CUDAMAT_ERR_ARG; }
+        hipLaunchKernelGGL(k_pat_fill_idx, dim3(grid), dim3(kBlock), 0, st, p->n, padded, p->vword, rp, vd->idx, p->vidx);
+        p->dict = vd->dict;
+        p->ndict = vd->n;
+    } else {
+        hipLaunchKernelGGL(k_pat_fill, dim3(grid), dim3(kBlock), 0, st, p->n, p->nchunks, p->W, rp, val, p->val);
+    }
+    CM_HIP(hipGetLastError());
+    return CUDAMAT_OK;
+}
+
 template <int WMAX>
 __global__ __launch_bounds__(kBlock) void k_spmv_pat(SpmvArgs a, int nchunks, int W, int tiles_per_block, const unsigned char *pid,
                                                      const int *tab, int npat_rows, const double *pval)

@@ -23,6 +23,8 @@ struct SellPlan {
 int sell_build(hipStream_t st, int n, int64_t nnz, const int *rp, const int *ci, const double *val, SellPlan *out,
                double max_fill = 0.0);
 void sell_free(SellPlan *p);
+// new values (CSR order of `rp`) into the slots the copy holds: the layout is closed-form in (row, entry of the row)
+int sell_refresh_values(hipStream_t st, const SellPlan &plan, const int *rp, const double *val);
 // y = alpha*(A x + d.*xd) + beta*y with the same fused dot / prologue options as launch_spmv
 int launch_spmv_sell(hipStream_t st, const SellPlan &plan, const SpmvArgs &a);
 

@@ -126,6 +126,27 @@ int sell_build(hipStream_t st, int n, int64_t nnz, const int *rp, const int *ci,
     return CUDAMAT_OK;
 }
 
+// k_sell_fill's values alone (cudamat_solver_set_values): the columns, the permutation and the padding pattern stay
+__global__ __launch_bounds__(kBlock) void k_sell_refresh(int nchunks, const int *rp, const double *val, const int *perm, const int *len,
+                                                         const long long *chunk_off, double *sval)
+{
+    const int c = blockIdx.x * (kBlock / kChunk) + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (c >= nchunks) return;
+    const int row = perm[(size_t)c * kChunk + lane], l = len[(size_t)c * kChunk + lane];
+    const long long base = chunk_off[c] * kChunk + lane;
+    const int s = row >= 0 ? rp[row] : 0;
+    for (int j = 0; j < l; j++) sval[base + (long long)j * kChunk] = val[s + j];
+}
+
+int sell_refresh_values(hipStream_t st, const SellPlan &p, const int *rp, const double *val)
+{
+    if (p.nchunks <= 0) return CUDAMAT_OK;
+    hipLaunchKernelGGL(k_sell_refresh, dim3((unsigned)((p.nchunks + 3) / 4)), dim3(kBlock), 0, st, p.nchunks, rp, val, p.perm, p.len,
+                       p.chunk_off, p.val);
+    CM_HIP(hipGetLastError());
+    return CUDAMAT_OK;
+}
+
 __global__ __launch_bounds__(kBlock) void k_spmv_sell(SpmvArgs a, int nchunks, int chunks_per_block, const int *perm,
                                                       const int *len, const long long *chunk_off, const double *sval,
                                                       const int *scol)

@@ -139,7 +139,9 @@ typedef struct cudamat_stats {
     double t_tune;         /* s, of t_setup: timed candidate launches (0 when the choice needed none)                    */
     int spmv_mode;         /* the SpMV form the solve used: 0 CSR forms, 1 blocked two-phase, 2 SELL-C-sigma             */
     int plan_reused;       /* cudamat_solve: 1 = the previous call brought the same matrix (pattern AND values): its solver
-                            * -- device copies, SpMV plan, value dictionary, ILU(0) factors -- was reused; 0 = built anew */
+                            * -- device copies, SpMV plan, value dictionary, ILU(0) factors -- was reused; 0 = built anew,
+                            * or -- same pattern, other values -- kept with the new values written into it
+                            * (cudamat_solver_set_values; t_setup is then that call's time, t_tune 0)                     */
     /* hybrid triangular solves (big factors with wide, scattered levels): groups of consecutive levels per factor; one
      * application of L^-1 (U^-1) = `groups` dependency-driven launches over the entries inside a group + `groups - 1`
      * blocked two-phase SpMVs over the entries whose column lies in an earlier group.  0: the factor is not split.    */
@@ -312,6 +314,25 @@ int cudamat_solver_ilu0_refactor(cudamat_solver *s, const double *d_factor);
  * wall time of the last one (stream drained), *map_bytes = device bytes of the value maps (0 before the first
  * refactorisation and for unsplit factors).  Any of the three may be NULL.                                             */
 int cudamat_solver_ilu0_refactor_info(cudamat_solver *s, int *count, double *seconds_last, size_t *map_bytes);
+/* New VALUES for the resident matrix on the structure the solver holds: val (device, nnz doubles in the CSR order of the
+ * creation) is read during the call only, and the call ends with the stream drained.  Afterwards the solver shows what a
+ * solver created from (rowptr, colidx, val) under the same switches shows, bit for bit wherever that solver runs the same
+ * kernels: products (spmv, spmm, spmm_shifts), every loop form of solve / solve_many / solve_shifts and -- once the factors
+ * have been brought up to date -- the preconditioned ones.  Everything that depends on the pattern alone is kept: validation,
+ * launch plans, compressed indices, the blocked copy's geometry and placement, the chosen SpMV form and the timings behind
+ * it, the set-up of ILU(0).  Every copy of the values is refreshed in place; the blocked copies go through a map of one int
+ * per stored entry that the first call builds (see _info).  A copy holds fp64 values or 8-bit indices into the value
+ * dictionary; when the new values change that (a dictionary appears or disappears) nothing is converted -- the copies are
+ * dropped and the form is chosen again at the next use, as in a new solver.
+ * The ILU(0) / block-Jacobi factors are NOT touched: they remain those of the old values, a lagged preconditioner that a
+ * solve may still use, until cudamat_solver_ilu0_refactor (or _ilu0 / _ilu0_shift / _block_ilu0) recomputes them from the
+ * new matrix.  The shift, the work vectors, the histories and the batched loop's form choice stay.
+ * One GPU, whole matrix: CUDAMAT_ERR_ARG for a sharded solver and for a NULL val; the solver is unchanged then.           */
+int cudamat_solver_set_values(cudamat_solver *s, const double *val);
+/* Without touching the device: *count = calls since the creation, *seconds_last = wall time of the last one (stream drained),
+ * *map_bytes = device bytes of the value maps the solver holds (0 before the first call and for forms that need none),
+ * *rebuilt_last = 1 when the last call changed the storage class and the SpMV form is chosen again.  Any may be NULL.     */
+int cudamat_solver_set_values_info(cudamat_solver *s, int *count, double *seconds_last, size_t *map_bytes, int *rebuilt_last);
 /* the same on the rank's DIAGONAL BLOCK (rows and columns it owns) -- allowed in a sharded solver;
  * no collective is involved, neither here nor in the preconditioning steps            */
 int cudamat_solver_block_ilu0(cudamat_solver *s);
