@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libcudamat_hip.so")
 
 OK = 0
 PRECOND_NONE, PRECOND_ILU0, PRECOND_BLOCK_ILU0 = 0, 1, 2
-LOOP_PBICGSTAB, LOOP_PBICGSTAB2, LOOP_PIPELINED = 0, 1, 2
+LOOP_PBICGSTAB, LOOP_PBICGSTAB2, LOOP_PIPELINED, LOOP_BICGSTAB_L2 = 0, 1, 2, 3
 FLAG_DEBUG, FLAG_PROFILE, FLAG_NO_EXIT, FLAG_X0_ONES, FLAG_GUARD = 1, 2, 4, 8, 16
 
 

@@ -5,6 +5,8 @@ Names and argument meaning follow pbicgstab.h / mmio_wrapper.h of the reference:
   bicgstab_d(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug)      pbicgstab.h:116 (overload)
   bicgstab_lu_precond(n, nnz, A, iA, jA, b, maxit, tol, debug)       pbicgstab.h:119
   bicgstab_d_lu_precond(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug)   ILU(0) of A0 + diag(d), the loop with d (new)
+  bicgstab_l2(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug)     BiCGSTAB(2), no preconditioner; d, x0 may be None (new)
+  bicgstab_l2_lu_precond(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug)   BiCGSTAB(2) with ILU(0) of A0 + diag(d) (new)
   bicgstab_many(n, nnz, A, iA, jA, B, maxit, tol, d, x0)             bicgstab / bicgstab_d for the columns of B (new)
   bicgstab_lu_precond_many(n, nnz, A, iA, jA, B, maxit, tol)         bicgstab_lu_precond for the columns of B (new)
   bicgstab_d_many(n, nnz, A0, iA0, jA0, D, x0, B, maxit, tol)        bicgstab_d with shift D[:, j] for column j of B (new)
@@ -23,7 +25,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (FLAG_DEBUG, FLAG_GUARD, FLAG_NO_EXIT, FLAG_PROFILE, FLAG_X0_ONES, LOOP_PBICGSTAB,
+from ._lib import (FLAG_DEBUG, FLAG_GUARD, FLAG_NO_EXIT, FLAG_PROFILE, FLAG_X0_ONES, LOOP_BICGSTAB_L2, LOOP_PBICGSTAB,
                    LOOP_PBICGSTAB2, LOOP_PIPELINED, PRECOND_BLOCK_ILU0, PRECOND_ILU0, PRECOND_NONE, Comm, CudamatError, Stats, check)
 
 
@@ -97,6 +99,21 @@ def bicgstab_d_lu_precond(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug=Fals
     if _GPUS > 1:
         raise ValueError("ILU(0) of the shifted matrix is one-GPU only: use_gpus(%d) is set (block-Jacobi takes no shift)" % _GPUS)
     x, st = _solve(n, nnz, A0, iA0, jA0, d, x0, b, PRECOND_ILU0, LOOP_PBICGSTAB, maxit, tol, debug)
+    return True, x, st.t_solve, st
+
+
+def bicgstab_l2(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug=False):
+    """solve (A0 + I*d) x = b from x0 with BiCGSTAB(2) (LOOP_BICGSTAB_L2: for the systems on which BiCGSTAB stalls), no
+    preconditioner; d None: no shift, x0 None: ones.  maxit and stats.iters count sweeps of four products each.  Mirrors
+    bicgstab_l2 of include/pbicgstab.h: `ok` is stats.converged.  One GPU only (use_gpus(k > 1): CudamatError)."""
+    x, st = _solve(n, nnz, A0, iA0, jA0, d, x0, b, PRECOND_NONE, LOOP_BICGSTAB_L2, maxit, tol, debug)
+    return bool(st.converged), x, st.t_solve, st
+
+
+def bicgstab_l2_lu_precond(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug=False):
+    """bicgstab_l2 with the ILU(0) preconditioner of A0 + diag(d) (of A0 when d is None), applied from the right.  Like
+    bicgstab_lu_precond `ok` is True whenever the solve ran; convergence is in stats.converged."""
+    x, st = _solve(n, nnz, A0, iA0, jA0, d, x0, b, PRECOND_ILU0, LOOP_BICGSTAB_L2, maxit, tol, debug)
     return True, x, st.t_solve, st
 
 

@@ -119,6 +119,21 @@ struct LoopState {
     double alpha2[2];  // pipelined loop: alpha of iteration k in slot k & 1
 };
 
+// The scalars of CUDAMAT_LOOP_BICGSTAB_L2 (bicgstab_l2.hip).  They live in the slot BEHIND the LoopState of the same solve -- the
+// solver allocates two slots, l2_state(la.st) is the second -- so LoopArgs and LoopState keep their layout for every other loop.  No
+// kernel reads a field its own leader writes: the j = 0 kernels write rho_a / alpha_a and read the others, the j = 1
+// kernels write rho_b / alpha_b, the minimal-residual kernel writes omega.  A sweep with LoopState::it == 0 takes the start
+// values rho0 = 1, alpha = 0, omega = 1 instead of reading them.
+struct L2State {
+    double rho_a;    // rho0 after j = 0 (r0.r~)
+    double alpha_a;  // alpha of j = 0
+    double rho_b;    // rho0 after j = 1 (r1.r~): the next sweep's rho0
+    double alpha_b;  // alpha of j = 1: the next sweep's alpha
+    double omega;    // g2 of the minimal-residual step
+};
+static_assert(sizeof(L2State) <= sizeof(LoopState), "L2State takes the LoopState slot behind the solve's own");
+__host__ __device__ inline L2State *l2_state(LoopState *st) { return reinterpret_cast<L2State *>(st + 1); }
+
 enum Check { CHECK_NONE = 0, CHECK_HALF = 1, CHECK_FULL = 2 };
 
 }  // namespace cm

@@ -182,6 +182,29 @@ int launch_pipe_b(hipStream_t s, LoopArgs la, ScalarSrc A, int64_t n, const doub
 int launch_residual(hipStream_t s, const LoopArgs &la, int64_t n, const double *f, const double *ax, double *r);
 int launch_pipe_dots(hipStream_t s, const LoopArgs &la, int64_t n, const double *rw, const double *r, const double *w, const double *sv,
                      const double *z, double *parts, int *nparts);
+// BiCGSTAB(2), CUDAMAT_LOOP_BICGSTAB_L2 (bicgstab_l2.hip): the six vector kernels of one sweep, in launch order.  Every scalar
+// is formed in the prologue of the kernel that consumes it, from the partials of the kernel or SpMV that produced its dot; a
+// breakdown (a zero divisor, a scalar that is not finite) freezes the loop in state 3 unless la.no_exit.
+// once, after launch_init: parts = (r0.r0, r0.r0), stride 2, summed in the pair order whatever the alignment of the caller's b
+int launch_l2_start(hipStream_t s, int64_t n, const double *r0, double *parts, int *nparts);
+// the stopping test of the sweep before (full = (r0.r~, r0.r0), stride 2); rho0 = -omega rho0, beta; u0 = r0 - beta u0
+int launch_l2_u0(hipStream_t s, LoopArgs la, ScalarSrc full, int64_t n, const double *r0, double *u0);
+// gamma = u1.r~ (gam), alpha; r0 -= alpha u1; y += alpha u0
+int launch_l2_step0(hipStream_t s, LoopArgs la, ScalarSrc gam, int64_t n, double *r0, const double *u1, const double *u0, double *y);
+// rho1 = r1.r~ (rho), beta; u0 = r0 - beta u0; u1 = r1 - beta u1
+int launch_l2_u1(hipStream_t s, LoopArgs la, ScalarSrc rho, int64_t n, const double *r0, const double *r1, double *u0, double *u1);
+// gamma = u2.r~ (gam), alpha; r0 -= alpha u1; r1 -= alpha u2; y += alpha u0; parts = (r1.r1, r1.r0), stride 2
+int launch_l2_step1(hipStream_t s, LoopArgs la, ScalarSrc gam, int64_t n, double *r0, double *r1, const double *u0, const double *u1,
+                    const double *u2, double *y, double *parts, int *nparts);
+// parts[b] = sum r2 r0 (the one reduction pass of a sweep that rides in no other kernel); returns at once when frozen
+int launch_l2_dot(hipStream_t s, LoopArgs la, int64_t n, const double *r2, const double *r0, double *parts, int *nparts);
+// the 2 x 2 minimal-residual system from d11 = (r1.r1, r1.r0), d2 = (r2.r1, r2.r2), d20 = r2.r0; y += g1 r0 + g2 r1;
+// u0 -= g1 u1 + g2 u2; r0 -= g1 r1 + g2 r2; omega = g2; parts = (r0.r~, r0.r0), stride 2; it++; the progress word
+int launch_l2_mr(hipStream_t s, LoopArgs la, ScalarSrc d11, ScalarSrc d2, ScalarSrc d20, int64_t n, double *y, double *r0,
+                 const double *r1, const double *r2, double *u0, const double *u1, const double *u2, const double *rt,
+                 double *parts, int *nparts);
+// the stopping test of the last sweep, after the loop (one workgroup)
+int launch_l2_check(hipStream_t s, LoopArgs la, ScalarSrc full);
 // standalone stopping tests (one workgroup)
 int launch_check(hipStream_t s, LoopArgs la, ScalarSrc src, int which);
 // out[k] = sum of partials, k < K (one workgroup)

@@ -5,6 +5,7 @@
 //   CUDAMAT_LOOP_PBICGSTAB2 = gpu_pbicgstab2 pbicgstab.cu:581-754 (d variant; with d == NULL the intended maths of
 //                             :425-578)
 //   CUDAMAT_LOOP_PIPELINED  = the same recurrences re-arranged (Cools & Vanroose 2017, Alg. 4): not a reference loop
+//   CUDAMAT_LOOP_BICGSTAB_L2 = BiCGSTAB(2) (Sleijpen & Fokkema 1993): not a reference loop; one sweep = four products
 //
 // One solve = Solve::setup (validation, set-up on first use, r0 and the LoopState: pbicgstab.cu:67-74), then ONE of
 // the loop forms, then Solve::finish (exit bookkeeping, statistics):
@@ -12,6 +13,7 @@
 //   iterate_fused     three launches per iteration                      (short rows, <= 3e5 rows, one GPU, M = I)
 //   iterate_reference five launches per iteration                       (everything else; + M^-1, + exchanges when sharded)
 //   iterate_pipelined four launches per iteration, reductions beside the SpMVs (sharded runs)
+//   iterate_l2        ten launches per sweep of CUDAMAT_LOOP_BICGSTAB_L2 (four SpMVs, six vector kernels; + M^-1; one GPU)
 // A guarded solve (CUDAMAT_FLAG_GUARD, or the switch GUARD = 1) always takes iterate_reference, with the GUARD instantiations
 // of k_update_p / k_full; cudamat_solver_solve strings its segments together (restarts on a lost rho, verified convergence).
 // The host-side loop (run_host_loop) is shared by the last three: it enqueues iteration k and looks at the progress
@@ -53,15 +55,18 @@ int wait_progress(cudamat_solver *s, hipStream_t st, int j, const char *what, un
     return CUDAMAT_OK;
 }
 
+// history entries per iteration: the half and the full step, or the end of the iteration alone
+static int history_per_iteration(int loop) { return loop == CUDAMAT_LOOP_PBICGSTAB2 || loop == CUDAMAT_LOOP_BICGSTAB_L2 ? 1 : 2; }
+
 int history_need(int loop, int maxit)
 {
-    const long long want = (long long)(loop != CUDAMAT_LOOP_PBICGSTAB2 ? 2 : 1) * (maxit > 0 ? maxit : 1);
+    const long long want = (long long)history_per_iteration(loop) * (maxit > 0 ? maxit : 1);
     return (int)(want < (1LL << 20) ? want : (1LL << 20));
 }
 
 int history_count(int loop, const LoopState &f, int cap)
 {
-    const int c = loop != CUDAMAT_LOOP_PBICGSTAB2 ? 2 * f.it + (f.state == 1 ? 1 : 0) : f.it;
+    const int c = history_per_iteration(loop) == 2 ? 2 * f.it + (f.state == 1 ? 1 : 0) : f.it;
     return c < cap ? c : cap;
 }
 
@@ -102,7 +107,7 @@ struct Solve {
     const Config *cfg = nullptr;
     hipStream_t st = nullptr;
     int n = 0;
-    bool profile = false, sharded = false, perm = false, pipelined = false, pipe_pc = false, guard = false;
+    bool profile = false, sharded = false, perm = false, pipelined = false, pipe_pc = false, guard = false, l2 = false;
     double rho_eps = 0.0;              // guarded solves: GUARD_RHO_ULPS * 2^-52 (check_rho)
     double *x_user = nullptr;          // the caller's x (x itself is the level-major copy while perm)
     int hist_base = 0;
@@ -133,6 +138,9 @@ struct Solve {
     int iterate_reference();
     int iterate_fused();
     int iterate_pipelined(int k);
+    int l2_prologue();
+    int l2_ahat(const double *in, double *out, int dot, const double *w, double *parts);
+    int iterate_l2();
     int pipe_reduce(ScalarSrc parts, int K, double *out, int slot);
     int pipe_wait(int slot);
     int finish(bool *precond_gave_up, cudamat_stats *out);
@@ -144,8 +152,14 @@ int Solve::setup()
     CM_ARG(s && b && x, "null pointer");
     CM_ARG(precond == CUDAMAT_PRECOND_NONE || precond == CUDAMAT_PRECOND_ILU0 || precond == CUDAMAT_PRECOND_BLOCK_ILU0,
            "precond");
-    CM_ARG(loop == CUDAMAT_LOOP_PBICGSTAB || loop == CUDAMAT_LOOP_PBICGSTAB2 || loop == CUDAMAT_LOOP_PIPELINED, "loop");
+    CM_ARG(loop == CUDAMAT_LOOP_PBICGSTAB || loop == CUDAMAT_LOOP_PBICGSTAB2 || loop == CUDAMAT_LOOP_PIPELINED ||
+           loop == CUDAMAT_LOOP_BICGSTAB_L2, "loop");
     CM_ARG(maxit >= 0, "maxit");
+    if (loop == CUDAMAT_LOOP_BICGSTAB_L2) {
+        CM_ARG(!s->sharded, "CUDAMAT_LOOP_BICGSTAB_L2 is one-GPU only: sharded solvers take the other loops");
+        CM_ARG(precond != CUDAMAT_PRECOND_BLOCK_ILU0, "CUDAMAT_LOOP_BICGSTAB_L2 takes CUDAMAT_PRECOND_NONE or CUDAMAT_PRECOND_ILU0, not CUDAMAT_PRECOND_BLOCK_ILU0");
+        CM_ARG(!(flags & CUDAMAT_FLAG_GUARD), "CUDAMAT_FLAG_GUARD (or the switch GUARD) does not cover CUDAMAT_LOOP_BICGSTAB_L2");
+    }
     CM_ARG(!(precond == CUDAMAT_PRECOND_ILU0 && s->sharded),
            "ILU(0) of the whole matrix is single-GPU only (SURVEY 8e); sharded runs take CUDAMAT_PRECOND_BLOCK_ILU0");
     // a shift takes the factors of a shifted matrix only (cudamat_solver_ilu0_shift): A0 is never factored silently in its place
@@ -215,6 +229,7 @@ int Solve::setup()
     sharded = s->sharded;
     pipelined = loop == CUDAMAT_LOOP_PIPELINED;
     pipe_pc = pipelined && precond != CUDAMAT_PRECOND_NONE;
+    l2 = loop == CUDAMAT_LOOP_BICGSTAB_L2;
     guard = (flags & CUDAMAT_FLAG_GUARD) != 0;
     rho_eps = guard ? (double)cfg->guard_rho_ulps * 0x1p-52 : 0.0;       // (exact: at most 2^52 ulps)
     la = LoopArgs{s->st, s->hist + hist_base, s->hist_cap - hist_base, loop, (flags & CUDAMAT_FLAG_NO_EXIT) ? 1 : 0, s->snap_dev, kRing, 0};
@@ -230,6 +245,9 @@ int Solve::setup()
     CM_HIP(hipMemcpyAsync(s->pw, x, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
     CM_TRY(spmv_local(s, s->pw, s->r, 0, nullptr, nullptr, la_none, CHECK_NONE, nosrc));
     CM_TRY(launch_init(st, n, b, s->r, s->rw, s->p, s->parts_full, &np_full));   // :69-74
+    // (BiCGSTAB(2) promises the same bits wherever b and x start: its start sums are formed again from r0, a work vector, in the
+    // pair order -- launch_init deals rows when b is 8 bytes off)
+    if (l2) CM_TRY(launch_l2_start(st, n, s->r, s->parts_full, &np_full));
     full_src = ScalarSrc{s->parts_full, np_full, 2};
     if (sharded) {
         CM_TRY(launch_reduce_parts(st, full_src, 2, s->red + 4, 0));
@@ -376,6 +394,69 @@ int Solve::iterate_pipelined(int k)
     return CUDAMAT_OK;
 }
 
+// ============================================================================================ BiCGSTAB(2)
+// CUDAMAT_LOOP_BICGSTAB_L2 (the iteration: include/cudamat.h; the kernels: bicgstab_l2.hip).  Vectors: r0 = r, r~ = rw, u0 = p
+// (launch_init left p = r0; the first sweep's beta is 0), u1 = v, r1 = s.  Without a preconditioner u2 = t, r2 = pw and y is
+// the caller's x; with one t and pw serve M^-1 (scratch and result), so u2, r2 and y -- zeroed here -- are the solver's
+// three extra vectors.  The scalars: L2State in the slot behind the solve's LoopState (common.h).
+int Solve::l2_prologue()
+{
+    if (!precond) return CUDAMAT_OK;
+    const size_t count = (size_t)(s->n_pad > 0 ? s->n_pad : 1), nb = sizeof(double) * count;
+    if (!s->l2_y) {
+        DevBuf<double> *vs[] = {&s->l2_u2, &s->l2_r2, &s->l2_y};
+        for (DevBuf<double> *q : vs) {
+            CM_TRY(q->alloc(count));
+            CM_HIP(hipMemsetAsync(q->get(), 0, nb, st));
+        }
+    }
+    CM_HIP(hipMemsetAsync(s->l2_y, 0, nb, st));
+    return CUDAMAT_OK;
+}
+
+// out = A^ in = A M^-1 in (M^-1 in in pw), with the dots of spmv_local in `parts`
+int Solve::l2_ahat(const double *in, double *out, int dot, const double *w, double *parts)
+{
+    const double *src = in;
+    if (precond) {
+        prof_mark();
+        CM_TRY(precond_apply(s, in, s->t, s->pw));
+        prof_mark();
+        src = s->pw;
+    }
+    prof_mark();
+    CM_TRY(spmv_local(s, src, out, dot, w, parts, la, CHECK_NONE, nosrc));
+    prof_mark();
+    return CUDAMAT_OK;
+}
+
+// One sweep.  Every dot rides in an SpMV epilogue or in the vector kernel that streams its operands, but r2.r0.
+int Solve::iterate_l2()
+{
+    double *const r0 = s->r, *const rt = s->rw, *const u0 = s->p, *const u1 = s->v, *const r1 = s->s;
+    double *const u2 = precond ? s->l2_u2.get() : s->t.get(), *const r2 = precond ? s->l2_r2.get() : s->pw.get();
+    double *const y = precond ? s->l2_y.get() : x;
+    const ScalarSrc rt_src{s->parts_rv, spmv_parts(s), 2};     // the r~ dot of the SpMV just launched
+    // j = 0
+    CM_TRY(launch_l2_u0(st, la, full_src, n, r0, u0));                      // the test on ||r0||; beta; u0 = r0 - beta u0
+    CM_TRY(l2_ahat(u0, u1, 1, rt, s->parts_rv));                            // u1 = A^ u0, u1.r~
+    CM_TRY(launch_l2_step0(st, la, rt_src, n, r0, u1, u0, y));              // alpha; r0 -= alpha u1; y += alpha u0
+    CM_TRY(l2_ahat(r0, r1, 1, rt, s->parts_rv));                            // r1 = A^ r0, r1.r~
+    // j = 1
+    CM_TRY(launch_l2_u1(st, la, rt_src, n, r0, r1, u0, u1));                // beta; u0 = r0 - beta u0; u1 = r1 - beta u1
+    CM_TRY(l2_ahat(u1, u2, 1, rt, s->parts_rv));                            // u2 = A^ u1, u2.r~
+    int np11 = 0, np20 = 0;
+    CM_TRY(launch_l2_step1(st, la, rt_src, n, r0, r1, u0, u1, u2, y, s->parts_half, &np11));   // alpha; r0, r1, y; (r1.r1, r1.r0)
+    CM_TRY(l2_ahat(r1, r2, 2, r1, s->parts_tt));                            // r2 = A^ r1, (r2.r1, r2.r2)
+    // the minimal-residual step
+    double *const parts20 = s->parts_half + 2 * kVecGridMax;                 // (behind step1's 2 * kVecGridMax partials)
+    CM_TRY(launch_l2_dot(st, la, n, r2, r0, parts20, &np20));               // r2.r0
+    CM_TRY(launch_l2_mr(st, la, ScalarSrc{s->parts_half, np11, 2}, ScalarSrc{s->parts_tt, spmv_parts(s), 2}, ScalarSrc{parts20, np20, 1},
+                        n, y, r0, r1, r2, u0, u1, u2, rt, s->parts_full, &np_full));
+    full_src = ScalarSrc{s->parts_full, np_full, 2};
+    return CUDAMAT_OK;
+}
+
 // ============================================================================================ small systems
 // Vectors resident in L2: three launches per iteration instead of five -- the vector updates in front of the two SpMVs
 // are folded into them (small_loops.hip); p, v and r are double-buffered.
@@ -387,7 +468,7 @@ bool Solve::wants_fused() const
 {
     const bool forced = cfg->fused >= 0;
     const long long max_rows = forced ? cfg->fused : 300000;
-    return loop != CUDAMAT_LOOP_PIPELINED && !sharded && !precond && s->spmv_mode == 0 && fused_spmv_supported(s->plan) && n > 0 &&
+    return loop != CUDAMAT_LOOP_PIPELINED && !l2 && !sharded && !precond && s->spmv_mode == 0 && fused_spmv_supported(s->plan) && n > 0 &&
            n <= max_rows && (forced || s->plan.stream_rows > 0);
 }
 
@@ -395,7 +476,7 @@ bool Solve::wants_fused() const
 // launch, grid barriers instead of launch boundaries (small_loops.hip).  The option RESIDENT = 0 disables.
 bool Solve::wants_resident()
 {
-    if (loop_form != 1 || profile || s->resident_off || !cfg->resident || !resident_loop_supported(s->plan, n)) return false;
+    if (loop_form != 1 || l2 || profile || s->resident_off || !cfg->resident || !resident_loop_supported(s->plan, n)) return false;
     // all workgroups must be resident at once: at most one per two compute units of THIS device
     if (s->device_cus == 0 && hipDeviceGetAttribute(&s->device_cus, hipDeviceAttributeMultiprocessorCount, s->ctx->device) != hipSuccess)
         s->device_cus = -1;
@@ -562,6 +643,7 @@ int Solve::run_host_loop()
         }
         la.k = k;
         if (pipelined) CM_TRY(iterate_pipelined(k));
+        else if (l2) CM_TRY(iterate_l2());
         else if (loop_form == 1) CM_TRY(iterate_fused());
         else CM_TRY(iterate_reference());
     }
@@ -574,7 +656,16 @@ int Solve::finish(bool *precond_gave_up, cudamat_stats *out)
     // the full-step test of the last iteration has not been looked at yet
     if (pipelined)      // (check_full wants (., r.r): the last two of the five phase-B scalars)
         CM_TRY(launch_check(st, la, ScalarSrc{pipeB_src.ptr + 3, pipeB_src.count, pipeB_src.stride}, CHECK_FULL));
-    else
+    else if (l2) {
+        CM_TRY(launch_l2_check(st, la, full_src));
+        // x = x0 + M^-1 y, whatever ended the loop (y = 0 when it never started: x0 comes back as it is).  Applied before
+        // trsv_status is looked at below: after a dependency-driven solve that gave up, x holds a void update until
+        // solve_guarded redoes the solve from the x0 it kept (keep_x0) or from ones.
+        if (precond) {
+            CM_TRY(precond_apply(s, s->l2_y, s->t, s->pw));
+            CM_TRY(launch_axpy(st, n, 1.0, s->pw, x));
+        }
+    } else
         CM_TRY(launch_check(st, la, full_src, CHECK_FULL));
     CM_HIP(hipMemcpyAsync(&s->st_ring[0], s->st, sizeof(LoopState), hipMemcpyDeviceToHost, st));
     CM_HIP(hipStreamSynchronize(st));                              // :372
@@ -670,7 +761,11 @@ int Solve::finish(bool *precond_gave_up, cudamat_stats *out)
         std::vector<double> h((size_t)(s->hist_count > 0 ? s->hist_count : 1));
         if (s->hist_count > 0)
             CM_HIP(hipMemcpy(h.data(), s->hist, sizeof(double) * (size_t)s->hist_count, hipMemcpyDeviceToHost));
-        if (loop != CUDAMAT_LOOP_PBICGSTAB2) {
+        if (l2) {
+            printf("initial norm = %g\n", fin.nrm0);
+            for (int i = 0; i < s->hist_count; i++) printf("sweep = %d, norm = %g\n", i, h[i]);
+            if (fin.state == 3) printf("BiCGSTAB(2) breakdown in sweep %d, cannot continue\n", fin.it);
+        } else if (loop != CUDAMAT_LOOP_PBICGSTAB2) {
             printf("gpu, init residual:norm %20.16f\n", fin.nrm0);            // :77
             for (int i = hist_base; i < s->hist_count; i++) {                  // (a restart segment prints its own part)
                 if ((i & 1) == 0) printf("i = %d, residual norm (before precond) = %g\n", i / 2, h[i]);  // :114
@@ -700,6 +795,7 @@ int solve_once(cudamat_solver *s, const double *b, double *x, int precond, int l
     CM_TRY(q.setup());
     Range range_loop("cudamat: iteration loop (enqueue + lagged checks)");
     if (q.pipelined) CM_TRY(q.pipelined_prologue());
+    if (q.l2) CM_TRY(q.l2_prologue());
     q.loop_form = !q.guard && q.wants_fused() ? 1 : 0;       // (a guarded solve: five launches, whatever the system's size)
     if (q.loop_form == 1 && !s->v2) {
         const size_t count = (size_t)(s->n_pad > 0 ? s->n_pad : 1), nb = sizeof(double) * count;
@@ -774,6 +870,7 @@ extern "C" int cudamat_solver_solve(cudamat_solver *s, const double *b, double *
     const bool guard = (flags & CUDAMAT_FLAG_GUARD) != 0;
     const bool exits = !(flags & CUDAMAT_FLAG_NO_EXIT);
     if (guard) {
+        CM_ARG(loop != CUDAMAT_LOOP_BICGSTAB_L2, "CUDAMAT_FLAG_GUARD (or the switch GUARD) does not cover CUDAMAT_LOOP_BICGSTAB_L2");
         CM_ARG(loop != CUDAMAT_LOOP_PIPELINED,
                "CUDAMAT_FLAG_GUARD does not cover CUDAMAT_LOOP_PIPELINED, which verifies its iterates itself");
         CM_ARG(!s->sharded, "CUDAMAT_FLAG_GUARD does not cover sharded solvers yet (its third sum would have to ride in the all-reduce)");

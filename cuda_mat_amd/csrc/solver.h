@@ -100,11 +100,14 @@ struct cudamat_solver {
     cm::DevBuf<double> prh, pwh, psh, pzh, pqh, ptmp;   // preconditioned pipelined loop: M^-1 r, w, s, z, q; scratch
     cm::DevBuf<double> pipeA, pipeB, red_pipe;
     hipEvent_t ev_red[2] = {}, ev_red_done[2] = {};
+    // CUDAMAT_LOOP_BICGSTAB_L2: u2, r2 and y (n_pad each), allocated at its first PRECONDITIONED solve -- without a preconditioner
+    // u2 and r2 live in t and pw, and y is the caller's x.  (Its scalars: the second slot of `st`.)
+    cm::DevBuf<double> l2_u2, l2_r2, l2_y;
 
     // reduction workspace: four stages of per-workgroup partials + reduced scalars
     cm::DevBuf<double> parts_full, parts_rv, parts_half, parts_tt;
     cm::DevBuf<double> red;    // 8 doubles
-    cm::DevBuf<cm::LoopState> st;             // device
+    cm::DevBuf<cm::LoopState> st;             // device: the solve's LoopState, and a second slot that holds the L2State of BiCGSTAB(2)
     cm::PinnedBuf<cm::LoopState> st_ring;     // pinned host, kRing slots
     hipEvent_t ev[cm::kRing] = {};
     cm::PinnedBuf<unsigned long long> snap_host;   // pinned: per-iteration progress words written by k_full

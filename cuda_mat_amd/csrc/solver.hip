@@ -159,7 +159,7 @@ int solver_alloc(cudamat_ctx *ctx, int n_local, int64_t n_cols, int64_t nnz, cud
     CM_TRY(s->parts_half.alloc(2 * kMaxParts));
     CM_TRY(s->parts_tt.alloc(2 * kMaxParts));
     CM_TRY(s->red.alloc(16));
-    CM_TRY(s->st.alloc(1));
+    CM_TRY(s->st.alloc(2));                   // (the second slot: L2State, common.h)
     LoopState *ring = nullptr;
     unsigned long long *snap = nullptr;
     if (hipHostMalloc((void **)&ring, sizeof(LoopState) * kRing, hipHostMallocDefault) != hipSuccess) {
@@ -173,7 +173,7 @@ int solver_alloc(cudamat_ctx *ctx, int n_local, int64_t n_cols, int64_t nnz, cud
         set_error("pinned progress words unavailable");
         return CUDAMAT_ERR_HIP;
     }
-    if (hipMemsetAsync(s->st, 0, sizeof(LoopState), st) != hipSuccess) return CUDAMAT_ERR_HIP;
+    if (hipMemsetAsync(s->st, 0, 2 * sizeof(LoopState), st) != hipSuccess) return CUDAMAT_ERR_HIP;
     *out = s.release();
     return CUDAMAT_OK;
 }

@@ -53,6 +53,59 @@ __device__ __forceinline__ double step_r_full(double r, double t, double omega) 
     return fma(-omega, t, r);
 }
 
+// ------------------------------------------------------------------ BiCGSTAB(2) (CUDAMAT_LOOP_BICGSTAB_L2, bicgstab_l2.hip)
+// The BiCG half of a sweep: beta = alpha rho1 / rho0 with rho0 = -omega rho0' at j = 0, alpha = rho0 / gamma.
+__device__ __forceinline__ double step_l2_beta(double alpha, double rho1, double rho0)
+{
+#pragma clang fp contract(off)
+    return (alpha * rho1) / rho0;
+}
+
+__device__ __forceinline__ double step_l2_alpha(double rho0, double gamma) { return rho0 / gamma; }
+
+// The minimal-residual half: [[a11, a12], [a12, a22]] (g1, g2) = (b1, b2) by Cramer's rule, every product and difference
+// rounded on its own; *det is what the caller tests for a singular system.
+__device__ __forceinline__ void step_l2_mr(double a11, double a12, double a22, double b1, double b2, double *det, double *g1,
+                                           double *g2)
+{
+#pragma clang fp contract(off)
+    const double dd = a11 * a22 - a12 * a12;
+    *det = dd;
+    *g1 = (b1 * a22 - b2 * a12) / dd;
+    *g2 = (a11 * b2 - a12 * b1) / dd;
+}
+
+__device__ __forceinline__ double step_l2_u(double r, double u, double beta)              // u_i = r_i - beta u_i
+{
+#pragma clang fp contract(off)
+    return fma(-beta, u, r);
+}
+
+__device__ __forceinline__ double step_l2_r(double r, double u, double alpha)             // r_i -= alpha u_(i+1)
+{
+#pragma clang fp contract(off)
+    return fma(-alpha, u, r);
+}
+
+__device__ __forceinline__ double step_l2_y(double y, double u, double alpha)             // y += alpha u0
+{
+#pragma clang fp contract(off)
+    return fma(alpha, u, y);
+}
+
+// y += g1 a + g2 b, and v -= g1 a + g2 b: two roundings each, the g1 term first
+__device__ __forceinline__ double step_l2_add2(double y, double a, double b, double g1, double g2)
+{
+#pragma clang fp contract(off)
+    return fma(g2, b, fma(g1, a, y));
+}
+
+__device__ __forceinline__ double step_l2_sub2(double v, double a, double b, double g1, double g2)
+{
+#pragma clang fp contract(off)
+    return fma(-g2, b, fma(-g1, a, v));
+}
+
 // the dots that ride with the steps (:74, :81, :106, :111, :136, :142): one more term into a thread's partial sum, one rounding
 __device__ __forceinline__ void dot_step(double &acc, double a, double b)
 {

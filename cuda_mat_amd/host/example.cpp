@@ -11,6 +11,8 @@
 //     2 = ILU(0)-preconditioned (the reference's only mode; default)
 //     0 = no preconditioner
 //     1 = the (A0 + I*d) entry point, with A's diagonal split off and x0 = 1
+// and  -L  (BiCGSTAB(2) in place of BiCGSTAB, for the systems on which BiCGSTAB stalls: with -C2 ILU(0)-preconditioned, with
+// -C0 or -C1 without a preconditioner; one GPU; -I then counts sweeps of four products)
 // Unlike the reference, the exit status reflects the outcome (upstream always returns EXIT_FAILURE) and a
 // preconditioned run that exhausts maxit reports "method failed" (upstream cannot tell).
 #include <cstdio>
@@ -39,6 +41,7 @@ struct Options {
     int method = 2;
     long seed = -1;
     int gpus = 1;
+    bool l2 = false;
 };
 
 struct System {
@@ -78,6 +81,7 @@ bool parse(int argc, char **argv, Options &o)
         case 'C': o.method = std::stoi(value); break;
         case 'S': o.seed = std::stol(value); break;
         case 'G': o.gpus = std::stoi(value); break;
+        case 'L': o.l2 = true; break;
         default:
             fprintf(stderr, "Unknown switch '-%s'\n", arg + 1);
             return false;
@@ -204,7 +208,14 @@ int main(int argc, char *argv[])
     double dtAlg = 0.0;
     const double t_begin = second();
     bool solved;
-    if (opt.method == 0) {
+    if (opt.l2) {
+        if (opt.method == 2)          // (d = NULL: no shift; x0 = NULL: ones)
+            solved = bicgstab_l2_lu_precond(sys.n, sys.nnz, sys.A, sys.iA, sys.jA, nullptr, nullptr, sys.b, opt.maxit, opt.tol,
+                                            opt.trace, x.data(), &dtAlg) && cudamat_last_stats()->converged;
+        else
+            solved = bicgstab_l2(sys.n, sys.nnz, sys.A, sys.iA, sys.jA, nullptr, nullptr, sys.b, opt.maxit, opt.tol, opt.trace,
+                                 x.data(), &dtAlg);
+    } else if (opt.method == 0) {
         solved = bicgstab(sys.n, sys.nnz, sys.A, sys.iA, sys.jA, sys.b, opt.maxit, opt.tol, opt.trace, x.data(), &dtAlg);
     } else if (opt.method == 1) {
         solved = solve_split(sys, opt, x.data(), &dtAlg);

@@ -99,3 +99,18 @@ bool bicgstab_lu_precond(int n, int nnz, double *A0, int *iA0, int *jA0, double 
     return run(n, nnz, A0, iA0, jA0, d, x0, b, CUDAMAT_PRECOND_ILU0, CUDAMAT_LOOP_PBICGSTAB, maxit, tol, debug, x, dtAlg,
                true);
 }
+
+// BiCGSTAB(2): the same shims with CUDAMAT_LOOP_BICGSTAB_L2 (one GPU: cudamat_solve refuses a sharded run with a message)
+bool bicgstab_l2(int n, int nnz, double *A0, int *iA0, int *jA0, double *d, double *x0, double *b, int maxit, double tol,
+                 bool debug, double *x, double *dtAlg)
+{
+    return run(n, nnz, A0, iA0, jA0, d, x0, b, CUDAMAT_PRECOND_NONE, CUDAMAT_LOOP_BICGSTAB_L2, maxit, tol, debug, x, dtAlg,
+               false);
+}
+
+bool bicgstab_l2_lu_precond(int n, int nnz, double *A0, int *iA0, int *jA0, double *d, double *x0, double *b, int maxit,
+                            double tol, bool debug, double *x, double *dtAlg)
+{
+    return run(n, nnz, A0, iA0, jA0, d, x0, b, CUDAMAT_PRECOND_ILU0, CUDAMAT_LOOP_BICGSTAB_L2, maxit, tol, debug, x, dtAlg,
+               true);
+}

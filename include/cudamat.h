@@ -71,6 +71,33 @@ extern "C" {
                                      * LOOP_PBICGSTAB re-arranged so that both reduction phases of an iteration run
                                      * while an SpMV runs; same stopping rules and history layout;
                                      * no preconditioner; iterates equal BiCGSTAB's up to rounding              */
+#define CUDAMAT_LOOP_BICGSTAB_L2 3  /* BiCGSTAB(2) (Sleijpen & Fokkema 1993, l = 2): not a reference loop.  For the systems on
+                                     * which BiCGSTAB's degree-1 minimal-residual step stalls (eigenvalues far from the real
+                                     * axis: convection-dominated operators).  One iteration is one SWEEP: two BiCG steps and
+                                     * one degree-2 minimal-residual step = FOUR products with A^ = A M^-1 (right
+                                     * preconditioning) against BiCGSTAB's two, so cudamat_stats.iters counts sweeps and one
+                                     * sweep costs what two iterations of the other loops cost.  With r~ = r0 = b - A x0,
+                                     * rho0 = 1, alpha = 0, omega = 1, u0 = 0 at the start:
+                                     *   rho0 = -omega rho0
+                                     *   j=0: rho1 = r0.r~; beta = alpha rho1/rho0; rho0 = rho1; u0 = r0 - beta u0
+                                     *        u1 = A^ u0; gamma = u1.r~; alpha = rho0/gamma; r0 -= alpha u1; y += alpha u0
+                                     *        r1 = A^ r0
+                                     *   j=1: rho1 = r1.r~; beta = alpha rho1/rho0; rho0 = rho1; u0 = r0 - beta u0;
+                                     *        u1 = r1 - beta u1; u2 = A^ u1; gamma = u2.r~; alpha = rho0/gamma
+                                     *        r0 -= alpha u1; r1 -= alpha u2; y += alpha u0; r2 = A^ r1
+                                     *   MR:  [[r1.r1, r1.r2], [r1.r2, r2.r2]] (g1, g2) = (r1.r0, r2.r0)
+                                     *        y += g1 r0 + g2 r1; u0 -= g1 u1 + g2 u2; r0 -= g1 r1 + g2 r2; omega = g2
+                                     * ||r0|| < tol ||r~|| after the MR step is the only stopping test; the history has one
+                                     * entry per sweep.  With a preconditioner x = x0 + M^-1 y is formed after the loop (one
+                                     * more application); without one y is x.  breakdown = 1, converged = 0 when gamma = 0,
+                                     * the dividing rho0 = 0, the 2 x 2 system is singular or a scalar is not finite: the
+                                     * loop stops there, the sweep is not counted.  x is then what the loop had reached:
+                                     * the BiCG updates of the uncounted sweep that preceded the breakdown are in it (x and
+                                     * r0 still belong together); it is not the iterate of the last counted sweep unless the
+                                     * breakdown came at j = 0.  CUDAMAT_FLAG_NO_EXIT takes none of these
+                                     * tests.  One GPU; PRECOND_NONE or PRECOND_ILU0; a shift as for the other loops.
+                                     * CUDAMAT_ERR_ARG for sharded solvers, PRECOND_BLOCK_ILU0 and CUDAMAT_FLAG_GUARD (or
+                                     * the switch GUARD).  Batched entry points run its columns one by one (form 0).     */
 
 /* flags for cudamat_solver_solve */
 #define CUDAMAT_FLAG_DEBUG      1   /* print the reference's debug lines                */

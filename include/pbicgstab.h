@@ -143,6 +143,24 @@ bool bicgstab_lu_precond(int n, int nnz,
                          int maxit, double tol, bool debug,
                          double OUT(*x), double OUT(*dtAlg));
 
+/* EXTENSION of this library: BiCGSTAB(2) (CUDAMAT_LOOP_BICGSTAB_L2 of cudamat.h), for the systems on which BiCGSTAB stalls
+ * (convection-dominated operators).  (A0 + I*d) x = b from x0, no preconditioner; d may be NULL (no shift), x0 may be NULL
+ * (x0 = 1).  maxit counts sweeps of four products each.  Returns what bicgstab returns: true when the method converged.
+ * Single GPU only: after cudamat_use_gpus(k > 1) the call returns false with a message. */
+bool bicgstab_l2(int n, int nnz,
+                 double IN(*A0), int IN(*iA0), int IN(*jA0),
+                 double IN(*d), double IN(*x0), double IN(*b),
+                 int maxit, double tol, bool debug,
+                 double OUT(*x), double OUT(*dtAlg));
+
+/* ... with the ILU(0) preconditioner of A0 + diag(d) (of A0 when d is NULL), applied from the right.  Returns what
+ * bicgstab_lu_precond returns: true whenever the solve ran; convergence is in cudamat_last_stats(). */
+bool bicgstab_l2_lu_precond(int n, int nnz,
+                            double IN(*A0), int IN(*iA0), int IN(*jA0),
+                            double IN(*d), double IN(*x0), double IN(*b),
+                            int maxit, double tol, bool debug,
+                            double OUT(*x), double OUT(*dtAlg));
+
 /* statistics of the last solve issued by the calling thread */
 const cudamat_stats *cudamat_last_stats();
 
