@@ -13,8 +13,8 @@ LIB_PATH = os.path.join(_HERE, "libcudamat_hip.so")
 
 OK = 0
 PRECOND_NONE, PRECOND_ILU0, PRECOND_BLOCK_ILU0 = 0, 1, 2
-LOOP_PBICGSTAB, LOOP_PBICGSTAB2, LOOP_PIPELINED, LOOP_BICGSTAB_L2 = 0, 1, 2, 3
-FLAG_DEBUG, FLAG_PROFILE, FLAG_NO_EXIT, FLAG_X0_ONES, FLAG_GUARD = 1, 2, 4, 8, 16
+LOOP_PBICGSTAB, LOOP_PBICGSTAB2, LOOP_PIPELINED, LOOP_BICGSTAB_L2, LOOP_CG = 0, 1, 2, 3, 8
+FLAG_DEBUG, FLAG_PROFILE, FLAG_NO_EXIT, FLAG_X0_ONES, FLAG_GUARD, FLAG_ASSUME_SYMMETRIC = 1, 2, 4, 8, 16, 32
 
 
 class CudamatError(RuntimeError):
@@ -108,6 +108,7 @@ _SIGS = {
     "cudamat_solver_ilu0_refactor": (C.c_int, [_P, _P]),
     "cudamat_solver_ilu0_refactor_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_size_t)]),
     "cudamat_solver_set_values": (C.c_int, [_P, _P]),
+    "cudamat_solver_symmetry": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
     "cudamat_solver_set_values_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "cudamat_solver_block_ilu0": (C.c_int, [_P]),
     "cudamat_solver_ilu0_values": (C.c_int, [_P, _P]),

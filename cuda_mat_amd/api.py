@@ -7,6 +7,8 @@ Names and argument meaning follow pbicgstab.h / mmio_wrapper.h of the reference:
   bicgstab_d_lu_precond(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug)   ILU(0) of A0 + diag(d), the loop with d (new)
   bicgstab_l2(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug)     BiCGSTAB(2), no preconditioner; d, x0 may be None (new)
   bicgstab_l2_lu_precond(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug)   BiCGSTAB(2) with ILU(0) of A0 + diag(d) (new)
+  cg(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug)              conjugate gradients for symmetric positive definite systems (new)
+  cg_lu_precond(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug)   ... with ILU(0) of A0 + diag(d) (new)
   bicgstab_many(n, nnz, A, iA, jA, B, maxit, tol, d, x0)             bicgstab / bicgstab_d for the columns of B (new)
   bicgstab_lu_precond_many(n, nnz, A, iA, jA, B, maxit, tol)         bicgstab_lu_precond for the columns of B (new)
   bicgstab_d_many(n, nnz, A0, iA0, jA0, D, x0, B, maxit, tol)        bicgstab_d with shift D[:, j] for column j of B (new)
@@ -25,7 +27,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (FLAG_DEBUG, FLAG_GUARD, FLAG_NO_EXIT, FLAG_PROFILE, FLAG_X0_ONES, LOOP_BICGSTAB_L2, LOOP_PBICGSTAB,
+from ._lib import (FLAG_ASSUME_SYMMETRIC, FLAG_DEBUG, FLAG_GUARD, FLAG_NO_EXIT, FLAG_PROFILE, FLAG_X0_ONES, LOOP_BICGSTAB_L2, LOOP_CG, LOOP_PBICGSTAB,
                    LOOP_PBICGSTAB2, LOOP_PIPELINED, PRECOND_BLOCK_ILU0, PRECOND_ILU0, PRECOND_NONE, Comm, CudamatError, Stats, check)
 
 
@@ -115,6 +117,21 @@ def bicgstab_l2_lu_precond(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug=Fal
     bicgstab_lu_precond `ok` is True whenever the solve ran; convergence is in stats.converged."""
     x, st = _solve(n, nnz, A0, iA0, jA0, d, x0, b, PRECOND_ILU0, LOOP_BICGSTAB_L2, maxit, tol, debug)
     return True, x, st.t_solve, st
+
+
+def cg(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug=False):
+    """solve (A0 + I*d) x = b from x0 by conjugate gradients (LOOP_CG: A0 + I*d symmetric positive definite), no preconditioner;
+    d None: no shift, x0 None: ones.  One product per iteration.  Mirrors cg of include/pbicgstab.h: `ok` is stats.converged;
+    a matrix that is not symmetric raises CudamatError, one that is not positive definite returns stats.breakdown = 1.  One GPU
+    only (use_gpus(k > 1): CudamatError)."""
+    x, st = _solve(n, nnz, A0, iA0, jA0, d, x0, b, PRECOND_NONE, LOOP_CG, maxit, tol, debug)
+    return bool(st.converged), x, st.t_solve, st
+
+
+def cg_lu_precond(n, nnz, A0, iA0, jA0, d, x0, b, maxit, tol, debug=False):
+    """cg with the ILU(0) preconditioner of A0 + diag(d) (of A0 when d is None).  `ok` is stats.converged."""
+    x, st = _solve(n, nnz, A0, iA0, jA0, d, x0, b, PRECOND_ILU0, LOOP_CG, maxit, tol, debug)
+    return bool(st.converged), x, st.t_solve, st
 
 
 def bicgstab_many(n, nnz, A, iA, jA, B, maxit, tol, d=None, x0=None):
@@ -500,6 +517,13 @@ class Solver:
                 tmp.free()
         else:
             check(_lib.lib().cudamat_solver_set_values(self.h, _ptr(val)))
+
+    def symmetry(self):
+        """(unmatched, max_abs_diff) of the matrix held (cudamat_solver_symmetry): stored off-diagonal entries without a
+        transposed partner, and max |a_ij - a_ji| over the others.  (0, 0.0): symmetric.  Kept until set_values()."""
+        lone, diff = C.c_longlong(), C.c_double()
+        check(_lib.lib().cudamat_solver_symmetry(self.h, C.byref(lone), C.byref(diff)))
+        return lone.value, diff.value
 
     def set_values_info(self):
         """(calls since the creation, wall seconds of the last one, device bytes of the value maps, 1 when the last call changed

@@ -8,8 +8,8 @@
 // As in kernels.hip: HBM-bound fp64 streaming, 16 bytes per lane where the operands allow it, every dot product produced by
 // the kernel that already streams its operands and summed in a fixed order in the prologue of the kernel that consumes it
 // (load_scalars); the arithmetic of each step is stated once, in steps.h.  The scalars live in L2State (common.h), in the slot
-// behind the solve's LoopState.  The only stopping test is ||r0|| after the minimal-residual step (l2_check: in the prologue of the
-// next sweep's first kernel, and once after the loop); a breakdown -- a zero divisor or a scalar that is not finite -- is
+// behind the solve's LoopState.  The only stopping test is ||r0|| after the minimal-residual step
+// (check_iteration_end, device.h: in the prologue of the next sweep's first kernel, and once after the loop); a breakdown -- a zero divisor or a scalar that is not finite -- is
 // noticed by the kernel that forms the scalar, which freezes the loop (state 3) before it touches a vector.
 //
 // Vector traffic per row and sweep, in doubles read + written: u0 2 + 1, step0 4 + 2, u1 4 + 2, step1 6 + 3, dot 2,
@@ -21,68 +21,13 @@
 
 namespace cm {
 
-namespace {
-
-// vec_loop's dealing for both alignments.  VEC = 1 is vec_loop<1>.  VEC = 0 (an operand 8 bytes off a 16-byte boundary) keeps
-// the pairs and visits their elements one by one, .x before .y, then the odd tail: a thread's partial sums take the same
-// terms in the same order, so the bits of a solve do not depend on where the caller's vectors start.
-template <int VEC, class Body>
-__device__ __forceinline__ void l2_loop(int64_t n, Body body)
-{
-    if constexpr (VEC) {
-        vec_loop<1>(n, body);
-    } else {
-        const int64_t n2 = n / 2;
-        const int64_t first = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
-        for (int64_t i = first; i < n2; i += stride) {
-            body(2 * i, Width<1>{});
-            body(2 * i + 1, Width<1>{});
-        }
-        for (int64_t i = 2 * n2 + first; i < n; i += stride) body(i, Width<1>{});
-    }
-}
-
-// ||r0|| of sweep it - 1 against the tolerance: one history entry per sweep, at slot it - 1.  rr = r0.r0.  Returns true when
-// the caller must return.  Called by every workgroup with the same sums: they reach the same decision.
-__device__ __forceinline__ bool l2_check(const LoopArgs &la, double rr)
-{
-    LoopState *st = la.st;
-    const int it = st->it;
-    if (it == 0) return false;
-    const double nrm = sqrt(rr);
-    if (leader()) {
-        st->nrm = nrm;
-        if (la.hist && it - 1 < la.hist_cap) la.hist[it - 1] = nrm;
-    }
-    if (la.no_exit) return false;
-    if (nrm < st->tolabs) {
-        if (leader()) st->state = 2;
-        return true;
-    }
-    if (isnan(nrm)) {
-        if (leader()) st->state = 3;
-        return true;
-    }
-    return false;
-}
-
-// a scalar the loop cannot go on with; under FLAG_NO_EXIT no test is taken.  Returns true when the caller must return.
-__device__ __forceinline__ bool l2_breakdown(const LoopArgs &la, bool bad)
-{
-    if (!bad || la.no_exit) return false;
-    if (leader()) la.st->state = 3;
-    return true;
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(kBlock) void k_l2_check(LoopArgs la, ScalarSrc full)
 {
     __shared__ double lds[8];
     if (uniform_state(la.st) != 0) return;
     double sc[2];
     load_scalars<2>(full, sc, lds);
-    l2_check(la, sc[1]);
+    check_iteration_end(la, sc[1]);
 }
 
 int launch_l2_check(hipStream_t s, LoopArgs la, ScalarSrc full)
@@ -93,7 +38,7 @@ int launch_l2_check(hipStream_t s, LoopArgs la, ScalarSrc full)
 }
 
 // The start sums of this loop: parts = (r0.r~, r0.r0) = (r0.r0, r0.r0), stride 2, as launch_init leaves them -- but summed with
-// l2_loop's dealing.  launch_init streams the caller's b and deals rows, not pairs, when b is 8 bytes off a 16-byte boundary;
+// pair_loop's dealing (device.h).  launch_init streams the caller's b and deals rows, not pairs, when b is 8 bytes off a 16-byte boundary;
 // its sum would then differ in the last bits, and with it ||r_init||, the first rho and every iterate after it.  r0 itself is
 // formed element by element and has the same bits either way.
 template <int VEC>
@@ -101,7 +46,7 @@ __global__ __launch_bounds__(kBlock) void k_l2_start(int64_t n, const double *r0
 {
     __shared__ double lds[4];
     double acc[1] = {0.0};
-    l2_loop<VEC>(n, [&](int64_t i, auto w) {
+    pair_loop<VEC>(n, [&](int64_t i, auto w) {
         constexpr int W = decltype(w)::value;
         double rr[W];
         load_row<W>(r0, i, rr);
@@ -133,14 +78,14 @@ __global__ __launch_bounds__(kBlock) void k_l2_u0(LoopArgs la, ScalarSrc full, i
     const int it = st->it;
     double sc[2];
     load_scalars<2>(full, sc, lds);
-    if (l2_check(la, sc[1])) return;
+    if (check_iteration_end(la, sc[1])) return;
     const double rho1 = sc[0];
     const double rho_prev = it == 0 ? 1.0 : q->rho_b, alpha = it == 0 ? 0.0 : q->alpha_b, omega = it == 0 ? 1.0 : q->omega;
     const double rho0 = -omega * rho_prev;
     const double beta = step_l2_beta(alpha, rho1, rho0);
-    if (l2_breakdown(la, rho0 == 0.0 || !isfinite(rho0) || !isfinite(rho1) || !isfinite(beta))) return;
+    if (loop_breakdown(la, rho0 == 0.0 || !isfinite(rho0) || !isfinite(rho1) || !isfinite(beta))) return;
     if (leader()) q->rho_a = rho1;
-    l2_loop<VEC>(n, [&](int64_t i, auto w) {
+    pair_loop<VEC>(n, [&](int64_t i, auto w) {
         constexpr int W = decltype(w)::value;
         double rr[W], uu[W];
         load_row<W>(r0, i, rr); load_row<W>(u0, i, uu);
@@ -167,9 +112,9 @@ __global__ __launch_bounds__(kBlock) void k_l2_step0(LoopArgs la, ScalarSrc gam,
     load_scalars<1>(gam, sc, lds);
     const double gamma = sc[0];
     const double alpha = step_l2_alpha(q->rho_a, gamma);
-    if (l2_breakdown(la, gamma == 0.0 || !isfinite(gamma) || !isfinite(alpha))) return;
+    if (loop_breakdown(la, gamma == 0.0 || !isfinite(gamma) || !isfinite(alpha))) return;
     if (leader()) q->alpha_a = alpha;
-    l2_loop<VEC>(n, [&](int64_t i, auto w) {
+    pair_loop<VEC>(n, [&](int64_t i, auto w) {
         constexpr int W = decltype(w)::value;
         double rr[W], u1v[W], u0v[W], yy[W];
         load_row<W>(r0, i, rr); load_row<W>(u1, i, u1v); load_row<W>(u0, i, u0v); load_row<W>(y, i, yy);
@@ -199,9 +144,9 @@ __global__ __launch_bounds__(kBlock) void k_l2_u1(LoopArgs la, ScalarSrc rho, in
     load_scalars<1>(rho, sc, lds);
     const double rho1 = sc[0], rho0 = q->rho_a;
     const double beta = step_l2_beta(q->alpha_a, rho1, rho0);
-    if (l2_breakdown(la, rho0 == 0.0 || !isfinite(rho1) || !isfinite(beta))) return;
+    if (loop_breakdown(la, rho0 == 0.0 || !isfinite(rho1) || !isfinite(beta))) return;
     if (leader()) q->rho_b = rho1;
-    l2_loop<VEC>(n, [&](int64_t i, auto w) {
+    pair_loop<VEC>(n, [&](int64_t i, auto w) {
         constexpr int W = decltype(w)::value;
         double r0v[W], r1v[W], u0v[W], u1v[W];
         load_row<W>(r0, i, r0v); load_row<W>(r1, i, r1v); load_row<W>(u0, i, u0v); load_row<W>(u1, i, u1v);
@@ -231,10 +176,10 @@ __global__ __launch_bounds__(kBlock) void k_l2_step1(LoopArgs la, ScalarSrc gam,
     load_scalars<1>(gam, sc, lds);
     const double gamma = sc[0];
     const double alpha = step_l2_alpha(q->rho_b, gamma);
-    if (l2_breakdown(la, gamma == 0.0 || !isfinite(gamma) || !isfinite(alpha))) return;
+    if (loop_breakdown(la, gamma == 0.0 || !isfinite(gamma) || !isfinite(alpha))) return;
     if (leader()) q->alpha_b = alpha;
     double acc[2] = {0.0, 0.0};
-    l2_loop<VEC>(n, [&](int64_t i, auto w) {
+    pair_loop<VEC>(n, [&](int64_t i, auto w) {
         constexpr int W = decltype(w)::value;
         double r0v[W], r1v[W], u0v[W], u1v[W], u2v[W], yy[W];
         load_row<W>(r0, i, r0v); load_row<W>(r1, i, r1v); load_row<W>(u0, i, u0v); load_row<W>(u1, i, u1v);
@@ -271,7 +216,7 @@ __global__ __launch_bounds__(kBlock) void k_l2_dot(LoopArgs la, int64_t n, const
     __shared__ double lds[4];
     if (uniform_state(la.st) != 0) return;
     double acc[1] = {0.0};
-    l2_loop<VEC>(n, [&](int64_t i, auto w) {
+    pair_loop<VEC>(n, [&](int64_t i, auto w) {
         constexpr int W = decltype(w)::value;
         double a[W], b[W];
         load_row<W>(r2, i, a); load_row<W>(r0, i, b);
@@ -309,12 +254,12 @@ __global__ __launch_bounds__(kBlock) void k_l2_mr(LoopArgs la, ScalarSrc d11, Sc
     load_scalars<1>(d20, e, lds);      // r2.r0
     double det, g1, g2;
     step_l2_mr(a[0], c[0], c[1], a[1], e[0], &det, &g1, &g2);
-    if (l2_breakdown(la, det == 0.0 || !isfinite(det) || !isfinite(g1) || !isfinite(g2))) {
+    if (loop_breakdown(la, det == 0.0 || !isfinite(det) || !isfinite(g1) || !isfinite(g2))) {
         publish_progress(la, 3);
         return;
     }
     double acc[2] = {0.0, 0.0};
-    l2_loop<VEC>(n, [&](int64_t i, auto w) {
+    pair_loop<VEC>(n, [&](int64_t i, auto w) {
         constexpr int W = decltype(w)::value;
         double yy[W], r0v[W], r1v[W], r2v[W], u0v[W], u1v[W], u2v[W], tv[W];
         load_row<W>(y, i, yy); load_row<W>(r0, i, r0v); load_row<W>(r1, i, r1v); load_row<W>(r2, i, r2v);

@@ -134,6 +134,21 @@ struct L2State {
 static_assert(sizeof(L2State) <= sizeof(LoopState), "L2State takes the LoopState slot behind the solve's own");
 __host__ __device__ inline L2State *l2_state(LoopState *st) { return reinterpret_cast<L2State *>(st + 1); }
 
+// The scalars of CUDAMAT_LOOP_CG (cg.hip), in the same second slot (a solve runs one loop).  No kernel reads a field its own
+// leader writes: k_cg_p reads rho[(it + 1) & 1] and writes rho[it & 1], rho_now and beta; k_cg_step -- which increments it, so
+// it may not index by it -- reads rho_now and writes alpha.
+struct CgState {
+    double rho[2];   // r.z of iteration it in slot it & 1
+    double rho_now;  // r.z of the iteration in progress
+    double alpha;
+    double beta;     // (for the debug lines)
+    double gamma;    // p.q of the iteration in progress (for the debug lines)
+    int why;         // which scalar ended the loop in state 3: 0 none of these, 1 rho, 2 gamma
+    int pad;
+};
+static_assert(sizeof(CgState) <= sizeof(LoopState), "CgState takes the LoopState slot behind the solve's own");
+__host__ __device__ inline CgState *cg_state(LoopState *st) { return reinterpret_cast<CgState *>(st + 1); }
+
 enum Check { CHECK_NONE = 0, CHECK_HALF = 1, CHECK_FULL = 2 };
 
 }  // namespace cm

@@ -220,6 +220,39 @@ __device__ __forceinline__ bool check_full(const LoopArgs &la, const double (&sc
     return false;
 }
 
+// The one stopping test of the loops that test once per iteration (BiCGSTAB(2): per sweep; CG): ||r|| of iteration it - 1
+// against the tolerance, one history entry per iteration, at slot it - 1.  rr = r.r.  Returns true when the caller must
+// return.  Called by every workgroup with the same sums: they reach the same decision.
+__device__ __forceinline__ bool check_iteration_end(const LoopArgs &la, double rr)
+{
+    LoopState *st = la.st;
+    const int it = st->it;
+    if (it == 0) return false;
+    const double nrm = sqrt(rr);
+    if (leader()) {
+        st->nrm = nrm;
+        if (la.hist && it - 1 < la.hist_cap) la.hist[it - 1] = nrm;
+    }
+    if (la.no_exit) return false;
+    if (nrm < st->tolabs) {
+        if (leader()) st->state = 2;
+        return true;
+    }
+    if (isnan(nrm)) {
+        if (leader()) st->state = 3;
+        return true;
+    }
+    return false;
+}
+
+// a scalar the loop cannot go on with; under FLAG_NO_EXIT no test is taken.  Returns true when the caller must return.
+__device__ __forceinline__ bool loop_breakdown(const LoopArgs &la, bool bad)
+{
+    if (!bad || la.no_exit) return false;
+    if (leader()) la.st->state = 3;
+    return true;
+}
+
 // The test on rho of a guarded solve (CUDAMAT_FLAG_GUARD), at the top of iteration it >= 1 after check_full, so that a
 // convergence exit wins (at it = 0, rho = r.r).  rho = rw.r and mag = sum |rw_i| |r_i| come from the same terms in the same
 // order (k_full<VEC, true>), so |rho| <= mag holds in floating point too; eps = GUARD_RHO_ULPS * 2^-52 (exact).  When
@@ -428,6 +461,25 @@ __device__ __forceinline__ void vec_loop(int64_t n, Body body)
     const int64_t first = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = first; i < n2; i += stride) body(i, Width<2>{});
     for (int64_t i = 2 * n2 + first; i < n; i += stride) body(i, Width<1>{});
+}
+
+// vec_loop's dealing for both alignments.  VEC = 1 is vec_loop<1>.  VEC = 0 (an operand 8 bytes off a 16-byte boundary) keeps
+// the pairs and visits their elements one by one, .x before .y, then the odd tail: a thread's partial sums take the same
+// terms in the same order, so the bits of a solve do not depend on where the caller's vectors start.
+template <int VEC, class Body>
+__device__ __forceinline__ void pair_loop(int64_t n, Body body)
+{
+    if constexpr (VEC) {
+        vec_loop<1>(n, body);
+    } else {
+        const int64_t n2 = n / 2;
+        const int64_t first = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
+        for (int64_t i = first; i < n2; i += stride) {
+            body(2 * i, Width<1>{});
+            body(2 * i + 1, Width<1>{});
+        }
+        for (int64_t i = 2 * n2 + first; i < n; i += stride) body(i, Width<1>{});
+    }
 }
 
 // a null pointer counts as aligned (an operand the launch does not use)

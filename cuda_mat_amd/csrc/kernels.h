@@ -205,6 +205,22 @@ int launch_l2_mr(hipStream_t s, LoopArgs la, ScalarSrc d11, ScalarSrc d2, Scalar
                  double *parts, int *nparts);
 // the stopping test of the last sweep, after the loop (one workgroup)
 int launch_l2_check(hipStream_t s, LoopArgs la, ScalarSrc full);
+// Conjugate gradients, CUDAMAT_LOOP_CG (cg.hip): k_cg_p | SpMV (+ p.q) | k_cg_step | [M^-1 | k_cg_rz].  Scalars as for
+// BiCGSTAB(2): formed in the consuming kernel's prologue; !(gamma > 0), !(rho > 0) or a scalar that is not finite freezes the
+// loop in state 3 unless la.no_exit.
+// the stopping test of the iteration before (full = (r.z, r.r), stride 2); rho, beta; p = z + beta p
+int launch_cg_p(hipStream_t s, LoopArgs la, ScalarSrc full, int64_t n, const double *z, double *p);
+// gamma = p.q (gam), alpha; x += alpha p; r -= alpha q; parts = (r.r, r.r), stride 2; it++; the progress word
+int launch_cg_step(hipStream_t s, LoopArgs la, ScalarSrc gam, int64_t n, double *x, double *r, const double *p, const double *q,
+                   double *parts, int *nparts);
+// parts = (r.z, r.r), stride 2; returns at once when frozen
+int launch_cg_rz(hipStream_t s, LoopArgs la, int64_t n, const double *r, const double *z, double *parts, int *nparts);
+// the stopping test of the last iteration, after the loop (one workgroup)
+int launch_cg_check(hipStream_t s, LoopArgs la, ScalarSrc full);
+// Symmetry of a CSR matrix with strictly increasing rows (symmetry.hip): parts[2 b] = stored off-diagonal entries (i, j)
+// without a stored (j, i) that workgroup b met, parts[2 b + 1] = its max |a_ij - a_ji| over the others (inf where that
+// difference is NaN); *nparts workgroups
+int launch_symmetry(hipStream_t s, int n, int64_t nnz, const int *rp, const int *ci, const double *val, double *parts, int *nparts);
 // standalone stopping tests (one workgroup)
 int launch_check(hipStream_t s, LoopArgs la, ScalarSrc src, int which);
 // out[k] = sum of partials, k < K (one workgroup)

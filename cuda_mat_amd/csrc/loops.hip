@@ -6,6 +6,8 @@
 //                             :425-578)
 //   CUDAMAT_LOOP_PIPELINED  = the same recurrences re-arranged (Cools & Vanroose 2017, Alg. 4): not a reference loop
 //   CUDAMAT_LOOP_BICGSTAB_L2 = BiCGSTAB(2) (Sleijpen & Fokkema 1993): not a reference loop; one sweep = four products
+//   CUDAMAT_LOOP_CG         = preconditioned conjugate gradients (Hestenes & Stiefel 1952) for symmetric positive definite
+//                             systems: what the reference's CPU program (BiCG) computes on a symmetric matrix
 //
 // One solve = Solve::setup (validation, set-up on first use, r0 and the LoopState: pbicgstab.cu:67-74), then ONE of
 // the loop forms, then Solve::finish (exit bookkeeping, statistics):
@@ -14,6 +16,7 @@
 //   iterate_reference five launches per iteration                       (everything else; + M^-1, + exchanges when sharded)
 //   iterate_pipelined four launches per iteration, reductions beside the SpMVs (sharded runs)
 //   iterate_l2        ten launches per sweep of CUDAMAT_LOOP_BICGSTAB_L2 (four SpMVs, six vector kernels; + M^-1; one GPU)
+//   iterate_cg        three launches per iteration of CUDAMAT_LOOP_CG (one SpMV, two vector kernels; + M^-1 and one more; one GPU)
 // A guarded solve (CUDAMAT_FLAG_GUARD, or the switch GUARD = 1) always takes iterate_reference, with the GUARD instantiations
 // of k_update_p / k_full; cudamat_solver_solve strings its segments together (restarts on a lost rho, verified convergence).
 // The host-side loop (run_host_loop) is shared by the last three: it enqueues iteration k and looks at the progress
@@ -56,7 +59,10 @@ int wait_progress(cudamat_solver *s, hipStream_t st, int j, const char *what, un
 }
 
 // history entries per iteration: the half and the full step, or the end of the iteration alone
-static int history_per_iteration(int loop) { return loop == CUDAMAT_LOOP_PBICGSTAB2 || loop == CUDAMAT_LOOP_BICGSTAB_L2 ? 1 : 2; }
+static int history_per_iteration(int loop)
+{
+    return loop == CUDAMAT_LOOP_PBICGSTAB2 || loop == CUDAMAT_LOOP_BICGSTAB_L2 || loop == CUDAMAT_LOOP_CG ? 1 : 2;
+}
 
 int history_need(int loop, int maxit)
 {
@@ -107,7 +113,7 @@ struct Solve {
     const Config *cfg = nullptr;
     hipStream_t st = nullptr;
     int n = 0;
-    bool profile = false, sharded = false, perm = false, pipelined = false, pipe_pc = false, guard = false, l2 = false;
+    bool profile = false, sharded = false, perm = false, pipelined = false, pipe_pc = false, guard = false, l2 = false, cg = false;
     double rho_eps = 0.0;              // guarded solves: GUARD_RHO_ULPS * 2^-52 (check_rho)
     double *x_user = nullptr;          // the caller's x (x itself is the level-major copy while perm)
     int hist_base = 0;
@@ -141,6 +147,8 @@ struct Solve {
     int l2_prologue();
     int l2_ahat(const double *in, double *out, int dot, const double *w, double *parts);
     int iterate_l2();
+    int cg_prologue();
+    int iterate_cg();
     int pipe_reduce(ScalarSrc parts, int K, double *out, int slot);
     int pipe_wait(int slot);
     int finish(bool *precond_gave_up, cudamat_stats *out);
@@ -153,8 +161,13 @@ int Solve::setup()
     CM_ARG(precond == CUDAMAT_PRECOND_NONE || precond == CUDAMAT_PRECOND_ILU0 || precond == CUDAMAT_PRECOND_BLOCK_ILU0,
            "precond");
     CM_ARG(loop == CUDAMAT_LOOP_PBICGSTAB || loop == CUDAMAT_LOOP_PBICGSTAB2 || loop == CUDAMAT_LOOP_PIPELINED ||
-           loop == CUDAMAT_LOOP_BICGSTAB_L2, "loop");
+           loop == CUDAMAT_LOOP_BICGSTAB_L2 || loop == CUDAMAT_LOOP_CG, "loop");
     CM_ARG(maxit >= 0, "maxit");
+    if (loop == CUDAMAT_LOOP_CG) {
+        CM_ARG(!s->sharded, "CUDAMAT_LOOP_CG is one-GPU only: sharded solvers take the BiCGSTAB loops");
+        CM_ARG(precond != CUDAMAT_PRECOND_BLOCK_ILU0, "CUDAMAT_LOOP_CG takes CUDAMAT_PRECOND_NONE or CUDAMAT_PRECOND_ILU0, not CUDAMAT_PRECOND_BLOCK_ILU0");
+        CM_ARG(!(flags & CUDAMAT_FLAG_GUARD), "CUDAMAT_FLAG_GUARD (or the switch GUARD) does not cover CUDAMAT_LOOP_CG");
+    }
     if (loop == CUDAMAT_LOOP_BICGSTAB_L2) {
         CM_ARG(!s->sharded, "CUDAMAT_LOOP_BICGSTAB_L2 is one-GPU only: sharded solvers take the other loops");
         CM_ARG(precond != CUDAMAT_PRECOND_BLOCK_ILU0, "CUDAMAT_LOOP_BICGSTAB_L2 takes CUDAMAT_PRECOND_NONE or CUDAMAT_PRECOND_ILU0, not CUDAMAT_PRECOND_BLOCK_ILU0");
@@ -168,6 +181,17 @@ int Solve::setup()
     CM_ARG(!(precond && s->d && loop == CUDAMAT_LOOP_PIPELINED),
            "the pipelined loop takes no preconditioner together with a shift (CUDAMAT_LOOP_PBICGSTAB / _PBICGSTAB2 do)");
     CM_HIP(hipSetDevice(s->ctx->device));
+    // CG on a matrix that is not symmetric runs without complaint and does not converge: the verdict on the values held
+    // (computed once, symmetry.hip) or the caller's word.  No tolerance is invented.
+    if (loop == CUDAMAT_LOOP_CG && !(flags & CUDAMAT_FLAG_ASSUME_SYMMETRIC)) {
+        CM_TRY(ensure_symmetry(s));
+        if (s->sym_unmatched > 0 || s->sym_max_diff > 0.0) {
+            set_error("bad argument: CUDAMAT_LOOP_CG needs a symmetric matrix: %lld stored off-diagonal entries have no transposed "
+                      "partner, max |a_ij - a_ji| = %g over the others (CUDAMAT_FLAG_ASSUME_SYMMETRIC skips this check)",
+                      s->sym_unmatched, s->sym_max_diff);
+            return CUDAMAT_ERR_ARG;
+        }
+    }
     cfg = &s->ctx->cfg;
     t_begin = now_s();
     st = s->ctx->stream;
@@ -230,6 +254,7 @@ int Solve::setup()
     pipelined = loop == CUDAMAT_LOOP_PIPELINED;
     pipe_pc = pipelined && precond != CUDAMAT_PRECOND_NONE;
     l2 = loop == CUDAMAT_LOOP_BICGSTAB_L2;
+    cg = loop == CUDAMAT_LOOP_CG;
     guard = (flags & CUDAMAT_FLAG_GUARD) != 0;
     rho_eps = guard ? (double)cfg->guard_rho_ulps * 0x1p-52 : 0.0;       // (exact: at most 2^52 ulps)
     la = LoopArgs{s->st, s->hist + hist_base, s->hist_cap - hist_base, loop, (flags & CUDAMAT_FLAG_NO_EXIT) ? 1 : 0, s->snap_dev, kRing, 0};
@@ -245,9 +270,9 @@ int Solve::setup()
     CM_HIP(hipMemcpyAsync(s->pw, x, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
     CM_TRY(spmv_local(s, s->pw, s->r, 0, nullptr, nullptr, la_none, CHECK_NONE, nosrc));
     CM_TRY(launch_init(st, n, b, s->r, s->rw, s->p, s->parts_full, &np_full));   // :69-74
-    // (BiCGSTAB(2) promises the same bits wherever b and x start: its start sums are formed again from r0, a work vector, in the
-    // pair order -- launch_init deals rows when b is 8 bytes off)
-    if (l2) CM_TRY(launch_l2_start(st, n, s->r, s->parts_full, &np_full));
+    // (BiCGSTAB(2) and CG promise the same bits wherever b and x start: their start sums are formed again from r0, a work vector,
+    // in the pair order -- launch_init deals rows when b is 8 bytes off)
+    if (l2 || cg) CM_TRY(launch_l2_start(st, n, s->r, s->parts_full, &np_full));
     full_src = ScalarSrc{s->parts_full, np_full, 2};
     if (sharded) {
         CM_TRY(launch_reduce_parts(st, full_src, 2, s->red + 4, 0));
@@ -457,6 +482,42 @@ int Solve::iterate_l2()
     return CUDAMAT_OK;
 }
 
+// ============================================================================================ conjugate gradients
+// CUDAMAT_LOOP_CG (the iteration: include/cudamat_cg.h; the kernels: cg.hip).  Vectors: p = p (launch_init left p = r0; the first
+// beta is 0), q = v, r = r, and with a preconditioner z = pw, t the scratch of M^-1; without one z is r.  x is the caller's.
+// The scalars: CgState in the slot behind the solve's LoopState (common.h).  With a preconditioner the sums (r.z, r.r) of
+// k_cg_rz replace those of k_cg_step in parts_full -- r.r from the same terms in the same order.
+int Solve::cg_prologue()
+{
+    CM_HIP(hipMemsetAsync(cg_state(s->st), 0, sizeof(CgState), st));
+    if (!precond) return CUDAMAT_OK;
+    prof_mark();
+    CM_TRY(precond_apply(s, s->r, s->t, s->pw));                           // z = M^-1 r0
+    prof_mark();
+    CM_TRY(launch_cg_rz(st, la, n, s->r, s->pw, s->parts_full, &np_full));
+    full_src = ScalarSrc{s->parts_full, np_full, 2};
+    return CUDAMAT_OK;
+}
+
+int Solve::iterate_cg()
+{
+    double *const p = s->p, *const q = s->v, *const r = s->r;
+    const double *const z = precond ? s->pw.get() : s->r.get();
+    CM_TRY(launch_cg_p(st, la, full_src, n, z, p));                         // the test on ||r||; rho, beta; p = z + beta p
+    prof_mark();
+    CM_TRY(spmv_local(s, p, q, 1, p, s->parts_rv, la, CHECK_NONE, nosrc));  // q = A p, p.q
+    prof_mark();
+    CM_TRY(launch_cg_step(st, la, ScalarSrc{s->parts_rv, spmv_parts(s), 2}, n, x, r, p, q, s->parts_full, &np_full));
+    if (precond) {
+        prof_mark();
+        CM_TRY(precond_apply(s, r, s->t, s->pw));                           // z = M^-1 r (scratch vectors only: harmless when frozen)
+        prof_mark();
+        CM_TRY(launch_cg_rz(st, la, n, r, s->pw, s->parts_full, &np_full));
+    }
+    full_src = ScalarSrc{s->parts_full, np_full, 2};
+    return CUDAMAT_OK;
+}
+
 // ============================================================================================ small systems
 // Vectors resident in L2: three launches per iteration instead of five -- the vector updates in front of the two SpMVs
 // are folded into them (small_loops.hip); p, v and r are double-buffered.
@@ -468,7 +529,7 @@ bool Solve::wants_fused() const
 {
     const bool forced = cfg->fused >= 0;
     const long long max_rows = forced ? cfg->fused : 300000;
-    return loop != CUDAMAT_LOOP_PIPELINED && !l2 && !sharded && !precond && s->spmv_mode == 0 && fused_spmv_supported(s->plan) && n > 0 &&
+    return loop != CUDAMAT_LOOP_PIPELINED && !l2 && !cg && !sharded && !precond && s->spmv_mode == 0 && fused_spmv_supported(s->plan) && n > 0 &&
            n <= max_rows && (forced || s->plan.stream_rows > 0);
 }
 
@@ -476,7 +537,7 @@ bool Solve::wants_fused() const
 // launch, grid barriers instead of launch boundaries (small_loops.hip).  The option RESIDENT = 0 disables.
 bool Solve::wants_resident()
 {
-    if (loop_form != 1 || l2 || profile || s->resident_off || !cfg->resident || !resident_loop_supported(s->plan, n)) return false;
+    if (loop_form != 1 || l2 || cg || profile || s->resident_off || !cfg->resident || !resident_loop_supported(s->plan, n)) return false;
     // all workgroups must be resident at once: at most one per two compute units of THIS device
     if (s->device_cus == 0 && hipDeviceGetAttribute(&s->device_cus, hipDeviceAttributeMultiprocessorCount, s->ctx->device) != hipSuccess)
         s->device_cus = -1;
@@ -644,6 +705,7 @@ int Solve::run_host_loop()
         la.k = k;
         if (pipelined) CM_TRY(iterate_pipelined(k));
         else if (l2) CM_TRY(iterate_l2());
+        else if (cg) CM_TRY(iterate_cg());
         else if (loop_form == 1) CM_TRY(iterate_fused());
         else CM_TRY(iterate_reference());
     }
@@ -665,7 +727,9 @@ int Solve::finish(bool *precond_gave_up, cudamat_stats *out)
             CM_TRY(precond_apply(s, s->l2_y, s->t, s->pw));
             CM_TRY(launch_axpy(st, n, 1.0, s->pw, x));
         }
-    } else
+    } else if (cg)
+        CM_TRY(launch_cg_check(st, la, full_src));
+    else
         CM_TRY(launch_check(st, la, full_src, CHECK_FULL));
     CM_HIP(hipMemcpyAsync(&s->st_ring[0], s->st, sizeof(LoopState), hipMemcpyDeviceToHost, st));
     CM_HIP(hipStreamSynchronize(st));                              // :372
@@ -765,6 +829,15 @@ int Solve::finish(bool *precond_gave_up, cudamat_stats *out)
             printf("initial norm = %g\n", fin.nrm0);
             for (int i = 0; i < s->hist_count; i++) printf("sweep = %d, norm = %g\n", i, h[i]);
             if (fin.state == 3) printf("BiCGSTAB(2) breakdown in sweep %d, cannot continue\n", fin.it);
+        } else if (cg) {
+            CgState c{};
+            CM_HIP(hipMemcpy(&c, cg_state(s->st), sizeof(CgState), hipMemcpyDeviceToHost));
+            printf("initial norm = %g\n", fin.nrm0);
+            for (int i = 0; i < s->hist_count; i++) printf("k = %d, norm = %g\n", i, h[i]);
+            if (fin.state == 3 && c.why == 1)
+                printf("rho = r.M^-1 r = %g in iteration %d: the preconditioner is not positive definite, cannot continue\n", c.rho_now, fin.it);
+            else if (fin.state == 3 && c.why == 2)
+                printf("gamma = p.Ap = %g in iteration %d: the matrix is not positive definite, cannot continue\n", c.gamma, fin.it);
         } else if (loop != CUDAMAT_LOOP_PBICGSTAB2) {
             printf("gpu, init residual:norm %20.16f\n", fin.nrm0);            // :77
             for (int i = hist_base; i < s->hist_count; i++) {                  // (a restart segment prints its own part)
@@ -796,6 +869,7 @@ int solve_once(cudamat_solver *s, const double *b, double *x, int precond, int l
     Range range_loop("cudamat: iteration loop (enqueue + lagged checks)");
     if (q.pipelined) CM_TRY(q.pipelined_prologue());
     if (q.l2) CM_TRY(q.l2_prologue());
+    if (q.cg) CM_TRY(q.cg_prologue());
     q.loop_form = !q.guard && q.wants_fused() ? 1 : 0;       // (a guarded solve: five launches, whatever the system's size)
     if (q.loop_form == 1 && !s->v2) {
         const size_t count = (size_t)(s->n_pad > 0 ? s->n_pad : 1), nb = sizeof(double) * count;
@@ -871,6 +945,7 @@ extern "C" int cudamat_solver_solve(cudamat_solver *s, const double *b, double *
     const bool exits = !(flags & CUDAMAT_FLAG_NO_EXIT);
     if (guard) {
         CM_ARG(loop != CUDAMAT_LOOP_BICGSTAB_L2, "CUDAMAT_FLAG_GUARD (or the switch GUARD) does not cover CUDAMAT_LOOP_BICGSTAB_L2");
+        CM_ARG(loop != CUDAMAT_LOOP_CG, "CUDAMAT_FLAG_GUARD (or the switch GUARD) does not cover CUDAMAT_LOOP_CG");
         CM_ARG(loop != CUDAMAT_LOOP_PIPELINED,
                "CUDAMAT_FLAG_GUARD does not cover CUDAMAT_LOOP_PIPELINED, which verifies its iterates itself");
         CM_ARG(!s->sharded, "CUDAMAT_FLAG_GUARD does not cover sharded solvers yet (its third sum would have to ride in the all-reduce)");

@@ -446,9 +446,10 @@ extern "C" int cudamat_solver_solve_shifts(cudamat_solver *s, int nrhs, const do
     // solver holds (those of cudamat_solver_ilu0_shift serve the single solve only: loops.hip)
     CM_ARG(!(s->d && precond), "the (A0 + I d) variant has no preconditioner (pbicgstab.h:110)");
     CM_ARG(maxit >= 0, "maxit");
-    // (CUDAMAT_LOOP_BICGSTAB_L2 is neither `plain` nor `pc` below: its columns run one cudamat_solver_solve each, form 0)
+    // (CUDAMAT_LOOP_BICGSTAB_L2 and CUDAMAT_LOOP_CG are neither `plain` nor `pc` below: their columns run one cudamat_solver_solve
+    // each, form 0)
     CM_ARG(loop == CUDAMAT_LOOP_PBICGSTAB || loop == CUDAMAT_LOOP_PBICGSTAB2 || loop == CUDAMAT_LOOP_PIPELINED ||
-           loop == CUDAMAT_LOOP_BICGSTAB_L2, "loop");
+           loop == CUDAMAT_LOOP_BICGSTAB_L2 || loop == CUDAMAT_LOOP_CG, "loop");
     CM_HIP(hipSetDevice(s->ctx->device));
     const double t0 = now_s();
     const Config &cfg = s->ctx->cfg;

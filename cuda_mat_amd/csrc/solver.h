@@ -79,6 +79,10 @@ struct cudamat_solver {
     cm::SpmvPlan plan{};
     int spmv_mode = -1;        // -1 undecided, 0 CSR forms, 1 blocked two-phase kernels, 2 SELL-C-sigma, 3 row-pattern dictionary
     bool cols_sorted = true;   // every row's columns strictly increasing (checked at creation)
+    // cudamat_solver_symmetry (symmetry.hip): the verdict on the values the solver holds, dropped by cudamat_solver_set_values
+    bool sym_known = false;
+    long long sym_unmatched = 0;   // stored off-diagonal entries (i, j) without a stored (j, i)
+    double sym_max_diff = 0.0;     // max |a_ij - a_ji| over the others
     cm::PbPlan pb{};
     cm::SellPlan sell{};
     cm::PatPlan pat{};
@@ -108,6 +112,7 @@ struct cudamat_solver {
     cm::DevBuf<double> parts_full, parts_rv, parts_half, parts_tt;
     cm::DevBuf<double> red;    // 8 doubles
     cm::DevBuf<cm::LoopState> st;             // device: the solve's LoopState, and a second slot that holds the L2State of BiCGSTAB(2)
+                                              // or the CgState of CG
     cm::PinnedBuf<cm::LoopState> st_ring;     // pinned host, kRing slots
     hipEvent_t ev[cm::kRing] = {};
     cm::PinnedBuf<unsigned long long> snap_host;   // pinned: per-iteration progress words written by k_full
@@ -258,6 +263,7 @@ bool trsv_syncfree_active(cudamat_solver *s);
 int trsv_form_code(cudamat_solver *s);           // 0 level launches, 1 dependency-driven, 2 single workgroup in LDS
 void trsv_group_counts(cudamat_solver *s, int *groups_l, int *groups_u);   // hybrid factors: groups of levels (0: not split)
 void trsv_disable_syncfree(cudamat_solver *s);   // sticky: level-by-level kernels from now on
+int ensure_symmetry(cudamat_solver *s);          // symmetry.hip: sym_unmatched / sym_max_diff of the values held, computed once
 void many_release(cudamat_solver *s);            // the buffers of the batched loop (loops_batch.hip)
 // the SpMV copies in other layouts and the value maps that belong to them: gone, the form is chosen again at the next use
 void spmv_copies_drop(cudamat_solver *s);

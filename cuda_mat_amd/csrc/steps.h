@@ -106,6 +106,29 @@ __device__ __forceinline__ double step_l2_sub2(double v, double a, double b, dou
     return fma(-g2, b, fma(-g1, a, v));
 }
 
+// ------------------------------------------------------------------ conjugate gradients (CUDAMAT_LOOP_CG, cg.hip)
+__device__ __forceinline__ double step_cg_beta(double rho, double rho_prev) { return rho / rho_prev; }
+
+__device__ __forceinline__ double step_cg_alpha(double rho, double gamma) { return rho / gamma; }
+
+__device__ __forceinline__ double step_cg_p(double z, double p, double beta)               // p = z + beta p
+{
+#pragma clang fp contract(off)
+    return fma(beta, p, z);
+}
+
+__device__ __forceinline__ double step_cg_x(double x, double p, double alpha)              // x += alpha p
+{
+#pragma clang fp contract(off)
+    return fma(alpha, p, x);
+}
+
+__device__ __forceinline__ double step_cg_r(double r, double q, double alpha)              // r -= alpha q
+{
+#pragma clang fp contract(off)
+    return fma(-alpha, q, r);
+}
+
 // the dots that ride with the steps (:74, :81, :106, :111, :136, :142): one more term into a thread's partial sum, one rounding
 __device__ __forceinline__ void dot_step(double &acc, double a, double b)
 {

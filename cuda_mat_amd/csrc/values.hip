@@ -209,6 +209,7 @@ int set_values(cudamat_solver *s, const double *val)
     }
     if (perm_changed) CM_TRY(ilu_perm_drop(s));      // (allocates the U positions before it lets go of anything)
     // ---- the numbers
+    s->sym_known = false;                            // (the verdict of cudamat_solver_symmetry belonged to the old values)
     if (nnz) CM_HIP(hipMemcpyAsync(s->val, val, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToDevice, st));
     if (dict_wanted) {
         s->vd = std::move(nv);                       // (the old dictionary goes here; every copy is re-pointed or dropped below)

@@ -13,6 +13,8 @@
 //     1 = the (A0 + I*d) entry point, with A's diagonal split off and x0 = 1
 // and  -L  (BiCGSTAB(2) in place of BiCGSTAB, for the systems on which BiCGSTAB stalls: with -C2 ILU(0)-preconditioned, with
 // -C0 or -C1 without a preconditioner; one GPU; -I then counts sweeps of four products)
+// and  -K  (conjugate gradients in place of the chosen BiCGSTAB loop, for symmetric positive definite matrices: with -C2
+// ILU(0)-preconditioned, with -C0 or -C1 without a preconditioner; one GPU; one product per iteration)
 // Unlike the reference, the exit status reflects the outcome (upstream always returns EXIT_FAILURE) and a
 // preconditioned run that exhausts maxit reports "method failed" (upstream cannot tell).
 #include <cstdio>
@@ -42,6 +44,7 @@ struct Options {
     long seed = -1;
     int gpus = 1;
     bool l2 = false;
+    bool cg = false;
 };
 
 struct System {
@@ -82,6 +85,7 @@ bool parse(int argc, char **argv, Options &o)
         case 'S': o.seed = std::stol(value); break;
         case 'G': o.gpus = std::stoi(value); break;
         case 'L': o.l2 = true; break;
+        case 'K': o.cg = true; break;
         default:
             fprintf(stderr, "Unknown switch '-%s'\n", arg + 1);
             return false;
@@ -208,7 +212,10 @@ int main(int argc, char *argv[])
     double dtAlg = 0.0;
     const double t_begin = second();
     bool solved;
-    if (opt.l2) {
+    if (opt.cg) {                     // (d = NULL: no shift; x0 = NULL: ones)
+        solved = (opt.method == 2 ? cg_lu_precond : cg)(sys.n, sys.nnz, sys.A, sys.iA, sys.jA, nullptr, nullptr, sys.b, opt.maxit,
+                                                        opt.tol, opt.trace, x.data(), &dtAlg);
+    } else if (opt.l2) {
         if (opt.method == 2)          // (d = NULL: no shift; x0 = NULL: ones)
             solved = bicgstab_l2_lu_precond(sys.n, sys.nnz, sys.A, sys.iA, sys.jA, nullptr, nullptr, sys.b, opt.maxit, opt.tol,
                                             opt.trace, x.data(), &dtAlg) && cudamat_last_stats()->converged;

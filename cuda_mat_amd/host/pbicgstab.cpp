@@ -114,3 +114,17 @@ bool bicgstab_l2_lu_precond(int n, int nnz, double *A0, int *iA0, int *jA0, doub
     return run(n, nnz, A0, iA0, jA0, d, x0, b, CUDAMAT_PRECOND_ILU0, CUDAMAT_LOOP_BICGSTAB_L2, maxit, tol, debug, x, dtAlg,
                true);
 }
+
+// Conjugate gradients for symmetric positive definite systems: the same shims with CUDAMAT_LOOP_CG (one GPU: cudamat_solve
+// refuses a sharded run, and a matrix that is not symmetric, with a message)
+bool cg(int n, int nnz, double *A0, int *iA0, int *jA0, double *d, double *x0, double *b, int maxit, double tol, bool debug,
+        double *x, double *dtAlg)
+{
+    return run(n, nnz, A0, iA0, jA0, d, x0, b, CUDAMAT_PRECOND_NONE, CUDAMAT_LOOP_CG, maxit, tol, debug, x, dtAlg, false);
+}
+
+bool cg_lu_precond(int n, int nnz, double *A0, int *iA0, int *jA0, double *d, double *x0, double *b, int maxit, double tol,
+                   bool debug, double *x, double *dtAlg)
+{
+    return run(n, nnz, A0, iA0, jA0, d, x0, b, CUDAMAT_PRECOND_ILU0, CUDAMAT_LOOP_CG, maxit, tol, debug, x, dtAlg, false);
+}

@@ -113,6 +113,8 @@ extern "C" {
                                        residual is within twice tol * ||r0||.  Needs tol > 0 (or FLAG_NO_EXIT, which runs
                                        the guarded kernels without ever taking the test).  The switch GUARD = 1 sets it
                                        for every solve of a context.  Off by default: a departure from the reference.    */
+/* (conjugate gradients for symmetric positive definite systems: its loop id and its flag are in cudamat_cg.h) */
+#include "cudamat_cg.h"
 
 typedef struct cudamat_ctx cudamat_ctx;         /* device + stream + reduction workspace  */
 typedef struct cudamat_solver cudamat_solver;   /* one HBM-resident linear system          */
@@ -360,6 +362,12 @@ int cudamat_solver_set_values(cudamat_solver *s, const double *val);
  * *map_bytes = device bytes of the value maps the solver holds (0 before the first call and for forms that need none),
  * *rebuilt_last = 1 when the last call changed the storage class and the SpMV form is chosen again.  Any may be NULL.     */
 int cudamat_solver_set_values_info(cudamat_solver *s, int *count, double *seconds_last, size_t *map_bytes, int *rebuilt_last);
+/* Is the matrix the solver holds symmetric?  *unmatched = stored off-diagonal entries (i, j) without a stored (j, i),
+ * *max_abs_diff = max |a_ij - a_ji| over the stored pairs (inf where a difference is NaN).  (0, 0.0): symmetric, pattern and
+ * values.  Exact: no tolerance; a shift (cudamat_solver_set_shift) sits on the diagonal and does not enter.  One pass over the
+ * entries on the device at the first call; the verdict is kept until cudamat_solver_set_values.  Either pointer may be NULL.
+ * CUDAMAT_ERR_ARG for a sharded solver and for a matrix whose rows are not strictly increasing in their columns.            */
+int cudamat_solver_symmetry(cudamat_solver *s, long long *unmatched, double *max_abs_diff);
 /* the same on the rank's DIAGONAL BLOCK (rows and columns it owns) -- allowed in a sharded solver;
  * no collective is involved, neither here nor in the preconditioning steps            */
 int cudamat_solver_block_ilu0(cudamat_solver *s);

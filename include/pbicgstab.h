@@ -161,6 +161,23 @@ bool bicgstab_l2_lu_precond(int n, int nnz,
                             int maxit, double tol, bool debug,
                             double OUT(*x), double OUT(*dtAlg));
 
+/* EXTENSION of this library: conjugate gradients (CUDAMAT_LOOP_CG of cudamat.h) for symmetric positive definite systems.
+ * (A0 + I*d) x = b from x0, no preconditioner; d may be NULL (no shift), x0 may be NULL (x0 = 1).  One product per iteration.
+ * Returns true when the method converged; false with a message when A0 is not symmetric, and false with
+ * cudamat_last_stats()->breakdown when it is not positive definite.  Single GPU only. */
+bool cg(int n, int nnz,
+        double IN(*A0), int IN(*iA0), int IN(*jA0),
+        double IN(*d), double IN(*x0), double IN(*b),
+        int maxit, double tol, bool debug,
+        double OUT(*x), double OUT(*dtAlg));
+
+/* ... with the ILU(0) preconditioner of A0 + diag(d) (of A0 when d is NULL).  Returns true when the method converged. */
+bool cg_lu_precond(int n, int nnz,
+                   double IN(*A0), int IN(*iA0), int IN(*jA0),
+                   double IN(*d), double IN(*x0), double IN(*b),
+                   int maxit, double tol, bool debug,
+                   double OUT(*x), double OUT(*dtAlg));
+
 /* statistics of the last solve issued by the calling thread */
 const cudamat_stats *cudamat_last_stats();
 
