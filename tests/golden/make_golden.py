@@ -14,6 +14,10 @@ records what the reference itself produces:
 
 The .npz files are data (inputs + expected outputs); no reference source is
 stored.  Run:  python tests/golden/make_golden.py
+
+  cg_pinned.npz     : x and the residual history of every case that tests/test_gpu_cg_bits.py pins, as the CPU mirror of
+                      CUDAMAT_LOOP_CG (tests/test_cg_rounding.py) computes them; needs neither the reference nor a GPU.
+                      Run:  python tests/golden/make_golden.py cg_pinned
 """
 import ctypes as C
 import os
@@ -75,5 +79,16 @@ def main():
             print("bicg", name, "iters", iters)
 
 
+def cg_pinned():
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_cg_rounding as G
+    values = G.recorded_values()
+    np.savez_compressed(os.path.join(HERE, "cg_pinned.npz"), **values)
+    print("cg_pinned", len(values), "arrays")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["cg_pinned"]:
+        cg_pinned()
+    else:
+        main()
