@@ -234,7 +234,8 @@ int launch_l2_dot(hipStream_t s, LoopArgs la, int64_t n, const double *r2, const
     CM_VEC_LAUNCH(all_aligned16(r2, r0), g, k_l2_dot<VEC>, la, n, r2, r0, parts);
 }
 
-// the minimal-residual step: (g1, g2) from the five dots; y += g1 r0 + g2 r1; u0 -= g1 u1 + g2 u2; r0 -= g1 r1 + g2 r2;
+// the minimal-residual step: (g1, g2) from the five dots, by elimination (step_l2_mr: exact under powers of two; a zero
+// pivot r1.r1 or t, or a quotient that is not finite, is the breakdown); y += g1 r0 + g2 r1; u0 -= g1 u1 + g2 u2; r0 -= g1 r1 + g2 r2;
 // omega = g2; (r0.r~, r0.r0); it++.  The last kernel of a sweep: it publishes the progress word, frozen or not.
 template <int VEC>
 __global__ __launch_bounds__(kBlock) void k_l2_mr(LoopArgs la, ScalarSrc d11, ScalarSrc d2, ScalarSrc d20, int64_t n, double *y,
@@ -252,9 +253,9 @@ __global__ __launch_bounds__(kBlock) void k_l2_mr(LoopArgs la, ScalarSrc d11, Sc
     load_scalars<2>(d11, a, lds);      // r1.r1, r1.r0
     load_scalars<2>(d2, c, lds);       // r2.r1, r2.r2
     load_scalars<1>(d20, e, lds);      // r2.r0
-    double det, g1, g2;
-    step_l2_mr(a[0], c[0], c[1], a[1], e[0], &det, &g1, &g2);
-    if (loop_breakdown(la, det == 0.0 || !isfinite(det) || !isfinite(g1) || !isfinite(g2))) {
+    double sq, piv, g1, g2;
+    step_l2_mr(a[0], c[0], c[1], a[1], e[0], &sq, &piv, &g1, &g2);
+    if (loop_breakdown(la, a[0] == 0.0 || piv == 0.0 || !isfinite(sq) || !isfinite(piv) || !isfinite(g1) || !isfinite(g2))) {
         publish_progress(la, 3);
         return;
     }

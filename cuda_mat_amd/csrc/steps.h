@@ -63,16 +63,25 @@ __device__ __forceinline__ double step_l2_beta(double alpha, double rho1, double
 
 __device__ __forceinline__ double step_l2_alpha(double rho0, double gamma) { return rho0 / gamma; }
 
-// The minimal-residual half: [[a11, a12], [a12, a22]] (g1, g2) = (b1, b2) by Cramer's rule, every product and difference
-// rounded on its own; *det is what the caller tests for a singular system.
-__device__ __forceinline__ void step_l2_mr(double a11, double a12, double a22, double b1, double b2, double *det, double *g1,
-                                           double *g2)
+// The minimal-residual half: [[a11, a12], [a12, a22]] (g1, g2) = (b1, b2) by elimination on the pivot a11 = r1.r1:
+//   s = a12 / a11;  t = a22 - s a12;  g2 = (b2 - s b1) / t;  g1 = (b1 - a12 g2) / a11      (one fma per difference)
+// Under (c b, c x0), c a power of two, the five dots scale with c^2, and so do t and both numerators; s, g1, g2 do not scale.
+// Under (c A, b, x0 / c): b1 ~ c, a11, b2 ~ c^2, a12 ~ c^3, a22 ~ c^4, and s ~ c, t ~ c^4, g1 ~ 1 / c, g2 ~ 1 / c^2.  No
+// intermediate carries a higher power of c than the dots themselves (the determinant of Cramer's rule carries c^4 under the
+// first scaling and c^6 under the second, and leaves the range of a double where the dots do not), and a scaling by a power of
+// two commutes with every rounding here: the bits of g1 and g2 are those of the unscaled system, scaled.  *s_out and *piv
+// (= t) are what the caller tests, with a11, for a singular system.
+__device__ __forceinline__ void step_l2_mr(double a11, double a12, double a22, double b1, double b2, double *s_out, double *piv,
+                                           double *g1, double *g2)
 {
 #pragma clang fp contract(off)
-    const double dd = a11 * a22 - a12 * a12;
-    *det = dd;
-    *g1 = (b1 * a22 - b2 * a12) / dd;
-    *g2 = (a11 * b2 - a12 * b1) / dd;
+    const double s = a12 / a11;
+    const double t = fma(-s, a12, a22);
+    const double gg2 = fma(-s, b1, b2) / t;
+    *s_out = s;
+    *piv = t;
+    *g2 = gg2;
+    *g1 = fma(-a12, gg2, b1) / a11;
 }
 
 __device__ __forceinline__ double step_l2_u(double r, double u, double beta)              // u_i = r_i - beta u_i

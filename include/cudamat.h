@@ -86,6 +86,7 @@ extern "C" {
                                      *        u1 = r1 - beta u1; u2 = A^ u1; gamma = u2.r~; alpha = rho0/gamma
                                      *        r0 -= alpha u1; r1 -= alpha u2; y += alpha u0; r2 = A^ r1
                                      *   MR:  [[r1.r1, r1.r2], [r1.r2, r2.r2]] (g1, g2) = (r1.r0, r2.r0)
+                                     *        (by elimination on r1.r1, not by Cramer's rule: exact under scaling by 2^k)
                                      *        y += g1 r0 + g2 r1; u0 -= g1 u1 + g2 u2; r0 -= g1 r1 + g2 r2; omega = g2
                                      * ||r0|| < tol ||r~|| after the MR step is the only stopping test; the history has one
                                      * entry per sweep.  With a preconditioner x = x0 + M^-1 y is formed after the loop (one

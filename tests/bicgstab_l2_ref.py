@@ -9,7 +9,9 @@ preconditioning; A^ = A without M^-1):
             u1 = A^ u0 ; gamma = u1.r~ ; alpha = rho0 / gamma ; r0 -= alpha u1 ; y += alpha u0 ; r1 = A^ r0
     j = 1:  rho1 = r1.r~ ; beta = alpha rho1 / rho0 ; rho0 = rho1 ; u0 = r0 - beta u0 ; u1 = r1 - beta u1
             u2 = A^ u1 ; gamma = u2.r~ ; alpha = rho0 / gamma ; r0 -= alpha u1 ; r1 -= alpha u2 ; y += alpha u0 ; r2 = A^ r1
-    MR:     [[r1.r1, r1.r2], [r1.r2, r2.r2]] (g1, g2) = (r1.r0, r2.r0)   by Cramer's rule
+    MR:     [[r1.r1, r1.r2], [r1.r2, r2.r2]] (g1, g2) = (r1.r0, r2.r0)   by Cramer's rule HERE (the kernel eliminates on r1.r1,
+            csrc/steps.h step_l2_mr: this file is an independent statement, compared to 1e-6, in range only -- the determinant
+            leaves the range of a double under scalings the kernel survives)
             y += g1 r0 + g2 r1 ; u0 -= g1 u1 + g2 u2 ; r0 -= g1 r1 + g2 r2 ; omega = g2
             ||r0|| < tol ||r_init||: the only stopping test, one history entry per iteration
 

@@ -18,6 +18,8 @@ stored.  Run:  python tests/golden/make_golden.py
   cg_pinned.npz     : x and the residual history of every case that tests/test_gpu_cg_bits.py pins, as the CPU mirror of
                       CUDAMAT_LOOP_CG (tests/test_cg_rounding.py) computes them; needs neither the reference nor a GPU.
                       Run:  python tests/golden/make_golden.py cg_pinned
+  l2_pinned.npz     : the same for CUDAMAT_LOOP_BICGSTAB_L2: every case that tests/test_gpu_l2_bits.py pins, as the CPU mirror
+                      tests/test_l2_rounding.py computes them.  Run:  python tests/golden/make_golden.py l2_pinned
 """
 import ctypes as C
 import os
@@ -87,8 +89,18 @@ def cg_pinned():
     print("cg_pinned", len(values), "arrays")
 
 
+def l2_pinned():
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_l2_rounding as T
+    values = T.recorded_values()
+    np.savez_compressed(os.path.join(HERE, "l2_pinned.npz"), **values)
+    print("l2_pinned", len(values), "arrays")
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["cg_pinned"]:
         cg_pinned()
+    elif sys.argv[1:] == ["l2_pinned"]:
+        l2_pinned()
     else:
         main()
