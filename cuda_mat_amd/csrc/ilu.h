@@ -73,7 +73,7 @@ struct IluPlans {
     // numeric-only refactorisation (ilu0_refactor): where in `lu` every stored value of a SPLIT factor comes from, one int per
     // entry -- the near parts in their own order, the far plans' pv in (column block, row block, row, column) order up to
     // cstart[NCB] (-1: an alignment pad, which stays 0.0).  Built at the first refactor, nothing before; unsplit factors
-    // need none (k_fill_factor over the kept row pointers is their refresh).
+    // need none (k_fill_factor<1> over the kept row pointers is their refresh).
     struct FactorSrc {
         cm::DevBuf<int> near;
         std::vector<cm::DevBuf<int>> far;           // far[g] beside TriHost::far[g] (empty where that plan is)

@@ -20,9 +20,14 @@
 //                       levels -- the reference form the others are bit-identical to, and the fallback when a
 //                       dependency-driven solve times out (another spinning kernel on the same GPU).
 // Block-Jacobi (row-sharded runs): the same machinery on the rank's diagonal block (select_precond_matrix).
-// A new shift on a kept solver: ilu0_refactor recomputes the numbers only (ilu0_numeric + the value refresh, end of this file).
-// K shifted matrices at once (cudamat_solver_solve_shifts_ilu0): ilu0_numeric_cols -- k_ilu0_init_cols, k_ilu0_level_cols<K, WAVES>,
-// k_fill_factor_cols -- factors A0 + diag(D_c), c < K, in one pass over the shared pattern, values interleaved.
+// The numbers of the factors: one launch loop (launch_ilu0_levels) over a level kernel, one way to report a zero
+// pivot (note_zero_pivot), then k_fill_factor<K> into the level-major storage.  The level kernels: k_ilu0_level<K, WAVES>,
+// prefetching, for K value columns; k_ilu0_level_fast<4>, its single-column form with the pivots staged in LDS, which the
+// set-up and ilu0_refactor keep because it measures 6 % faster than k_ilu0_level<1, 4>; k_ilu0_level_simple<WAVES>,
+// unstaged, for rows too long for the tables and as the form the others are compared with (ILU0_SIMPLE = 1).
+// A new shift on a kept solver: ilu0_refactor recomputes the numbers only (ilu0_numeric + the value refresh, end of
+// this file).  K shifted matrices at once (cudamat_solver_solve_shifts_ilu0): ilu0_numeric_cols -- k_ilu0_init_cols<K>,
+// then the same loop and fill at K -- factors A0 + diag(D_c), c < K, in one pass over the shared pattern, values interleaved.
 // Algorithmic bytes per preconditioner application: 12 nnz + 8 (n+1) + 32 n.
 #include <algorithm>
 #include <vector>
@@ -191,7 +196,10 @@ __global__ __launch_bounds__(kBlock) void k_levels_dep(int n, const int *rp, con
   }
 }
 
-// copy one triangular part of the combined LU values into level-major storage
+// copy one triangular part of the combined LU values (K interleaved columns, lu[p*K + c]) into level-major storage:
+// fval[(o + k)*K + c], and for U dinv[pr*K + c] = 1 / its diagonal (one division, one rounding).  fci: the column ids beside
+// them, or null where the pattern side is already stored (the K-wide factors share the solver's own).  8 lanes per row.
+template <int K>
 __global__ __launch_bounds__(kBlock) void k_fill_factor(int n, const int *rp, const int *ci, const double *lu,
                                                         const int *diag_pos, int upper, const int *row_of,
                                                         const int *frp, int *fci, double *fval, double *dinv)
@@ -205,22 +213,42 @@ __global__ __launch_bounds__(kBlock) void k_fill_factor(int n, const int *rp, co
     const int e = upper ? rp[r + 1] : diag_pos[r];
     const int o = frp[pr];
     for (int k = lane; k < e - s; k += L) {
-        fci[o + k] = ci[s + k];
-        fval[o + k] = lu[s + k];
+        if (fci) fci[o + k] = ci[s + k];
+        double v[K];
+        load_row<K>(lu, s + k, v);
+        store_row<K>(fval, o + k, v, kAll);
     }
-    if (upper && lane == 0) dinv[pr] = 1.0 / lu[diag_pos[r]];
+    if (upper && lane == 0) {
+        double v[K];
+        load_row<K>(lu, diag_pos[r], v);
+#pragma unroll
+        for (int c = 0; c < K; c++) v[c] = 1.0 / v[c];
+        store_row<K>(dinv, pr, v, kAll);
+    }
 }
 
 // ---------------------------------------------------------------- numeric ILU(0)
+// Where the level kernels report a zero pivot; exactly one of the two words is given.
+struct ZeroPivotReport {
+    int *max_row;                    // the single-column factorisation: the LARGEST row + 1 (the word k_find_diag reports in, too)
+    unsigned long long *min_pair;    // the K-wide one: the SMALLEST (column << 32 | row)
+};
+__device__ __forceinline__ void note_zero_pivot(const ZeroPivotReport &report, int c, int row)
+{
+    if (report.max_row) atomicMax(report.max_row, row + 1);
+    else atomicMin(report.min_pair, ((unsigned long long)c << 32) | (unsigned)row);
+}
+
 // One wavefront per row of the current level (IKJ ordering).  The row's values are staged in LDS
 // (this wave's slice), where the wave's own in-order DS pipeline makes every update visible to the
 // next elimination step without any global-memory round trip; the pivot rows k < i belong to
 // earlier levels and are final in HBM.  Row k's entries right of its diagonal are spread over the
 // 64 lanes, each finds its column in row i by binary search (columns are sorted).
+// This is the unstaged form: rows beyond kIluPrefetchCap entry slots, and ILU0_SIMPLE = 1 (the comparison form).
 template <int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void k_ilu0_level(int row_begin, int row_end, const int *row_of,
-                                                          const int *rp, const int *ci, const int *diag_pos,
-                                                          double *lu, int cap, int *flags)
+__global__ __launch_bounds__(64 * WAVES) void k_ilu0_level_simple(int row_begin, int row_end, const int *row_of,
+                                                                 const int *rp, const int *ci, const int *diag_pos,
+                                                                 double *lu, int cap, ZeroPivotReport report)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -237,7 +265,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_ilu0_level(int row_begin, int ro
         const int k = ci[rs + kk];
         const int dk = diag_pos[k];
         const double piv = lu[dk];
-        if (piv == 0.0 && lane == 0) atomicMax(&flags[1], k + 1);
+        if (piv == 0.0 && lane == 0) note_zero_pivot(report, 0, k);
         const double lik = sv[kk] / piv;                 // every lane reads the same LDS word
         __builtin_amdgcn_wave_barrier();
         if (lane == 0) sv[kk] = lik;
@@ -254,7 +282,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_ilu0_level(int row_begin, int ro
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
-    if (nlow >= 0 && sv[nlow] == 0.0 && lane == 0) atomicMax(&flags[1], i + 1);   // zero pivot of row i
+    if (nlow >= 0 && sv[nlow] == 0.0 && lane == 0) note_zero_pivot(report, 0, i);   // zero pivot of row i
     for (int q = lane; q < len; q += 64) lu[rs + q] = sv[q];
 }
 
@@ -263,10 +291,14 @@ __global__ __launch_bounds__(64 * WAVES) void k_ilu0_level(int row_begin, int ro
 // row k, pivot value) are staged in LDS up front by all lanes at once, the binary search runs on the LDS copy of
 // the columns, and the entries of pivot row kk+1 are fetched while pivot kk is being applied.  Per pivot the
 // chain is then one LDS round trip instead of ~10 dependent global loads (C5: 169 -> 77 ms for the 137 levels).
+// This is k_ilu0_level<1, WAVES> below but for one point: the pivot values are staged in LDS (mp[], 8 more bytes per slot)
+// where that kernel loads each pivot one step ahead into a register.  Kept for the single-column path because the register
+// form measured 6 % slower there (ilu0_refactor on random 1e6 x 50: 8.06 against 7.60 ms; HISTORY.md, "Numeric ILU(0): one
+// launch loop").  Every rule about contraction and operation order holds in both bodies; test_factors_bit_for_bit ties them.
 template <int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void k_ilu0_level_fast(int row_begin, int row_end, const int *row_of,
                                                                const int *rp, const int *ci, const int *diag_pos,
-                                                               double *lu, int cap, int *flags)
+                                                               double *lu, int cap, ZeroPivotReport report)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -321,7 +353,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_ilu0_level_fast(int row_begin, i
                 un = lu[ppn];
             }
         }
-        if (piv == 0.0 && lane == 0) atomicMax(&flags[1], sc[kk] + 1);
+        if (piv == 0.0 && lane == 0) note_zero_pivot(report, 0, sc[kk]);
         const double lik = sv[kk] / piv;
         __builtin_amdgcn_wave_barrier();
         if (lane == 0) sv[kk] = lik;
@@ -348,7 +380,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_ilu0_level_fast(int row_begin, i
         j = jn;
         u = un;
     }
-    if (nlow >= 0 && sv[nlow] == 0.0 && lane == 0) atomicMax(&flags[1], i + 1);   // zero pivot of row i
+    if (nlow >= 0 && sv[nlow] == 0.0 && lane == 0) note_zero_pivot(report, 0, i);   // zero pivot of row i
     for (int q = lane; q < len; q += 64) lu[rs + q] = sv[q];
 }
 
@@ -357,15 +389,16 @@ __global__ __launch_bounds__(64 * WAVES) void k_ilu0_level_fast(int row_begin, i
 // differ.  Values are interleaved as the vectors of batch.h are: lu[p*K + c].  One wave per row of the level, as above; the
 // row's K value columns are staged in LDS (sv[q*K + c]), its column ids and the per-pivot tables (position of the pivot's
 // diagonal, end of the pivot's row) once.  Per pivot-row entry a lane does ONE binary search and then K updates.  Per entry
-// and column the operations are those of k_ilu0_level / k_ilu0_level_fast in the same order -- lik = sv / piv, then for every
+// and column the operations are those of k_ilu0_level_simple / k_ilu0_level_fast in the same order -- lik = sv / piv, then for every
 // pivot at most one sv -= lik * u, written as there so that it contracts as there -- hence column c carries the bits of the
-// single-column factorisation of A0 + diag(D_c).  As in the fast kernel the entries and the pivot of pivot row kk + 1 are in
-// flight while pivot kk is applied (they belong to earlier levels and are final).
-// LDS per wave: cap * (8 K + 12) bytes (trsm.h: ilu0_cols_waves).  zp: the smallest (column << 32 | row) with a zero pivot.
+// single-column factorisation of A0 + diag(D_c).  As in the fast kernel the entries of pivot row kk + 1 are in flight while
+// pivot kk is applied (they belong to earlier levels and are final); the pivot itself is not staged in LDS but loaded with them
+// into registers (8 bytes per slot less, which is what ilu0_cols_max_row rests on).
+// LDS per wave: cap * (8 K + 12) bytes (trsm.h: ilu0_slot_bytes, ilu0_cols_waves).
 template <int K, int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void k_ilu0_level_cols(int row_begin, int row_end, const int *row_of, const int *rp,
-                                                               const int *ci, const int *diag_pos, double *lu, int cap,
-                                                               unsigned long long *zp)
+__global__ __launch_bounds__(64 * WAVES) void k_ilu0_level(int row_begin, int row_end, const int *row_of, const int *rp,
+                                                          const int *ci, const int *diag_pos, double *lu, int cap,
+                                                          ZeroPivotReport report)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -427,7 +460,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_ilu0_level_cols(int row_begin, i
         load_row<K>(sv, kk, lik);                        // every lane reads the same LDS words
 #pragma unroll
         for (int c = 0; c < K; c++) {
-            if (piv[c] == 0.0 && lane == 0) atomicMin(zp, ((unsigned long long)c << 32) | (unsigned)sc[kk]);
+            if (piv[c] == 0.0 && lane == 0) note_zero_pivot(report, c, sc[kk]);
             lik[c] = lik[c] / piv[c];
         }
         __builtin_amdgcn_wave_barrier();
@@ -477,7 +510,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_ilu0_level_cols(int row_begin, i
         load_row<K>(sv, nlow, dv);
 #pragma unroll
         for (int c = 0; c < K; c++)
-            if (dv[c] == 0.0) atomicMin(zp, ((unsigned long long)c << 32) | (unsigned)i);
+            if (dv[c] == 0.0) note_zero_pivot(report, c, i);
     }
     for (int q = lane; q < len; q += 64) {
         double v[K];
@@ -510,35 +543,6 @@ __global__ __launch_bounds__(kBlock) void k_ilu0_init_cols(int n, const int *rp,
             for (int c = 0; c < K; c++) v[c] = a + D[(size_t)(c < kc ? c : kc - 1) * (size_t)ldd + (size_t)i];
         }
         store_row<K>(lu, p, v, kAll);
-    }
-}
-
-// k_fill_factor's job for K value columns: one triangular part of lu into level-major order, fval[(o + k)*K + c], and
-// dinv[pr*K + c] = 1 / U's diagonal (the expression of k_fill_factor: one division, one rounding).  The pattern side (frp,
-// row_of; the column ids are not written again) is the solver's own.
-template <int K>
-__global__ __launch_bounds__(kBlock) void k_fill_factor_cols(int n, const int *rp, const double *lu, const int *diag_pos, int upper,
-                                                            const int *row_of, const int *frp, double *fval, double *dinv)
-{
-    constexpr int L = 8;
-    const int lane = threadIdx.x & (L - 1);
-    const long long pr = ((long long)blockIdx.x * kBlock + threadIdx.x) / L;
-    if (pr >= n) return;
-    const int r = row_of[pr];
-    const int s = upper ? diag_pos[r] + 1 : rp[r];
-    const int e = upper ? rp[r + 1] : diag_pos[r];
-    const int o = frp[pr];
-    for (int k = lane; k < e - s; k += L) {
-        double v[K];
-        load_row<K>(lu, s + k, v);
-        store_row<K>(fval, o + k, v, kAll);
-    }
-    if (upper && lane == 0) {
-        double v[K];
-        load_row<K>(lu, diag_pos[r], v);
-#pragma unroll
-        for (int c = 0; c < K; c++) v[c] = 1.0 / v[c];
-        store_row<K>(dinv, pr, v, kAll);
     }
 }
 
@@ -1247,7 +1251,7 @@ static int fill_factor(cudamat_solver *s, bool upper, TriFactor &F)
     if (!n) return CUDAMAT_OK;
     const long long threads = (long long)n * 8;
     const unsigned grid = (unsigned)((threads + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_fill_factor, dim3(grid), dim3(kBlock), 0, s->ctx->stream, n, s->pm_rp, s->pm_ci, s->lu,
+    hipLaunchKernelGGL(k_fill_factor<1>, dim3(grid), dim3(kBlock), 0, s->ctx->stream, n, s->pm_rp, s->pm_ci, s->lu,
                        s->diag_pos, upper ? 1 : 0, F.row_of, F.rp, F.ci, F.val, F.dinv);
     CM_HIP(hipGetLastError());
     return CUDAMAT_OK;
@@ -1478,6 +1482,39 @@ int ilu0_setup(cudamat_solver *s, bool block, const double *d_factor, bool keep_
     return CUDAMAT_OK;
 }
 
+// The level launches of a numeric factorisation, one per level of L: lu holds K interleaved value columns on the matrix's
+// pattern and is eliminated in place.  FORM: k_ilu0_level<K, WAVES>, or at K = 1 one of the set-up's two other kernels.  Rows
+// (waves) per workgroup: as trsm.h's LDS formula allows; the simple kernel four up to 2048 slots and one beyond.  LDS per entry
+// slot and wave: trsm.h's ilu0_slot_bytes; the fast kernel 8 bytes more (mp[]); the simple one the 8 bytes of the value alone.
+enum class IluForm { wide, fast, simple };
+template <int K, IluForm FORM>
+static int launch_ilu0_levels(cudamat_solver *s, double *lu, int maxrow, ZeroPivotReport report)
+{
+    static_assert(K == 1 || FORM == IluForm::wide, "the set-up's other two level kernels take one column");
+    using LevelKernel = void (*)(int, int, const int *, const int *, const int *, const int *, double *, int, ZeroPivotReport);
+    const int cap = ilu0_cols_cap(maxrow);
+    const size_t slot = FORM == IluForm::simple ? sizeof(double) : ilu0_slot_bytes(K) + (FORM == IluForm::fast ? sizeof(double) : 0);
+    const int waves = FORM == IluForm::wide ? ilu0_cols_waves(K, maxrow) : FORM == IluForm::fast || cap <= 2048 ? 4 : 1;
+    if (waves < 1 || (size_t)waves * (size_t)cap * slot > kIluLdsBudget) {
+        set_error("ILU(0): a row with %d entries does not fit the LDS staging of %d column(s)", maxrow, K);
+        return CUDAMAT_ERR_ARG;
+    }
+    const size_t lds = (size_t)waves * (size_t)cap * slot;
+    LevelKernel kernel;
+    if constexpr (FORM == IluForm::simple) kernel = waves == 4 ? k_ilu0_level_simple<4> : k_ilu0_level_simple<1>;
+    else if constexpr (FORM == IluForm::fast) kernel = k_ilu0_level_fast<4>;
+    else kernel = waves == 4 ? k_ilu0_level<K, 4> : waves == 2 ? k_ilu0_level<K, 2> : k_ilu0_level<K, 1>;
+    CM_TRY(set_max_lds((const void *)kernel));
+    for (int l = 0; l < s->L.nlevels; l++) {
+        const int r0 = s->L.level_ptr[(size_t)l], r1 = s->L.level_ptr[(size_t)l + 1];
+        const int rows = r1 - r0;
+        if (rows <= 0) continue;
+        hipLaunchKernelGGL(kernel, dim3((rows + waves - 1) / waves), dim3(64 * waves), lds, s->ctx->stream, r0, r1, s->L.row_of,
+                           s->pm_rp, s->pm_ci, s->diag_pos, lu, cap, report);
+    }
+    return CUDAMAT_OK;
+}
+
 // The NUMBERS of the factorisation: lu = the matrix's values (+ d_factor on the diagonal), eliminated level by level.  Needs the
 // analysis (diag_pos, L's levels, the longest row) and two ints of device scratch; shared by the set-up and by ilu0_refactor,
 // which therefore run the same kernels in the same launch shapes.
@@ -1506,32 +1543,16 @@ static int ilu0_numeric(cudamat_solver *s, int *d_flags, int maxrow_all, const d
     } else {
         s->ilu_d.reset();                   // (a refactorisation without a kept shift: the copy of the previous one goes)
     }
-    const int maxrow = maxrow_all;
-    const int cap = ((maxrow + 63) / 64) * 64 + 64;
-    const bool one_wave = cap > 2048;
-    const bool fast = cap <= 1024 && !s->ctx->cfg.ilu0_simple;
-    if ((size_t)cap * sizeof(double) > 150 * 1024) {
-        set_error("ILU(0): a row with %d entries exceeds the %d-entry LDS staging limit", maxrow, 150 * 1024 / 8);
+    const int cap = ilu0_cols_cap(maxrow_all);
+    if ((size_t)cap * sizeof(double) > kIluLdsBudget) {
+        set_error("ILU(0): a row with %d entries exceeds the %d-entry LDS staging limit", maxrow_all, (int)(kIluLdsBudget / sizeof(double)));
         return CUDAMAT_ERR_ARG;
     }
     if (hipMemsetAsync(d_flags, 0, 2 * sizeof(int), st) != hipSuccess) return CUDAMAT_ERR_HIP;
-    CM_TRY(set_max_lds((const void *)k_ilu0_level<1>));
-    CM_TRY(set_max_lds((const void *)k_ilu0_level<4>));
-    CM_TRY(set_max_lds((const void *)k_ilu0_level_fast<4>));
-    for (int l = 0; l < s->L.nlevels; l++) {
-        const int r0 = s->L.level_ptr[(size_t)l], r1 = s->L.level_ptr[(size_t)l + 1];
-        const int rows = r1 - r0;
-        if (fast) {     // 28 bytes of LDS per entry slot and wave: values, pivots, columns, two pivot tables
-            hipLaunchKernelGGL(k_ilu0_level_fast<4>, dim3((rows + 3) / 4), dim3(256), (size_t)28 * 4 * (size_t)cap, st,
-                               r0, r1, s->L.row_of, s->pm_rp, s->pm_ci, s->diag_pos, s->lu, cap, d_flags);
-        } else if (one_wave) {
-            hipLaunchKernelGGL(k_ilu0_level<1>, dim3(rows), dim3(64), sizeof(double) * (size_t)cap, st, r0, r1,
-                               s->L.row_of, s->pm_rp, s->pm_ci, s->diag_pos, s->lu, cap, d_flags);
-        } else {
-            hipLaunchKernelGGL(k_ilu0_level<4>, dim3((rows + 3) / 4), dim3(256), sizeof(double) * 4 * (size_t)cap, st,
-                               r0, r1, s->L.row_of, s->pm_rp, s->pm_ci, s->diag_pos, s->lu, cap, d_flags);
-        }
-    }
+    const ZeroPivotReport report{d_flags + 1, nullptr};
+    const bool fast = cap <= kIluPrefetchCap && !s->ctx->cfg.ilu0_simple;
+    CM_TRY(fast ? (launch_ilu0_levels<1, IluForm::fast>(s, s->lu, maxrow_all, report))
+                : (launch_ilu0_levels<1, IluForm::simple>(s, s->lu, maxrow_all, report)));
     if (hipGetLastError() != hipSuccess) { set_error("ilu0 launch failed"); return CUDAMAT_ERR_HIP; }
     if (hipMemcpyAsync(hflags, d_flags, sizeof(hflags), hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess) { set_error("ilu0 failed"); return CUDAMAT_ERR_HIP; }
@@ -1560,30 +1581,12 @@ static int ilu0_numeric_cols_k(cudamat_solver *s, IluPlans *pl, int kc, const do
     const int n = s->n;
     const unsigned grid8 = (unsigned)(((long long)n * 8 + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_ilu0_init_cols<K>, dim3(grid8), dim3(kBlock), 0, st, n, s->pm_rp, s->diag_pos, s->pm_val, D, ldd, kc, f.lu);
-    const int cap = ilu0_cols_cap(pl->maxrow_all);
-    const int waves = ilu0_cols_waves(K, pl->maxrow_all);
-    const size_t lds = (size_t)waves * (size_t)cap * (size_t)(8 * K + 12);
-    CM_TRY(set_max_lds((const void *)k_ilu0_level_cols<K, 1>));
-    CM_TRY(set_max_lds((const void *)k_ilu0_level_cols<K, 2>));
-    CM_TRY(set_max_lds((const void *)k_ilu0_level_cols<K, 4>));
-    for (int l = 0; l < s->L.nlevels; l++) {
-        const int r0 = s->L.level_ptr[(size_t)l], r1 = s->L.level_ptr[(size_t)l + 1];
-        const int rows = r1 - r0;
-        if (rows <= 0) continue;
-        if (waves == 4)
-            hipLaunchKernelGGL((k_ilu0_level_cols<K, 4>), dim3((rows + 3) / 4), dim3(256), lds, st, r0, r1, s->L.row_of, s->pm_rp, s->pm_ci,
-                               s->diag_pos, f.lu, cap, zp);
-        else if (waves == 2)
-            hipLaunchKernelGGL((k_ilu0_level_cols<K, 2>), dim3((rows + 1) / 2), dim3(128), lds, st, r0, r1, s->L.row_of, s->pm_rp, s->pm_ci,
-                               s->diag_pos, f.lu, cap, zp);
-        else
-            hipLaunchKernelGGL((k_ilu0_level_cols<K, 1>), dim3(rows), dim3(64), lds, st, r0, r1, s->L.row_of, s->pm_rp, s->pm_ci,
-                               s->diag_pos, f.lu, cap, zp);
-    }
-    hipLaunchKernelGGL(k_fill_factor_cols<K>, dim3(grid8), dim3(kBlock), 0, st, n, s->pm_rp, f.lu, s->diag_pos, 0, s->L.row_of, s->L.rp,
-                       f.lval, (double *)nullptr);
-    hipLaunchKernelGGL(k_fill_factor_cols<K>, dim3(grid8), dim3(kBlock), 0, st, n, s->pm_rp, f.lu, s->diag_pos, 1, s->U.row_of, s->U.rp,
-                       f.uval, f.dinv);
+    CM_TRY((launch_ilu0_levels<K, IluForm::wide>(s, f.lu, pl->maxrow_all, ZeroPivotReport{nullptr, zp})));
+    // (the column ids of the factors are the solver's own: none are written)
+    hipLaunchKernelGGL(k_fill_factor<K>, dim3(grid8), dim3(kBlock), 0, st, n, s->pm_rp, s->pm_ci, f.lu, s->diag_pos, 0, s->L.row_of,
+                       s->L.rp, (int *)nullptr, f.lval, (double *)nullptr);
+    hipLaunchKernelGGL(k_fill_factor<K>, dim3(grid8), dim3(kBlock), 0, st, n, s->pm_rp, s->pm_ci, f.lu, s->diag_pos, 1, s->U.row_of,
+                       s->U.rp, (int *)nullptr, f.uval, f.dinv);
     return CUDAMAT_OK;
 }
 
@@ -1884,7 +1887,7 @@ static int refactor_maps_of(cudamat_solver *s, bool upper, const TriFactor &F, c
     CM_TRY(fci.alloc((size_t)fnnz));
     CM_TRY(fval.alloc((size_t)fnnz));
     if (upper) CM_TRY(dinv_unused.alloc((size_t)n));
-    if (n) hipLaunchKernelGGL(k_fill_factor, dim3(gp8), dim3(kBlock), 0, st, n, s->pm_rp, s->pm_ci, tags, s->diag_pos, upper ? 1 : 0,
+    if (n) hipLaunchKernelGGL(k_fill_factor<1>, dim3(gp8), dim3(kBlock), 0, st, n, s->pm_rp, s->pm_ci, tags, s->diag_pos, upper ? 1 : 0,
                        F.row_of, frp, fci, fval, dinv_unused);
     CM_HIP(hipGetLastError());
     SplitParts sp;

@@ -25,16 +25,21 @@ int precond_apply_b(cudamat_solver *s, int K, const double *in, double *tmp, dou
 struct ColFactors {
     double *lu = nullptr, *lval = nullptr, *uval = nullptr, *dinv = nullptr;
 };
-// The longest row a K-wide factorisation stages in LDS (the one place that says so): per wave and entry slot 8 K bytes of values
-// and 12 bytes of tables (column id, the pivot's diagonal position, the end of its row), cap = the row rounded up to 64 plus
-// 64 slots, against the 150 KiB the single-column kernels ask of the 160 KiB of a CU.  K = 1, 2, 4, 8: 7616, 5376, 3392, 1920.
+// The LDS the numeric ILU(0) stages a row in (the one place that says so; ilu.hip: launch_ilu0_levels).  Per wave and entry
+// slot 8 K bytes of values and 12 bytes of tables (column id, the pivot's diagonal position, the end of its row), cap = the row
+// rounded up to 64 plus 64 slots, against 150 KiB of the 160 KiB of a CU.  The longest row a K-wide factorisation stages,
+// K = 1, 2, 4, 8: 7616, 5376, 3392, 1920.
 constexpr size_t kIluLdsBudget = 150 * 1024;
+// the single-column set-up and refactorisation take a prefetching kernel up to this many entry slots (cap), beyond it the
+// unstaged one (k_ilu0_level_simple: 8 bytes per slot, rows up to kIluLdsBudget / 8 entries)
+constexpr int kIluPrefetchCap = 1024;
+inline size_t ilu0_slot_bytes(int K) { return (size_t)(8 * K + 12); }
 inline int ilu0_cols_cap(int maxrow) { return ((maxrow + 63) / 64) * 64 + 64; }
-inline int ilu0_cols_max_row(int K) { return (int)(kIluLdsBudget / (size_t)(8 * K + 12)) / 64 * 64 - 64; }
+inline int ilu0_cols_max_row(int K) { return (int)(kIluLdsBudget / ilu0_slot_bytes(K)) / 64 * 64 - 64; }
 // waves (rows) per workgroup for that K and row length: 4, 2 or 1; 0: the row does not fit, the block runs column by column
 inline int ilu0_cols_waves(int K, int maxrow)
 {
-    const size_t per_wave = (size_t)ilu0_cols_cap(maxrow) * (size_t)(8 * K + 12);
+    const size_t per_wave = (size_t)ilu0_cols_cap(maxrow) * ilu0_slot_bytes(K);
     const size_t w = kIluLdsBudget / per_wave;
     return w >= 4 ? 4 : w >= 2 ? 2 : (int)w;
 }

@@ -355,6 +355,39 @@ def test_zero_pivot_and_refusals(cm, ctx, oracle, golden_dir):
         dd1.free()
 
 
+def test_zero_pivot_names_the_row(cm, ctx, sw):
+    """Two diagonal blocks [[1, 1], [1, 1]]: rows 1 and 3 both eliminate to an exact 0.0 and neither depends on the other, so no
+    NaN hides either.  The single-column factorisation names the LARGEST such row, with the prefetching and with the simple level
+    kernel; the K-wide one (ilu0_shifts_values on the kept structure, a zero shift in both columns) the smallest (column, row)."""
+    rowptr = np.array([0, 2, 4, 6, 8], np.int32)
+    colidx = np.array([0, 1, 0, 1, 2, 3, 2, 3], np.int32)
+    val, n = np.ones(8), 4
+    for simple in ("0", "1"):
+        sw("ILU0_SIMPLE", simple)
+        s = cm.Solver.from_host_csr(ctx, rowptr, colidx, val)
+        try:
+            with pytest.raises(cm.CudamatError) as e:
+                s.ilu0()
+        finally:
+            s.close()
+        print(e.value)
+        assert e.value.code == ERR_ZERO_PIVOT and str(e.value).endswith("zero pivot in row 3"), str(e.value)
+    sw("ILU0_SIMPLE", "0")
+    sw("MANY_PRECOND", "batched")
+    s = cm.Solver.from_host_csr(ctx, rowptr, colidx, val)
+    good, dD = ctx.array(np.ones(n)), ctx.array(np.zeros(2 * n))
+    try:
+        s.ilu0(shift=good)                                  # [[2, 1], [1, 2]]: the structure the K-wide pass works on
+        with pytest.raises(cm.CudamatError) as e:
+            s.ilu0_shifts_values(2, dD, n)
+    finally:
+        s.close()
+        good.free()
+        dD.free()
+    print(e.value)
+    assert e.value.code == ERR_ZERO_PIVOT and str(e.value).endswith("zero pivot in column 0, row 1"), str(e.value)
+
+
 # ------------------------------------------------------------------ 5. the drop-in call
 def test_drop_in_call_refactors_on_a_reused_plan(cm, oracle, golden_dir, monkeypatch, capfd):
     """bicgstab_d_lu_precond on mat900 with d, 8 d, d under VERBOSE = 1: the second and third calls reuse the plan, print the

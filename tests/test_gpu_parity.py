@@ -1128,7 +1128,7 @@ def test_solver_validates_its_csr(cm, ctx, oracle, sw):
 @pytest.mark.parametrize("name", ["mat10000", "rand20000x50", "longrows"])
 def test_ilu0_prefetching_kernel_equals_simple_kernel(cm, ctx, oracle, golden_dir, name, sw):
     """k_ilu0_level_fast (columns, pivot table and next pivot row staged / prefetched) performs the same
-    updates in the same order as k_ilu0_level: bit-identical factors; both within 1e-12 of the oracle"""
+    updates in the same order as k_ilu0_level_simple: bit-identical factors; both within 1e-12 of the oracle"""
     if name == "rand20000x50":
         A = oracle.rand_rows(20000, 50, 0x5EED)
     elif name == "longrows":
@@ -1246,7 +1246,7 @@ def test_stream_spmv_with_compressed_indices(cm, ctx, oracle, case, sw):
 
 @pytest.mark.parametrize("n,longest", [(3000, 1300), (3000, 2500)])
 def test_ilu0_very_long_rows(cm, ctx, oracle, n, longest):
-    """a maximum row length above 1024 entries selects k_ilu0_level<4> (LDS slice per wave), above 2048 the
+    """a maximum row length above 1024 entries selects k_ilu0_level_simple<4> (LDS slice per wave), above 2048 the
     one-wave-per-workgroup launch; factors and L^-1 U^-1 against the oracle.  (A few dense rows among sparse
     ones keep the oracle's O(sum len^2) factorisation cheap.)"""
     import scipy.sparse as sp

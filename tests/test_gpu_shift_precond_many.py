@@ -144,8 +144,9 @@ def _solve_family(cm, ctx, s, D, B, ldd=None, ldb=None, ldx=None, X0=None, **kw)
 # ------------------------------------------------------------------ 1. factors
 @pytest.mark.parametrize("name,nrhs", [(nm, k) for nm in ("mat900", "wide") for k in (1, 2, 3, 5, 8, 9)] + [("few", 1), ("few", 2)])
 def test_factors_bit_for_bit(cm, ctx, oracle, golden_dir, sw, name, nrhs):
-    """column j of ilu0_shifts_values == ilu0(shift = D_j) -> ilu0_values() as raw bits: mat900 (base 1, rows of 7: the set-up's
-    fast kernel), the matrix with wide levels, and `few` (rows of 6000 entries: the set-up's one-wave kernel); nrhs 1, 2, 3, 5, 8,
+    """column j of ilu0_shifts_values (k_ilu0_level<K, WAVES>) == ilu0(shift = D_j) -> ilu0_values() as raw bits: mat900 (base 1,
+    rows of 7: the set-up's k_ilu0_level_fast), the matrix with wide levels, and `few` (rows of 6000 entries: the set-up's
+    one-wave k_ilu0_level_simple<1>); nrhs 1, 2, 3, 5, 8,
     9 = padding to 4 and 8 and a second block.  On `few` a block of one column fits the LDS limit (7616 entries) and a block of
     two does not (5376): the second runs column by column and must give the same bits.  Which form ran shows in the solver's
     own factors afterwards: K-wide leaves them those of D_0 (the structure's set-up), column by column those of the last
